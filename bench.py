@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Headline benchmark: jacobi2d fp32 on an 8192 x 8192 grid, iterate = 100.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--full]
+                  [--dump-outputs DIR]
 
 One "step" = one full pass of the hot path over one batch of synthetic input:
 all 100 iterations of the program on the whole grid, inputs resident in HBM.
@@ -9,7 +10,11 @@ Metric: cells*iters/s (BASELINE.json).  N > 1: launched by torchrun, one rank
 per GPU; the same 8192^2 grid is cut into slabs along the streamed dimension
 (strong scaling) with halo exchange over RCCL (soda_amd/dist.py).
 
-Besides the contract's fields the JSON line carries
+A plain run sets up, spins untimed until the clocks settle, restarts from the
+seeded input, warms up (W steps, then a fixed number of settling steps), times
+K chained steps and prints the JSON line; `--dump-outputs DIR` writes what the
+last timed step computed -- the same bits on every run of the same arguments.
+With `--full` the JSON line also carries
   roofline      HBM roofline of the dominant kernel: algorithmic bytes per
                 launch / its average duration measured here with HIP events on
                 the launch stream;
@@ -19,7 +24,9 @@ Besides the contract's fields the JSON line carries
                 blocking), for the "LDS/register halo tile" config of BASELINE;
   rehearsed_scaling  (N = 1) what an N-GPU job would score if every rank ran
                 its slab at the speed measured here for the middle rank's slab
-                (compute only, no exchange).
+                (compute only, no exchange);
+  other_configs BASELINE's C3 / C4 / C5 on this GPU;
+  parity        the result check of one more step against the CPU oracle.
 
 N > 1 under torchrun: every step opens with a halo exchange; `--overlap auto`
 (default) times a few steps with the exchange hidden under the compute
@@ -38,6 +45,15 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0   # MI355X HBM3E spec peak (MI355X_MICROARCH.md)
+# --dump-outputs: cells per output array at most (4 Mi: 16 MiB as float32),
+# and bytes of all outputs together at most
+DUMP_CELLS = 1 << 22
+DUMP_BYTES = 48 << 20
+DUMP_SEED = 1234
+# untimed chained steps after the restart from the seeded input, on top of
+# --warmup, counted in iterations: the timed steps run on a field smoothed as
+# far as in the sustained runs of earlier versions (500 steps of the headline)
+SETTLE_ITERATIONS = 50000
 
 
 def parse_args():
@@ -98,7 +114,23 @@ def parse_args():
                   'the timed region, ~2 s)')
   ap.add_argument('--cpu-seconds', type=float, default=12.0,
                   help='target CPU time of the cpu_baseline sample')
-  return ap.parse_args()
+  ap.add_argument('--full', action='store_true',
+                  help='besides the headline, measure and check everything '
+                  'else: roofline of every scheduled kernel, result check '
+                  'against the CPU oracle, single_iter, C3 / C4 / C5, '
+                  'rehearsed scaling, CPU baseline (the --no-* options drop '
+                  'single legs of it)')
+  ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                  help='after the timed steps, write what the last of them '
+                  'computed as DIR/<output>.npy (float32, or float64 for '
+                  'other cell types): the valid box of each output array, or '
+                  'where that exceeds %d cells a fixed seeded sample of it '
+                  '(the same cells on every run of the same arguments)' %
+                  DUMP_CELLS)
+  args = ap.parse_args()
+  if args.steps < 1:
+    ap.error('--steps must be at least 1')
+  return args
 
 
 def time_events(fn, stream, repeats):
@@ -111,6 +143,31 @@ def time_events(fn, stream, repeats):
     fn()
   stop.record(stream)
   return start.elapsed_ms(stop) / repeats
+
+
+def dump_outputs(path, stencil, extent, iterate, arrays):
+  """--dump-outputs: `arrays` = the program's output arrays over the whole
+  grid (dim-0-fastest tensors), as a step of `iterate` iterations left them.
+  Writes DIR/<output>.npy: the valid box of the output, or, where the box
+  holds more than `most` cells, the cells at `most` positions drawn from it
+  with a fixed seed (duplicates dropped, in memory order) -- a 1-D array
+  then."""
+  import numpy as np
+  import torch
+  os.makedirs(path, exist_ok=True)
+  most = min(DUMP_CELLS, DUMP_BYTES // (8 * len(arrays)))
+  for t, name, typ in zip(arrays, stencil.output_names, stencil.output_types):
+    lo, hi = stencil.valid_box(extent, name, iterate)
+    box = t[tuple(slice(l, h) for l, h in zip(lo[::-1], hi[::-1]))]
+    if box.numel() > most:
+      rng = np.random.default_rng(DUMP_SEED)
+      flat = np.unique(rng.integers(0, box.numel(), most))
+      at = tuple(torch.from_numpy(np.ascontiguousarray(c)).to(t.device)
+                 for c in np.unravel_index(flat, tuple(box.shape)))
+      box = box[at]
+    cells = box.contiguous().cpu().numpy().view(typ.np_name)
+    out = cells.astype(np.float32 if cells.dtype == np.float32 else np.float64)
+    np.save(os.path.join(path, '%s.npy' % name), out)
 
 
 def cpu_baseline(stencil, extent, target_seconds):
@@ -364,7 +421,7 @@ def group_main(args):
     cells *= e
   table = stencil.symbol_table
   parity = None
-  if not args.no_parity:
+  if args.full and not args.no_parity:
     # the same result check as the rank-per-GPU path: two chained steps from
     # the seeded input (the second opens with the exchange), gathered by the
     # library, against the CPU oracle (test infrastructure, the checker only)
@@ -511,6 +568,9 @@ def main():
   # a no-op when it is newer than its sources
   import __graft_entry__ as entry
   entry.build_library()
+  if args.dump_outputs and (args.group or args.emulate_slab > 1):
+    raise SystemExit('bench.py: --dump-outputs writes the whole grid of the '
+                     'rank-per-GPU path; not with --group or --emulate-slab')
   if args.group:
     return group_main(args)
   if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
@@ -665,10 +725,7 @@ def main():
     if tdist is not None:
       tdist.barrier()
 
-  # ---- roofline of the dominant kernel (this rank's slab), HIP events --------
-  # Measured BEFORE the timed region: it needs no result of it, and its ~60
-  # launches bring the GPU to its sustained clocks, so a short --steps run is
-  # not dominated by the first milliseconds after idle.
+  # ---- the dominant kernel (this rank's slab) --------------------------------
   table = stencil.symbol_table
   bytes_cell = (sum(table[n].size_in_bytes for n in stencil.input_names) +
                 sum(table[n].size_in_bytes for n in stencil.output_names))
@@ -695,143 +752,151 @@ def main():
 
   fuse_deepest = fuse
   fuse = max(sched, key=lambda t: sched[t] * cal_us.get(t, float(t)))
-  per_call = pure_calls(fuse)
-  if prog.schedule(local_extent, fuse * per_call) != {fuse: per_call}:
-    raise SystemExit('cannot time pass T=%d alone' % fuse)
-
-  def dominant():
-    step_fn(b_bufs, a_bufs, local_extent, fuse * per_call)
-
-  def time_pass(depth):
-    n = pure_calls(depth)
-    if prog.schedule(local_extent, depth * n) != {depth: n}:
-      return None
-
-    def go():
-      step_fn(b_bufs, a_bufs, local_extent, depth * n)
-    go()
-    return time_events(go, stream, max(1, 24 // n)) / n
-
-  dominant()
-  torch.cuda.synchronize()
-  calls = max(1, 48 // per_call)
-  reps = calls * per_call
-  kernel_ms = time_events(dominant, stream, calls) / per_call
   passes = [p for p in prog.module.sorted_passes() if p.fused_iters == fuse]
   kname = prog.module.kernels[passes[0].kernels[0]].name if passes else '?'
   alg_bytes = float(local_cells) * bytes_cell
-  achieved = alg_bytes / (kernel_ms * 1e-3) / 1e9
-  roofline = {
-      'bound': 'hbm', 'achieved': achieved, 'peak': HBM_PEAK_GBS,
-      'unit': 'GB/s', 'frac': achieved / HBM_PEAK_GBS, 'traffic': None,
-      'kernel': kname, 'kernel_ms': kernel_ms,
-      'algorithmic_bytes_per_launch': alg_bytes,
-      'iterations_per_launch': fuse,
-      'effective_GBs_at_8B_per_cell_iter': achieved * fuse,
-      'timing': 'hipEvent pair around %d back-to-back launches on the launch '
-                'stream right after the timed steps, arrays rotating as in a '
-                'step' % reps,
-  }
-  # measured streaming roofline on THIS GPU: float4 copy, buffers rotating as
-  # in an iterated run (the north star quotes its target against this)
-  try:
-    from soda_amd import streamcopy
-    n = local_cells - local_cells % 4
-    cp = streamcopy.StreamCopy(device=local_rank, unroll=1, nt_load=True)
-    ring = [a_bufs[0], b_bufs[0], torch.empty_like(a_bufs[0])]
-    state = {'i': 0}
 
-    def copy_once():
-      i = state['i']
-      cp.run(ring[(i + 1) % 3].data_ptr(), ring[i % 3].data_ptr(), n, stream)
-      state['i'] = i + 1
+  roofline = None
+  if args.full:
+    # ---- roofline of the dominant kernel, HIP events (--full) ---------------
+    # Measured BEFORE the timed region: it needs no result of it, and its ~60
+    # launches bring the GPU to its sustained clocks, so a short --steps run is
+    # not dominated by the first milliseconds after idle.
+    per_call = pure_calls(fuse)
+    if prog.schedule(local_extent, fuse * per_call) != {fuse: per_call}:
+      raise SystemExit('cannot time pass T=%d alone' % fuse)
 
-    copy_once()
-    copy_ms = time_events(copy_once, stream, 30)
-    copy_gbs = n * 8.0 / (copy_ms * 1e-3) / 1e9
-    roofline['measured_copy_GBs'] = copy_gbs
-    roofline['frac_of_measured_copy'] = achieved / copy_gbs
-    cp.close()
-    del ring
-  except Exception as e:  # a measurement aid must not take the bench down
-    roofline['measured_copy_GBs'] = None
-    roofline['measured_copy_error'] = str(e)[:200]
-  # PMC traffic is collected in separate rocprofv3 passes (tools/
-  # profile_round.sh) and kept in profiles/traffic.json under the key of the
-  # KERNEL it was measured on -- a hash of that kernel's machine code and
-  # descriptor (soda_amd/isa.py; until round 4 the key covered the whole module
-  # source, so an edit to a helper orphaned every number).  A number taken on
-  # other code under the same name is dropped, not reported.
-  from soda_amd import isa
-  kernel_key = runtime.source_key(prog.module.source)
-  roofline['kernel_key'] = kernel_key
-  roofline['isa_key'] = isa.isa_key(prog.code, kname)
-  roofline['compiler'] = runtime.compiler_version()
-  # vector-ALU wave-instructions per launch counted from the code object
-  # (straight-line prologue + loop body x trips, over the launch geometry):
-  # the second roof of a temporally blocked stencil, present with or without
-  # a PMC pass
-  static = {}
-  try:
-    static = isa.module_static(prog.module, prog.code,
-                               prog.geometry(local_extent)[0], local_extent)
-  except Exception as e:   # a measurement aid must not take the bench down
-    roofline['static_error'] = '%s: %s' % (type(e).__name__, str(e)[:160])
+    def dominant():
+      step_fn(b_bufs, a_bufs, local_extent, fuse * per_call)
 
-  def valu_roof(name, ms, pmc_insts=None):
-    st = static.get(name)
-    if not st:
-      return None
-    out = {
-        'wave_instructions_per_launch': st['valu_per_launch'],
-        'min_issue_ms': st['min_issue_ms'],
-        'frac_of_valu_issue_peak': st['min_issue_ms'] / ms if ms else None,
-        'per_row_step': {k: st['%s_per_row_step' % k]
-                         for k in ('valu', 'dpp', 'lds_crossbar', 'vmem_load',
-                                   'vmem_store', 'waitcnt')},
-        'source': 'static: llvm-objdump of the code object, loop body x trips '
-                  'over the launch geometry (soda_amd/isa.py); peak = 1024 '
-                  'SIMDs x 2.4 GHz / 2 cycles per wave64 instruction',
+    def time_pass(depth):
+      n = pure_calls(depth)
+      if prog.schedule(local_extent, depth * n) != {depth: n}:
+        return None
+
+      def go():
+        step_fn(b_bufs, a_bufs, local_extent, depth * n)
+      go()
+      return time_events(go, stream, max(1, 24 // n)) / n
+
+    dominant()
+    torch.cuda.synchronize()
+    calls = max(1, 48 // per_call)
+    reps = calls * per_call
+    kernel_ms = time_events(dominant, stream, calls) / per_call
+    achieved = alg_bytes / (kernel_ms * 1e-3) / 1e9
+    roofline = {
+        'bound': 'hbm', 'achieved': achieved, 'peak': HBM_PEAK_GBS,
+        'unit': 'GB/s', 'frac': achieved / HBM_PEAK_GBS, 'traffic': None,
+        'kernel': kname, 'kernel_ms': kernel_ms,
+        'algorithmic_bytes_per_launch': alg_bytes,
+        'iterations_per_launch': fuse,
+        'effective_GBs_at_8B_per_cell_iter': achieved * fuse,
+        'timing': 'hipEvent pair around %d back-to-back launches on the '
+                  'launch stream right after the timed steps, arrays rotating '
+                  'as in a step' % reps,
     }
-    if pmc_insts:
-      out['measured_wave_instructions_per_launch'] = pmc_insts
-      out['static_over_measured'] = st['valu_per_launch'] / pmc_insts
-    return out
-
-  def pmc_of(name, key):
-    """The counter entry of profiles/traffic.json for `name`, if it was taken
-    on this very machine code (else None and why)."""
-    entry = traffic_table.get(name)
-    if not entry:
-      return None, None
-    if entry.get('isa_key'):
-      if entry['isa_key'] == key:
-        return entry, None
-      return None, ('profiles/traffic.json holds %s for machine code %s; this '
-                    'run built %s' % (name, entry['isa_key'], key))
-    if entry.get('kernel_key') == kernel_key:     # (files of rounds 1-4)
-      return entry, None
-    return None, ('profiles/traffic.json holds %s for module key %s; this run '
-                  'built %s' % (name, entry.get('kernel_key'), kernel_key))
-
-  traffic_file = os.path.join(ROOT, 'profiles', 'traffic.json')
-  traffic_table = {}
-  if os.path.exists(traffic_file):
+    # measured streaming roofline on THIS GPU: float4 copy, buffers rotating
+    # as in an iterated run (the north star quotes its target against this)
     try:
-      with open(traffic_file) as f:
-        traffic_table = json.load(f)
-    except (OSError, ValueError):
-      traffic_table = {}
-  pmc, why = pmc_of(kname, roofline['isa_key'])
-  if why:
-    roofline['traffic_dropped'] = why
-  if pmc and pmc.get('hbm_bytes_per_launch'):
-    roofline['traffic'] = pmc['hbm_bytes_per_launch']
-    roofline['traffic_source'] = pmc.get('source')
-  v = valu_roof(kname, kernel_ms,
-                (pmc or {}).get('valu_wave_instructions_per_launch'))
-  if v:
-    roofline['valu'] = v
+      from soda_amd import streamcopy
+      n = local_cells - local_cells % 4
+      cp = streamcopy.StreamCopy(device=local_rank, unroll=1, nt_load=True)
+      ring = [a_bufs[0], b_bufs[0], torch.empty_like(a_bufs[0])]
+      state = {'i': 0}
+
+      def copy_once():
+        i = state['i']
+        cp.run(ring[(i + 1) % 3].data_ptr(), ring[i % 3].data_ptr(), n, stream)
+        state['i'] = i + 1
+
+      copy_once()
+      copy_ms = time_events(copy_once, stream, 30)
+      copy_gbs = n * 8.0 / (copy_ms * 1e-3) / 1e9
+      roofline['measured_copy_GBs'] = copy_gbs
+      roofline['frac_of_measured_copy'] = achieved / copy_gbs
+      cp.close()
+      del ring
+    except Exception as e:  # a measurement aid must not take the bench down
+      roofline['measured_copy_GBs'] = None
+      roofline['measured_copy_error'] = str(e)[:200]
+    # PMC traffic is collected in separate rocprofv3 passes (tools/
+    # profile_round.sh) and kept in profiles/traffic.json under the key of the
+    # KERNEL it was measured on -- a hash of that kernel's machine code and
+    # descriptor (soda_amd/isa.py; until round 4 the key covered the whole
+    # module source, so an edit to a helper orphaned every number).  A number
+    # taken on other code under the same name is dropped, not reported.
+    from soda_amd import isa
+    kernel_key = runtime.source_key(prog.module.source)
+    roofline['kernel_key'] = kernel_key
+    roofline['isa_key'] = isa.isa_key(prog.code, kname)
+    roofline['compiler'] = runtime.compiler_version()
+    # vector-ALU wave-instructions per launch counted from the code object
+    # (straight-line prologue + loop body x trips, over the launch geometry):
+    # the second roof of a temporally blocked stencil, present with or without
+    # a PMC pass
+    static = {}
+    try:
+      static = isa.module_static(prog.module, prog.code,
+                                 prog.geometry(local_extent)[0], local_extent)
+    except Exception as e:   # a measurement aid must not take the bench down
+      roofline['static_error'] = '%s: %s' % (type(e).__name__, str(e)[:160])
+
+    def valu_roof(name, ms, pmc_insts=None):
+      st = static.get(name)
+      if not st:
+        return None
+      out = {
+          'wave_instructions_per_launch': st['valu_per_launch'],
+          'min_issue_ms': st['min_issue_ms'],
+          'frac_of_valu_issue_peak': st['min_issue_ms'] / ms if ms else None,
+          'per_row_step': {k: st['%s_per_row_step' % k]
+                           for k in ('valu', 'dpp', 'lds_crossbar',
+                                     'vmem_load', 'vmem_store', 'waitcnt')},
+          'source': 'static: llvm-objdump of the code object, loop body x '
+                    'trips over the launch geometry (soda_amd/isa.py); peak = '
+                    '1024 SIMDs x 2.4 GHz / 2 cycles per wave64 instruction',
+      }
+      if pmc_insts:
+        out['measured_wave_instructions_per_launch'] = pmc_insts
+        out['static_over_measured'] = st['valu_per_launch'] / pmc_insts
+      return out
+
+    def pmc_of(name, key):
+      """The counter entry of profiles/traffic.json for `name`, if it was
+      taken on this very machine code (else None and why)."""
+      entry = traffic_table.get(name)
+      if not entry:
+        return None, None
+      if entry.get('isa_key'):
+        if entry['isa_key'] == key:
+          return entry, None
+        return None, ('profiles/traffic.json holds %s for machine code %s; '
+                      'this run built %s' % (name, entry['isa_key'], key))
+      if entry.get('kernel_key') == kernel_key:     # (files of rounds 1-4)
+        return entry, None
+      return None, ('profiles/traffic.json holds %s for module key %s; this '
+                    'run built %s' % (name, entry.get('kernel_key'),
+                                      kernel_key))
+
+    traffic_file = os.path.join(ROOT, 'profiles', 'traffic.json')
+    traffic_table = {}
+    if os.path.exists(traffic_file):
+      try:
+        with open(traffic_file) as f:
+          traffic_table = json.load(f)
+      except (OSError, ValueError):
+        traffic_table = {}
+    pmc, why = pmc_of(kname, roofline['isa_key'])
+    if why:
+      roofline['traffic_dropped'] = why
+    if pmc and pmc.get('hbm_bytes_per_launch'):
+      roofline['traffic'] = pmc['hbm_bytes_per_launch']
+      roofline['traffic_source'] = pmc.get('source')
+    v = valu_roof(kname, kernel_ms,
+                  (pmc or {}).get('valu_wave_instructions_per_launch'))
+    if v:
+      roofline['valu'] = v
 
   launches_per_step = 0
   overlap_trial = None
@@ -897,21 +962,6 @@ def main():
                      if trial[True] != float('inf') else None,
                      'serial_ms_per_step': trial[False],
                      **({'overlapped_failed': failed} if failed else {})}
-  for _ in range(args.warmup):
-    one_step()
-  torch.cuda.synchronize()
-  # launches of one step: count them once, outside the timed region
-  _orig_step = step_fn
-
-  def counting_step(dst, src, lext, iters, **kw):
-    nonlocal launches_per_step
-    _orig_step(dst, src, lext, iters, **kw)
-    launches_per_step += prog.last_launches()[0]
-
-  step_fn_real, step_fn = step_fn, counting_step
-  one_step()
-  step_fn = step_fn_real
-  torch.cuda.synchronize()
   # Bring the GPU to the clocks it sustains, OUTSIDE the timed region: a step
   # is ~1.2 ms, and 20 steps right after idle read 5-7 % slower than 200
   # (round 3: driver 5.55e12 with --steps 20 --warmup 5, own 200-step runs
@@ -946,11 +996,49 @@ def main():
     if (stable >= 3 and clock_warm_steps >= 100) or \
         pair[1] >= args.clock_warm_seconds:
       break
+
+  def restart():
+    """Every array of the rotation back to the seeded input (each rank's
+    slab of it): a step writes only the valid box of its output, and the next
+    step reads the rest of that array too."""
+    for i, full in enumerate(seeded_fields()):
+      a_bufs[i].copy_(full[slab.begin:slab.end])
+      del full
+    for bufs in pool[1:]:
+      for t, a in zip(bufs, a_bufs):
+        t.copy_(a)
+    chain['cur'], chain['first'] = a_bufs, True
+    if hider is not None:
+      hider.invalidate()
+
+  # Then back to the seeded input, and the warm-up steps from there: how many
+  # steps the spin above ran depends on the clocks, and what the last timed
+  # step computes (the arrays --dump-outputs writes) must depend on the
+  # arguments alone.  The speed of a step depends on the field it runs on:
+  # timed steps 1 / 6 / 51 steps after the restart ran 3 / 1.5 / 0.9 % slower
+  # than after the few hundred steps that used to precede them, hence the
+  # settling steps.  The one step after them, untimed, counts the launches of
+  # a step and makes the first timed step open with a halo exchange, as every
+  # later one does.
+  restart()
+  settle_steps = -(-SETTLE_ITERATIONS // max(1, args.iterate))
+  for _ in range(args.warmup + settle_steps):
+    one_step()
+  _orig_step = step_fn
+
+  def counting_step(dst, src, lext, iters, **kw):
+    nonlocal launches_per_step
+    _orig_step(dst, src, lext, iters, **kw)
+    launches_per_step += prog.last_launches()[0]
+
+  step_fn_real, step_fn = step_fn, counting_step
+  one_step()
+  step_fn = step_fn_real
   barrier()
   torch.cuda.synchronize()
   t0 = time.perf_counter()
   for _ in range(args.steps):
-    one_step()
+    last = one_step()
   torch.cuda.synchronize()
   barrier()
   torch.cuda.synchronize()
@@ -962,58 +1050,89 @@ def main():
   transport = ('RCCL send/recv' if backend == 'nccl' else backend +
                ' (REHEARSAL on one GPU, not a measurement)')
 
-  # the dominant kernel again, now at the clocks the timed steps ran at (the
-  # pre-measurement above starts ~1 ms after idle and reads up to 20 % slow on
-  # the VALU-bound fused kernel); this is the number the roofline reports
-  kernel_ms_cold = kernel_ms
-  kernel_ms = time_events(dominant, stream, calls) / per_call
-  torch.cuda.synchronize()
-  achieved = alg_bytes / (kernel_ms * 1e-3) / 1e9
-  roofline.update({
-      'achieved': achieved, 'frac': achieved / HBM_PEAK_GBS,
-      'kernel_ms': kernel_ms, 'kernel_ms_before_timed_region': kernel_ms_cold,
-      'effective_GBs_at_8B_per_cell_iter': achieved * fuse,
-  })
-  if roofline.get('measured_copy_GBs'):
-    roofline['frac_of_measured_copy'] = achieved / roofline['measured_copy_GBs']
-  # every pass of the step's schedule, timed the same way (the dominant one is
-  # the object above)
-  scheduled = []
-  for depth, count in sorted(sched.items(), reverse=True):
-    ms = kernel_ms if depth == fuse else time_pass(depth)
-    ps = [p for p in prog.module.sorted_passes() if p.fused_iters == depth]
-    name = prog.module.kernels[ps[0].kernels[0]].name if ps else '?'
-    key = isa.isa_key(prog.code, name)
-    pmc_k, _ = pmc_of(name, key)
-    vk = valu_roof(name, ms, (pmc_k or {}).get(
-        'valu_wave_instructions_per_launch'))
-    scheduled.append({
-        'kernel': name, 'isa_key': key,
-        'traffic': (pmc_k or {}).get('hbm_bytes_per_launch'),
-        'iterations_per_launch': depth,
-        'launches_per_exchange_interval': count,
-        'kernel_ms': ms,
-        'frac': alg_bytes / (ms * 1e-3) / 1e9 / HBM_PEAK_GBS if ms else None,
-        **({'valu_frac': vk['frac_of_valu_issue_peak'],
-            'valu_wave_instructions_per_launch':
-                vk['wave_instructions_per_launch']} if vk else {}),
+  def whole_grid(res):
+    """The output arrays of a step as the caller of the whole grid receives
+    them: every rank's own rows, gathered on rank 0 (a collective: every rank
+    calls it)."""
+    own = [r[slab.ghost_lo:slab.ghost_lo + slab.own_rows] for r in res]
+    if world > 1:
+      most = -(-extent[-1] // world)
+      gathered = []
+      for t in own:
+        pad = torch.zeros((most,) + tuple(t.shape[1:]), dtype=t.dtype,
+                          device=dev if backend == 'nccl' else 'cpu')
+        pad[:t.shape[0]].copy_(t)
+        parts = [torch.empty_like(pad) for _ in range(world)]
+        tdist.all_gather(parts, pad)
+        rows_of = [extent[-1] // world + (1 if r < extent[-1] % world else 0)
+                   for r in range(world)]
+        gathered.append(torch.cat([p[:n] for p, n in zip(parts, rows_of)]))
+      own = gathered
+    return own
+
+  if args.dump_outputs:
+    # (before anything else runs on the arrays of the rotation)
+    grid = whole_grid(last)
+    if rank == 0:
+      dump_outputs(args.dump_outputs, stencil, extent, args.iterate, grid)
+    del grid
+
+  if args.full:
+    # the dominant kernel again, now at the clocks the timed steps ran at (the
+    # pre-measurement above starts ~1 ms after idle and reads up to 20 % slow
+    # on the VALU-bound fused kernel); this is the number the roofline reports
+    kernel_ms_cold = kernel_ms
+    kernel_ms = time_events(dominant, stream, calls) / per_call
+    torch.cuda.synchronize()
+    achieved = alg_bytes / (kernel_ms * 1e-3) / 1e9
+    roofline.update({
+        'achieved': achieved, 'frac': achieved / HBM_PEAK_GBS,
+        'kernel_ms': kernel_ms,
+        'kernel_ms_before_timed_region': kernel_ms_cold,
+        'effective_GBs_at_8B_per_cell_iter': achieved * fuse,
     })
-  torch.cuda.synchronize()
-  roofline['scheduled_kernels'] = scheduled
-  if 'valu' in roofline:
-    roofline['valu']['frac_of_valu_issue_peak'] = (
-        roofline['valu']['min_issue_ms'] / kernel_ms)
-    # which roof the launch is nearer to.  `achieved` / `peak` / `frac` stay
-    # the HBM figures of the contract (algorithmic bytes / duration); a fused
-    # kernel that sits nearer its VALU-issue roof says so here
-    if roofline['valu']['frac_of_valu_issue_peak'] > roofline['frac']:
-      roofline['bound'] = 'valu'
-      roofline['bound_frac'] = roofline['valu']['frac_of_valu_issue_peak']
-      roofline['bound_note'] = (
-          'VALU issue: %.3g wave-instructions per launch need %.1f us at peak '
-          'issue; `frac` is the HBM fraction of the same launch' %
-          (roofline['valu']['wave_instructions_per_launch'],
-           roofline['valu']['min_issue_ms'] * 1e3))
+    if roofline.get('measured_copy_GBs'):
+      roofline['frac_of_measured_copy'] = (achieved /
+                                           roofline['measured_copy_GBs'])
+    # every pass of the step's schedule, timed the same way (the dominant one
+    # is the object above)
+    scheduled = []
+    for depth, count in sorted(sched.items(), reverse=True):
+      ms = kernel_ms if depth == fuse else time_pass(depth)
+      ps = [p for p in prog.module.sorted_passes() if p.fused_iters == depth]
+      name = prog.module.kernels[ps[0].kernels[0]].name if ps else '?'
+      key = isa.isa_key(prog.code, name)
+      pmc_k, _ = pmc_of(name, key)
+      vk = valu_roof(name, ms, (pmc_k or {}).get(
+          'valu_wave_instructions_per_launch'))
+      scheduled.append({
+          'kernel': name, 'isa_key': key,
+          'traffic': (pmc_k or {}).get('hbm_bytes_per_launch'),
+          'iterations_per_launch': depth,
+          'launches_per_exchange_interval': count,
+          'kernel_ms': ms,
+          'frac': (alg_bytes / (ms * 1e-3) / 1e9 / HBM_PEAK_GBS
+                   if ms else None),
+          **({'valu_frac': vk['frac_of_valu_issue_peak'],
+              'valu_wave_instructions_per_launch':
+                  vk['wave_instructions_per_launch']} if vk else {}),
+      })
+    torch.cuda.synchronize()
+    roofline['scheduled_kernels'] = scheduled
+    if 'valu' in roofline:
+      roofline['valu']['frac_of_valu_issue_peak'] = (
+          roofline['valu']['min_issue_ms'] / kernel_ms)
+      # which roof the launch is nearer to.  `achieved` / `peak` / `frac`
+      # stay the HBM figures of the contract (algorithmic bytes / duration); a
+      # fused kernel that sits nearer its VALU-issue roof says so here
+      if roofline['valu']['frac_of_valu_issue_peak'] > roofline['frac']:
+        roofline['bound'] = 'valu'
+        roofline['bound_frac'] = roofline['valu']['frac_of_valu_issue_peak']
+        roofline['bound_note'] = (
+            'VALU issue: %.3g wave-instructions per launch need %.1f us at '
+            'peak issue; `frac` is the HBM fraction of the same launch' %
+            (roofline['valu']['wave_instructions_per_launch'],
+             roofline['valu']['min_issue_ms'] * 1e3))
 
   cells = 1
   for e in extent:
@@ -1027,7 +1146,7 @@ def main():
       'rccl_world': rccl_world,
       **({'emulated_n_gpus': emulate} if emulate > 1 else {}),
       'steps': args.steps, 'warmup': args.warmup,
-      'clock_warm_steps': clock_warm_steps,
+      'clock_warm_steps': clock_warm_steps, 'settle_steps': settle_steps,
       'ms_per_step': elapsed / args.steps * 1e3, 'higher_is_better': True,
       'scaling': args.scaling, 'vs_baseline': None, 'dtype': 'f32',
       'data': 'synthetic',
@@ -1062,17 +1181,17 @@ def main():
           'pass_us_measured': {str(t): round(v, 1) for t, v in
                                prog.pass_times(local_extent)[0].items()},
       },
-      'roofline': roofline,
+      **({'roofline': roofline} if roofline else {}),
   }
 
-  # ---- result check (outside the timed region) -------------------------------
+  # ---- result check (outside the timed region; --full) -----------------------
   # The reference's generated host checks every run it times, in the same
   # process (frt/host.py:545-553 run, :625-657 compare).  Here: ONE more step
   # -- the same programs, schedule, exchange mode and code path as the timed
   # ones -- from the seeded input, the ranks' own rows gathered on rank 0 and
   # compared with the CPU oracle (test infrastructure, used as the checker
   # only) on the valid box, bit for bit.
-  if not args.no_parity and emulate <= 1:
+  if args.full and not args.no_parity and emulate <= 1:
     host_in = {}
     for i, (name, full) in enumerate(zip(stencil.input_names,
                                          seeded_fields())):
@@ -1091,20 +1210,7 @@ def main():
     for _ in range(checked_steps):
       res = one_step()
     torch.cuda.synchronize()
-    own = [r[slab.ghost_lo:slab.ghost_lo + slab.own_rows] for r in res]
-    if world > 1:
-      most = -(-extent[-1] // world)
-      gathered = []
-      for t in own:
-        pad = torch.zeros((most,) + tuple(t.shape[1:]), dtype=t.dtype,
-                          device=dev if backend == 'nccl' else 'cpu')
-        pad[:t.shape[0]].copy_(t)
-        parts = [torch.empty_like(pad) for _ in range(world)]
-        tdist.all_gather(parts, pad)
-        rows_of = [extent[-1] // world + (1 if r < extent[-1] % world else 0)
-                   for r in range(world)]
-        gathered.append(torch.cat([p[:n] for p, n in zip(parts, rows_of)]))
-      own = gathered
+    own = whole_grid(res)
     if rank == 0:
       import numpy as np
       from oracle import c_oracle
@@ -1133,7 +1239,7 @@ def main():
       }
       del want, host_in
 
-  if world == 1 and rank == 0:
+  if args.full and world == 1 and rank == 0:
     if not args.no_single_iter and fuse > 1:
       prog1 = runtime.Program(stencil, options([1]), device=local_rank,
                               extent=local_extent)

@@ -445,7 +445,8 @@ def test_bench_two_ranks_rehearsed_on_one_gpu(overlap):
          '--master-port', str(_free_port()), os.path.join(ROOT, 'bench.py'),
          '--gpus', '2', '--steps', '3', '--warmup', '1', '--extent', '2048',
          '2048', '--iterate', '48', '--fuse', '12', '4', '--exchange-every',
-         '24', '--overlap', overlap, '--no-cpu-baseline', '--no-single-iter']
+         '24', '--overlap', overlap, '--full', '--no-cpu-baseline',
+         '--no-single-iter']
   run = subprocess.run(cmd, capture_output=True, text=True, env=env,
                        timeout=600)
   assert run.returncode == 0, run.stderr[-3000:]
@@ -489,8 +490,8 @@ def test_bench_overlap_trial_survives_a_failing_overlapped_way():
          '--master-port', str(_free_port()), os.path.join(ROOT, 'bench.py'),
          '--gpus', '2', '--steps', '2', '--warmup', '1', '--extent', '2048',
          '2048', '--iterate', '48', '--fuse', '12', '4', '--exchange-every',
-         '24', '--overlap', 'auto', '--no-cpu-baseline', '--no-single-iter',
-         '--clock-warm-seconds', '0.05']
+         '24', '--overlap', 'auto', '--full', '--no-cpu-baseline',
+         '--no-single-iter', '--clock-warm-seconds', '0.05']
   run = subprocess.run(cmd, capture_output=True, text=True, env=env,
                        timeout=600)
   assert run.returncode == 0, run.stderr[-3000:]
@@ -511,8 +512,9 @@ def test_bench_line_carries_a_result_check():
   up; a wrong result would also have made it exit non-zero."""
   import json
   run = _run_bench('--steps', '3', '--warmup', '1', '--extent', '2048', '1536',
-                   '--iterate', '38', '--no-cpu-baseline', '--no-single-iter',
-                   '--no-rehearsal', '--clock-warm-seconds', '0.05')
+                   '--iterate', '38', '--full', '--no-cpu-baseline',
+                   '--no-single-iter', '--no-rehearsal',
+                   '--clock-warm-seconds', '0.05')
   assert run.returncode == 0, run.stderr[-3000:]
   out = json.loads([l for l in run.stdout.splitlines()
                     if l.startswith('{')][-1])
@@ -520,6 +522,46 @@ def test_bench_line_carries_a_result_check():
   assert out['parity']['cells'] == (2048 - 76) * (1536 - 76)
   assert out['clock_warm_steps'] >= 10 and out['value'] > 0
   assert out['roofline']['kernel'].startswith('jacobi2d_march2d_T')
+
+
+@pytest.mark.gpu
+def test_bench_dumps_what_its_last_timed_step_computed(tmp_path):
+  """`--dump-outputs DIR`: DIR/t0.npy is the valid box of what the last timed
+  step computed, float32 -- the same bits in a plain run and in a --full run
+  of the same arguments (whatever their clock spins ran; --full's result
+  check finds no mismatch), other bits after one more timed step.  A plain
+  line holds the headline fields and none of --full's legs; `steps` is
+  --steps."""
+  import json
+  from soda_amd import core
+  extent, iterate = (2048, 1536), 38
+  flags = ('--warmup', '2', '--extent', *map(str, extent), '--iterate',
+           str(iterate))
+  got, lines = {}, {}
+  for tag, steps, more in (
+      ('a', 3, ()), ('c', 4, ()),
+      ('b', 3, ('--full', '--no-cpu-baseline', '--no-single-iter',
+                '--no-rehearsal', '--no-other-configs'))):
+    run = _run_bench('--steps', str(steps), *flags, *more, '--dump-outputs',
+                     str(tmp_path / tag))
+    assert run.returncode == 0, run.stderr[-3000:]
+    out = json.loads([l for l in run.stdout.splitlines()
+                      if l.startswith('{')][-1])
+    assert out['steps'] == steps and out['ms_per_step'] > 0
+    assert out['higher_is_better'] is True and out['dtype'] == 'f32'
+    assert out['value'] > 0 and out['unit'] == 'cells*iters/s'
+    got[tag], lines[tag] = np.load(str(tmp_path / tag / 't0.npy')), out
+  full_only = {'roofline', 'parity', 'single_iter', 'other_configs',
+               'rehearsed_scaling', 'cpu_baseline'}
+  assert not full_only & set(lines['a']) and not full_only & set(lines['c'])
+  assert lines['b']['parity']['mismatches'] == 0 and 'roofline' in lines['b']
+  st = core.from_file(soda_path('jacobi2d.soda'), iterate=iterate)
+  lo, hi = st.valid_box(extent, 't0', iterate)
+  assert got['a'].dtype == np.float32
+  assert got['a'].shape == (hi[1] - lo[1], hi[0] - lo[0])
+  assert np.isfinite(got['a']).all()
+  assert got['a'].tobytes() == got['b'].tobytes()
+  assert got['a'].tobytes() != got['c'].tobytes()
 
 
 @pytest.mark.gpu
@@ -540,7 +582,7 @@ def test_bench_one_rank_over_rccl():
   run = subprocess.run(
       [sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '3',
        '--warmup', '1', '--extent', '2048', '1024', '--iterate', '26',
-       '--no-cpu-baseline', '--no-single-iter', '--no-rehearsal',
+       '--full', '--no-cpu-baseline', '--no-single-iter', '--no-rehearsal',
        '--clock-warm-seconds', '0.05'],
       capture_output=True, text=True, env=env, timeout=600)
   assert run.returncode == 0, run.stderr[-3000:]

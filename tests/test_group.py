@@ -539,7 +539,7 @@ def test_bench_group_mode_checks_its_result(built):
       [sys.executable, os.path.join(ROOT, 'bench.py'), '--group', '--virtual',
        '--gpus', '4', '--steps', '3', '--warmup', '1', '--extent', '2048',
        '1600', '--iterate', '24', '--fuse', '12', '4', '--exchange-every',
-       '12'], capture_output=True, text=True, timeout=600)
+       '12', '--full'], capture_output=True, text=True, timeout=600)
   assert run.returncode == 0, run.stderr[-3000:]
   out = json.loads([l for l in run.stdout.splitlines()
                     if l.startswith('{')][-1])

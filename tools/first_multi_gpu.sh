@@ -88,7 +88,7 @@ bench() {   # N, bench.py arguments...: one rank per GPU under torchrun
   fi
 }
 
-quick="--steps 20 --warmup 5 --no-cpu-baseline --no-rehearsal --no-single-iter --no-other-configs"
+quick="--steps 20 --warmup 5 --full --no-cpu-baseline --no-rehearsal --no-single-iter --no-other-configs"
 # 0. the single-GPU line on this node, for the ratio
 step n1 python bench.py $quick || exit 1
 # 1. two ranks over RCCL, exchange NOT hidden: ncclSend/ncclRecv + the nccl
@@ -112,7 +112,7 @@ n=$max
 #    jacobi2d x 1000 (several exchanges per step)
 step c4_n${n} bench $n --soda tests/golden/soda/heat3d.soda \
     --extent 512 512 512 --iterate 50 --fuse 2 $quick || exit 1
-step c5_n${n} bench $n --iterate 1000 --steps 5 --warmup 2 \
+step c5_n${n} bench $n --iterate 1000 --steps 5 --warmup 2 --full \
     --no-cpu-baseline --no-rehearsal --no-single-iter --no-other-configs || exit 1
 # 7. weak scaling: every rank keeps the single-GPU grid
 step weak_n${n} bench $n --scaling weak $quick || exit 1

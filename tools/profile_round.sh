@@ -9,9 +9,9 @@ set -o pipefail
 tag=${1:-r01}
 out=gpurun_out
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
-quick="--no-cpu-baseline --no-rehearsal --no-other-configs --no-parity --steps 1 --warmup 1"
+quick="--full --no-cpu-baseline --no-rehearsal --no-other-configs --no-parity --steps 1 --warmup 1"
 # 1. per-kernel time: rocprofv3 --kernel-trace --stats of the bench command
-rocprofv3 --kernel-trace --stats --output-format csv -d $out/${tag}_trace -- python3 bench.py --no-cpu-baseline --no-rehearsal > $out/${tag}_trace.log 2>&1 || exit 1
+rocprofv3 --kernel-trace --stats --output-format csv -d $out/${tag}_trace -- python3 bench.py --full --no-cpu-baseline --no-rehearsal > $out/${tag}_trace.log 2>&1 || exit 1
 # 2. counters, one pass per set (never together with --stats)
 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $out/${tag}_fetch -- python3 bench.py $quick > $out/${tag}_fetch.log 2>&1 || exit 1
 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $out/${tag}_write -- python3 bench.py $quick > $out/${tag}_write.log 2>&1 || exit 1
@@ -22,7 +22,7 @@ python tools/pmc_summary.py $out/${tag}_trace $out/${tag}_fetch $out/${tag}_writ
 cp $(ls $out/${tag}_trace/*/*kernel_stats.csv | head -1) $out/${tag}_kernel_stats.csv
 cp $out/${tag}_traffic.json profiles/traffic.json
 # 4. the bench line itself, LAST: it must find its counters in the table
-python bench.py > $out/${tag}_bench.json 2> $out/${tag}_bench.err || exit 1
+python bench.py --full > $out/${tag}_bench.json 2> $out/${tag}_bench.err || exit 1
 python bench.py --steps 20 --warmup 5 > $out/${tag}_bench_driver_like.json 2>> $out/${tag}_bench.err || exit 1
 python tools/hostpath.py > $out/${tag}_hostpath.jsonl 2> $out/${tag}_hostpath.err
 python - <<PY
