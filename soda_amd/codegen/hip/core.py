@@ -40,9 +40,10 @@ def add_arguments(parser) -> None:
   parser.add_argument('--hip-backend', action='store_true', dest='hip_backend',
                       help='JIT-build the HIP kernels and run them on the GPU')
   parser.add_argument('--hip-strategy', type=str, dest='hip_strategy',
-                      choices=('auto', 'direct', 'march', 'lds', 'ldswin'), default='auto',
+                      choices=lower.STRATEGIES, default='auto',
                       help='kernel family: register-marching wavefront strips '
-                      '(2-D / 3-D programs) or the direct kernels')
+                      '(2-D / 3-D programs), the LDS window ring (2-D) or the '
+                      'direct kernels')
   parser.add_argument('--hip-fuse', type=int, nargs='*', dest='hip_fuse',
                       metavar='T', default=list(lower.DEFAULT_FUSE),
                       help='temporal blocking: the numbers of iterations a '

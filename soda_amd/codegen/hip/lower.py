@@ -3,7 +3,7 @@
 What the reference's HLS emitter does for an FPGA (reference
 src/soda/codegen/xilinx/hls_kernel.py:338-410 `print_code`, :665-886
 `print_module_definition`; src/soda/dataflow.py:336-625) is done here for a
-GPU.  Two families of kernels are generated:
+GPU.  Three families of kernels are generated:
 
 `direct`   one kernel per stage, 16 bytes' worth of cells per thread, parents
            read straight from global memory into per-thread row buffers
@@ -15,7 +15,8 @@ GPU.  Two families of kernels are generated:
            marches along dimension 1 (the dimension SODA streams).  Every
            tensor of the -- possibly T-times unrolled -- stage chain keeps a
            sliding window of rows in REGISTERS; neighbours along dimension 0
-           come from adjacent lanes by DPP wave shifts; inputs arrive by one
+           come from adjacent lanes by lane shifts (DPP, or DPP down and
+           ds_swizzle up: default_lane_shift); inputs arrive by one
            coalesced 16-byte load per lane per row, PF rows ahead of use;
            only the last iteration's outputs are stored.  That is SODA's own
            micro-architecture (line buffers chained through all iterations so
@@ -23,32 +24,38 @@ GPU.  Two families of kernels are generated:
            mapped onto a wavefront: the FIFOs become registers, the `unroll
            factor` PEs become 64*V lanes, and `iterate` stages fused in one
            pipeline become T fused iterations per launch (temporal blocking).
-           Waves never talk to each other (no LDS, no barrier): the halo a
-           strip needs is recomputed by overlapping strips/chunks.
+           Unless a block shares x-halos (xshare) or fused iterations (pipe)
+           through LDS, waves never talk to each other: the halo a strip
+           needs is recomputed by overlapping strips/chunks.
+           (`march3d` does the same for 3-D programs with a tile of rows
+           per wave.)
+
+`ldswin`   one-stage 2-D programs with windows many cells wide (contrast):
+           the window rows live in an LDS ring that a block's waves fill
+           together, every lane computes 8 cells, no lane shifts.
 
 Floating-point results are bit-identical to the CPU oracle because the kernels
 compile the same C expression text with -ffp-contract=off.
 
 Layout of the package: module.py (Module, descriptors, the device runtime
-text), march.py (`march2d` / `march3d`), direct.py, lds2d.py (the classic LDS
-halo tile, kept as the measured alternative); this file holds the options and
-`lower()`, which picks the shape.
+text), march.py (`march2d` / `march3d`), ldswin.py, direct.py; this file holds
+the options and `lower()`, which picks the family and the shape (DESIGN.md
+section 4.3).
 """
+import dataclasses
 import os
-from typing import Optional, Sequence
+from typing import Dict, Optional, Sequence, Union
 
 from soda_amd import core, util
 
 from soda_amd.codegen.hip.module import (KernelDesc, Module, PassDesc,  # noqa: F401
                                          _check_native, runtime_text)
 from soda_amd.codegen.hip.direct import DIRECT_BLOCK, add_direct_pass  # noqa: F401
-from soda_amd.codegen.hip.lds2d import (add_lds2d_pass,  # noqa: F401
-                                        lds2d_supported)
 from soda_amd.codegen.hip.ldswin import (add_ldswin_pass,  # noqa: F401
                                          ldswin_candidate, ldswin_pays,
                                          ldswin_supported)
-from soda_amd.codegen.hip.march import (MAX_FUSE_3D, MAX_FUSE_PRESERVE,  # noqa: F401
-                                        MAX_SHIFT_TEMPS,
+from soda_amd.codegen.hip.march import (LANE_SHIFTS, MAX_FUSE_3D,  # noqa: F401
+                                        MAX_FUSE_PRESERVE, MAX_SHIFT_TEMPS,
                                         MAX_UNROLL, REG_BUDGET, MarchConfig,
                                         add_march_pass, default_vec,
                                         march_supported)
@@ -68,6 +75,11 @@ DEFAULT_FUSE = (13, 12, 8, 4)
 SLIDING_SUMS = os.environ.get('SODA_HIP_SLIDE', '1') != '0'
 
 
+# kernel families lower() can be asked for (LowerOptions.strategy)
+STRATEGIES = ('auto', 'direct', 'march', 'ldswin')
+
+
+@dataclasses.dataclass(kw_only=True, eq=False)
 class LowerOptions:
   """Knobs of the HIP backend (command-line spelling: --hip-*).  `None` means
   "the measured default for this program's dimensionality" (profiles/
@@ -76,99 +88,76 @@ class LowerOptions:
   they use plain loads (the overlap then hits in L2), prefetch 1 plane and hold
   4 output rows per wave to stay under 128 VGPRs."""
 
-  def __init__(self, strategy: str = 'auto', fuse: Sequence[int] = (4,),
-               vec: Optional[int] = None, chunk_rows: Optional[int] = None,
-               prefetch: Optional[int] = None, waves_x: int = 1,
-               waves_y: int = 1, nt_store: Optional[bool] = None,
-               nt_load: Optional[bool] = None, xcd_swizzle: bool = True,
-               edge_loads: bool = True, tile_rows: Optional[int] = None,
-               warm_guards: bool = False, interleave: bool = False,
-               lane_shift: Optional[str] = None, min_waves: int = 0,
-               occupancy: int = 0, buffer_ops: bool = True,
-               pipe: Optional[int] = None, pipe_rows: int = 2,
-               reg_budget: Optional[int] = None,
-               stamps: bool = False,
-               peel=None, align_lanes: Optional[int] = None,
-               xshare: Optional[bool] = None,
-               row_cells: Optional[int] = None,
-               windows: Optional[bool] = None,
-               inline: Optional[bool] = None):
-    # locals read only at the cell being computed are folded into their
-    # consumers (optimization/pointwise.py): denoise3d is 4 tensors instead
-    # of 10.  SODA_HIP_INLINE=0/1 overrides for A/B runs
-    if inline is None:
-      inline = os.environ.get('SODA_HIP_INLINE', '1') != '0'
-    self.inline = inline
-    # long integer window reductions (erosion's 19-tap min, xcorr's 19-tap
-    # sums) as chains of power-of-two windows: 6 instead of 18 operations per
-    # cell, bit-exact (optimization/windows.py).  SODA_HIP_WINDOWS=0/1
-    # overrides for A/B runs
-    if windows is None:
-      windows = os.environ.get('SODA_HIP_WINDOWS', '1') != '0'
-    self.windows = windows
-    self.stamps = stamps
-    # fused 3-D kernels whose block covers the whole row, x-halos handed over
-    # through LDS (MarchConfig.xshare).  Needs the row length the program will
-    # run on (`row_cells` = extent[0]; runtime.Program fills it in from its
-    # extent): the kernels then REFUSE any other row length at launch.
-    # None: where it applies (3-D, fused, <= 4 waves per row); True also in
-    # 2-D; SODA_HIP_XSHARE=0/1 overrides for A/B runs
-    if xshare is None and os.environ.get('SODA_HIP_XSHARE'):
-      xshare = os.environ['SODA_HIP_XSHARE'] == '1'
-    self.xshare = xshare
-    self.row_cells = row_cells
-    # valid lanes of a strip as a multiple of this; None: as many as make a
-    # strip's output rows start on 64-byte boundaries where they are written
-    # with non-temporal stores, else 1
-    if align_lanes is None and os.environ.get('SODA_HIP_ALIGN_LANES'):
-      align_lanes = int(os.environ['SODA_HIP_ALIGN_LANES'])   # A/B runs
-    self.align_lanes = align_lanes
-    # trips of the unrolled loop whose warm-up is peeled into straight-line
-    # code without the stages that do not matter yet: an int for every fusion
-    # depth, a dict {depth: trips}, -1 = all of the warm-up, None = let
-    # runtime.select_peel choose per kernel from the compiled register counts
-    # (lower() itself treats None as -1)
-    self.peel = peel
-    # estimated VGPRs a marching shape may need before the ladder in lower()
-    # moves on to a leaner one (None: REG_BUDGET)
-    self.reg_budget = reg_budget
-    # waves of a block sharing the fused iterations of a 2-D kernel; None =
-    # default_pipe(fusion depth)
-    self.pipe = pipe
-    self.pipe_rows = pipe_rows
-    self.buffer_ops = buffer_ops
-    self.occupancy = occupancy
-    self.min_waves = min_waves
-    self.lane_shift = lane_shift
-    self.interleave = interleave
-    self.warm_guards = warm_guards
-    self.strategy = strategy      # auto | direct | march | lds
-    self.fuse = tuple(fuse)       # temporal-blocking depths to generate
-    self.vec = vec
-    self.chunk_rows = chunk_rows
-    self.prefetch = prefetch
-    self.waves_x = waves_x
-    self.waves_y = waves_y
-    # Cache hints, measured on MI355X with buffers ping-ponging as in a real
-    # iterated run (tools/sweep.py --launches N): inputs are read once per
-    # launch, so their loads are non-temporal; the outputs are the next
-    # launch's inputs, so their stores are plain.
-    self.nt_store = nt_store
-    self.nt_load = nt_load
-    self.xcd_swizzle = xcd_swizzle
-    self.edge_loads = edge_loads
-    self.tile_rows = tile_rows
+  strategy: str = 'auto'        # one of STRATEGIES
+  fuse: Sequence[int] = (4,)    # temporal-blocking depths to generate
+  vec: Optional[int] = None
+  chunk_rows: Optional[int] = None
+  prefetch: Optional[int] = None
+  waves_x: int = 1
+  waves_y: int = 1
+  # Cache hints, measured on MI355X with buffers ping-ponging as in a real
+  # iterated run (tools/sweep.py --launches N): inputs are read once per
+  # launch, so their loads are non-temporal; the outputs are the next
+  # launch's inputs, so their stores are plain.
+  nt_store: Optional[bool] = None
+  nt_load: Optional[bool] = None
+  xcd_swizzle: bool = True
+  edge_loads: bool = True
+  tile_rows: Optional[int] = None
+  # 'dpp' or 'mixh' (march.LANE_SHIFTS); None: default_lane_shift
+  lane_shift: Optional[str] = None
+  min_waves: int = 0
+  occupancy: int = 0
+  # waves of a block sharing the fused iterations of a 2-D kernel; None =
+  # default_pipe(fusion depth)
+  pipe: Optional[int] = None
+  pipe_rows: int = 2
+  # estimated VGPRs a marching shape may need before the ladder in lower()
+  # moves on to a leaner one (None: REG_BUDGET)
+  reg_budget: Optional[int] = None
+  stamps: bool = False
+  # trips of the unrolled loop whose warm-up is peeled into straight-line
+  # code without the stages that do not matter yet: an int for every fusion
+  # depth, a dict {depth: trips}, -1 = all of the warm-up, None = let
+  # runtime.select_peel choose per kernel from the compiled register counts
+  # (lower() itself treats None as -1)
+  peel: Union[None, int, Dict[int, int]] = None
+  # valid lanes of a strip as a multiple of this; None: as many as make a
+  # strip's output rows start on 64-byte boundaries where they are written
+  # with non-temporal stores, else 1.  SODA_HIP_ALIGN_LANES overrides None
+  # for A/B runs
+  align_lanes: Optional[int] = None
+  # fused 3-D kernels whose block covers the whole row, x-halos handed over
+  # through LDS (MarchConfig.xshare).  Needs the row length the program will
+  # run on (`row_cells` = extent[0]; runtime.Program fills it in from its
+  # extent): the kernels then REFUSE any other row length at launch.
+  # None: where it applies (3-D, fused, <= 4 waves per row); True also in
+  # 2-D; SODA_HIP_XSHARE=0/1 overrides for A/B runs
+  xshare: Optional[bool] = None
+  row_cells: Optional[int] = None
+  # long integer window reductions (erosion's 19-tap min, xcorr's 19-tap
+  # sums) as chains of power-of-two windows: 6 instead of 18 operations per
+  # cell, bit-exact (optimization/windows.py).  SODA_HIP_WINDOWS=0/1
+  # overrides for A/B runs
+  windows: Optional[bool] = None
+  # locals read only at the cell being computed are folded into their
+  # consumers (optimization/pointwise.py): denoise3d is 4 tensors instead
+  # of 10.  SODA_HIP_INLINE=0/1 overrides for A/B runs
+  inline: Optional[bool] = None
+
+  def __post_init__(self):
+    self.fuse = tuple(self.fuse)
+    if self.inline is None:
+      self.inline = os.environ.get('SODA_HIP_INLINE', '1') != '0'
+    if self.windows is None:
+      self.windows = os.environ.get('SODA_HIP_WINDOWS', '1') != '0'
+    if self.xshare is None and os.environ.get('SODA_HIP_XSHARE'):
+      self.xshare = os.environ['SODA_HIP_XSHARE'] == '1'
+    if self.align_lanes is None and os.environ.get('SODA_HIP_ALIGN_LANES'):
+      self.align_lanes = int(os.environ['SODA_HIP_ALIGN_LANES'])
 
   def resolved(self, dim: int, iterated: bool = True) -> 'LowerOptions':
-    out = LowerOptions(self.strategy, self.fuse, self.vec, self.chunk_rows,
-                       self.prefetch, self.waves_x, self.waves_y,
-                       self.nt_store, self.nt_load, self.xcd_swizzle,
-                       self.edge_loads, self.tile_rows, self.warm_guards,
-                       self.interleave, self.lane_shift, self.min_waves,
-                       self.occupancy, self.buffer_ops, self.pipe,
-                       self.pipe_rows, self.reg_budget,
-                       self.stamps, self.peel, self.align_lanes, self.xshare,
-                       self.row_cells, self.windows, self.inline)
+    out = dataclasses.replace(self)
     if out.prefetch is None and dim == 3:
       out.prefetch = 1
     # 2-D: resolved per fusion depth in lower() (default_prefetch)
@@ -185,13 +174,6 @@ class LowerOptions:
     if out.tile_rows is None:
       out.tile_rows = 4
     return out
-
-  def key(self) -> str:
-    return '%s_f%s_v%s_c%s_p%s_w%dx%d_%d%s%d%d_r%s' % (
-        self.strategy, '-'.join(map(str, self.fuse)), self.vec,
-        self.chunk_rows, self.prefetch, self.waves_x, self.waves_y,
-        self.nt_store, self.nt_load, self.xcd_swizzle, self.edge_loads,
-        self.tile_rows)
 
 
 # operations per cell (as written) between which a one-iteration 2-D program
@@ -262,7 +244,7 @@ def default_prefetch(fused_iters: int, lane_shift: str = 'dpp') -> int:
   153 at 4; with 'mixh' shifts, 11 registers leaner: 149.6 at 2, 136.2 at 4)."""
   if fused_iters <= 2:
     return 8
-  if fused_iters <= 8 or lane_shift in ('mixh', 'mix64', 'mix64d'):
+  if fused_iters <= 8 or lane_shift == 'mixh':
     return 4
   return 2
 
@@ -272,6 +254,12 @@ def lower(stencil: core.Stencil, opts: Optional[LowerOptions] = None) -> Module:
   1-iteration pass (always present: the scheduler needs it for remainders)."""
   opts = (opts or LowerOptions()).resolved(
       stencil.dim, iterated=stencil.iterate > 1)
+  if opts.strategy not in STRATEGIES:
+    raise util.SemanticError('strategy %r: one of %s' %
+                             (opts.strategy, ', '.join(STRATEGIES)))
+  if opts.lane_shift is not None and opts.lane_shift not in LANE_SHIFTS:
+    raise util.SemanticError('lane_shift %r: None or one of %s' %
+                             (opts.lane_shift, ', '.join(LANE_SHIFTS)))
   _check_native(stencil)
   stencil.check_preserve()
   # arithmetic per cell of one iteration AS WRITTEN (the rewrites below fold
@@ -325,12 +313,12 @@ def lower(stencil: core.Stencil, opts: Optional[LowerOptions] = None) -> Module:
   if opts.strategy == 'ldswin':
     raise util.SemanticError('ldswin: %s' % (
         ldswin_supported(stencil) or 'the program does not fold to one stage'))
-  if opts.inline and opts.strategy != 'lds':
+  if opts.inline:
     from soda_amd.optimization import pointwise
     folded = pointwise.inline_pointwise(stencil)
     if same_boxes(folded):
       stencil = folded
-  if opts.windows and opts.strategy != 'lds':
+  if opts.windows:
     from soda_amd.optimization import windows
     # (the marching kernels reduce dimension-0 windows themselves, all cells
     # of a lane jointly; `direct` kernels get chains in every dimension)
@@ -350,13 +338,6 @@ def lower(stencil: core.Stencil, opts: Optional[LowerOptions] = None) -> Module:
   from soda_amd.codegen.hip import exact
   stencil = exact.specialize(stencil)
   mod = Module(stencil)
-  if opts.strategy == 'lds':
-    if stencil.preserve_border:
-      raise util.SemanticError('lds2d: border: preserve is not supported')
-    if stencil.symbol_table[stencil.input_names[0]].size_in_bytes != 4:
-      raise util.SemanticError('lds2d: 4-byte cells only')
-    add_lds2d_pass(mod, nt_load=bool(opts.nt_load))
-    return mod
   use_march = opts.strategy in ('auto', 'march') and \
       march_supported(stencil) is None
   if opts.strategy == 'march' and not use_march:
@@ -392,7 +373,7 @@ def lower(stencil: core.Stencil, opts: Optional[LowerOptions] = None) -> Module:
 
     def pipe_for(t: int) -> int:
       want = default_pipe(t) if opts.pipe is None else opts.pipe
-      ok = (want > 1 and t > 1 and t % want == 0 and opts.buffer_ops and
+      ok = (want > 1 and t > 1 and t % want == 0 and
             opts.waves_x * opts.waves_y == 1)
       return want if ok else 1
 
@@ -401,8 +382,7 @@ def lower(stencil: core.Stencil, opts: Optional[LowerOptions] = None) -> Module:
     def shift_for(t: int, xshare: int = 0) -> str:
       if opts.lane_shift is not None:
         return opts.lane_shift
-      if xshare or pipe_for(t) > 1 or opts.waves_x * opts.waves_y != 1 or \
-          not opts.buffer_ops:
+      if xshare or pipe_for(t) > 1 or opts.waves_x * opts.waves_y != 1:
         return 'dpp'
       return default_lane_shift(t, stencil.dim)
 
@@ -411,19 +391,21 @@ def lower(stencil: core.Stencil, opts: Optional[LowerOptions] = None) -> Module:
       shift = shift_for(t, xshare)
       if pf is None:
         pf = default_prefetch(t, shift)
-      cfg = MarchConfig(t, vec, opts.chunk_rows or 64, pf,
-                        opts.waves_x, opts.waves_y, opts.nt_store,
-                        opts.nt_load, opts.xcd_swizzle, opts.edge_loads,
-                        rows or opts.tile_rows, opts.warm_guards,
-                        opts.interleave,
-                        shift, opts.min_waves, opts.occupancy,
-                        opts.buffer_ops,
-                        pipe_for(t), opts.pipe_rows,
-                        opts.stamps, peel_for(t),
-                        opts.align_lanes if opts.align_lanes is not None else
-                        (max(1, 64 // (vec * out_bytes)) if opts.nt_store
-                         else 1), xshare, bool(opts.windows),
-                        bool(opts.windows) and SLIDING_SUMS)
+      if opts.align_lanes is not None:
+        align = opts.align_lanes
+      else:
+        align = max(1, 64 // (vec * out_bytes)) if opts.nt_store else 1
+      cfg = MarchConfig(
+          fused_iters=t, vec=vec, chunk_rows=opts.chunk_rows or 64,
+          prefetch=pf, waves_x=opts.waves_x, waves_y=opts.waves_y,
+          nt_store=opts.nt_store, nt_load=opts.nt_load,
+          xcd_swizzle=opts.xcd_swizzle, edge_loads=opts.edge_loads,
+          tile_rows=rows or opts.tile_rows, lane_shift=shift,
+          min_waves=opts.min_waves, occupancy=opts.occupancy,
+          pipe=pipe_for(t), pipe_rows=opts.pipe_rows, stamps=opts.stamps,
+          peel=peel_for(t), align_lanes=align, xshare=xshare,
+          xwindow=bool(opts.windows),
+          slide=bool(opts.windows) and SLIDING_SUMS)
       cfg.chunk_fixed = opts.chunk_rows is not None
       return cfg
 

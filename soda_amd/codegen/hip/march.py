@@ -85,17 +85,20 @@ LDS_PER_CU = 160 * 1024     # MI355X_MICROARCH.md
 MIRROR_PREFETCH = 1         # ticks between a mirror's LDS read and its first use
 
 
+# how a row is shifted by one lane (MarchConfig.lane_shift) -> its tag in the
+# kernel name
+LANE_SHIFTS = {'dpp': '', 'mixh': '_mixh'}
+
+
 class MarchConfig:
 
-  def __init__(self, fused_iters: int = 1, vec: int = 4, chunk_rows: int = 64,
+  def __init__(self, *, fused_iters: int = 1, vec: int = 4, chunk_rows: int = 64,
                prefetch: int = 2, waves_x: int = 1, waves_y: int = 1,
                nt_store: bool = False, nt_load: bool = True,
                xcd_swizzle: bool = True, edge_loads: bool = True,
-               tile_rows: int = 6, warm_guards: bool = False,
-               interleave: bool = False, lane_shift: str = 'dpp',
+               tile_rows: int = 6, lane_shift: str = 'dpp',
                min_waves: int = 0, occupancy: int = 0,
-               buffer_ops: bool = True, pipe: int = 1, pipe_rows: int = 4,
-               stamps: bool = False,
+               pipe: int = 1, pipe_rows: int = 4, stamps: bool = False,
                peel: int = -1, align_lanes: int = 1, xshare: int = 0,
                xwindow: bool = True, slide: bool = True):
     # integer window reductions along dimension 0 evaluated for all cells of
@@ -143,10 +146,6 @@ class MarchConfig:
     # SIMD) and `pipe` times longer chunks for the same number of waves (the
     # 2T-row warm-up is paid per block, not per wave).
     self.pipe = pipe
-    # vector memory through buffer resources with out-of-range offsets instead
-    # of `if (row_ok)` branches (soda_rt.h): straight-line loop body, exact
-    # s_waitcnt counts
-    self.buffer_ops = buffer_ops
     # cap the waves resident per SIMD (0 = whatever the registers allow) by
     # giving every block an LDS allocation it never touches: 3 waves per SIMD
     # issue VALU work slower than 2 or 4 (tools/valubench.py)
@@ -155,22 +154,10 @@ class MarchConfig:
     # (amdgpu_waves_per_eu); 0 = let it use what it wants
     self.min_waves = min_waves
     # how a row is shifted by one lane: 'dpp' (wave_shr/shl fused into the
-    # consuming add), 'bperm' (ds_bpermute_b32, issued one stage early), 'swz'
-    # (ds_swizzle rotate + a readlane/writelane patch for the lane that crosses
-    # the 32-lane halves) or 'swzh' (ds_swizzle rotate alone: the wave holds
-    # two independent 32-lane half strips, each with its own halo lanes) or
-    # 'lds': every lane files the end cells of a row it has computed in a
-    # wave-private LDS line and takes its neighbours' from there one row step
-    # later (plain ds_write / ds_read, no barrier: one wave, in-order LDS), so
-    # the vector ALU sees no cross-lane operation for computed rows at all
+    # consuming add) or 'mixh' (down through DPP, up through a ds_swizzle
+    # rotate; the wave holds two independent 32-lane half strips, each with its
+    # own halo lanes)
     self.lane_shift = lane_shift
-    # emit a stage's cells operation-major (independent statements back to
-    # back).  Measured SLOWER on gfx950 (T=12: 186 vs 151 us): a wave64 VALU op
-    # runs as two 32-lane passes, so a dependent op already issues without a
-    # bubble, and the interleaved order only adds register-bank pressure.
-    self.interleave = interleave
-    self.warm_guards = warm_guards  # skip a stage while its rows cannot
-    #                                 reach any output row of this chunk yet
     self.fused_iters = fused_iters
     self.vec = vec
     self.chunk_rows = chunk_rows  # cells one wave marches over (last dim)
@@ -186,38 +173,23 @@ class MarchConfig:
     self.chunk_fixed = False      # True: the host must not re-size the chunk
 
   def key(self) -> str:
-    # chunk_rows is a launch-time value, not part of the code
-    return 'T%d_V%d_P%d_W%dx%d_R%d%s%s%s%s' % (
-        self.fused_iters, self.vec, self.prefetch,
-        self.waves_x, self.waves_y, self.tile_rows,
+    # chunk_rows is a launch-time value, not part of the code.  Every name
+    # carries `_buf` (buffer addressing, once optional): the names key
+    # profiles/traffic.json
+    return ''.join((
+        'T%d_V%d_P%d_W%dx%d_R%d' % (self.fused_iters, self.vec, self.prefetch,
+                                    self.waves_x, self.waves_y, self.tile_rows),
         '_nts' if self.nt_store else '', '_ntl' if self.nt_load else '',
-        '_xcd' if self.xcd_swizzle else '',
-        '_edge' if self.edge_loads else '') + (
-            '_wg' if self.warm_guards else '') + (
-                '_il' if self.interleave else '') + (
-                    '_bp' if self.lane_shift == 'bperm' else
-                    '_swz' if self.lane_shift == 'swz' else
-                    '_swzh' if self.lane_shift == 'swzh' else
-                    '_mixh' if self.lane_shift == 'mixh' else
-                    '_mix64' if self.lane_shift == 'mix64' else
-                    '_mix64d' if self.lane_shift == 'mix64d' else
-                    '_ldsx' if self.lane_shift == 'lds' else
-                    '_noshift' if self.lane_shift == 'none' else '') + (
-                        '_mw%d' % self.min_waves if self.min_waves else '') + (
-                            '_occ%d' % self.occupancy if self.occupancy else '') + (
-                                '_buf' if self.buffer_ops else '') + (
-                                    '_pipe%dx%d' % (self.pipe, self.pipe_rows)
-                                    if self.pipe > 1 else '') + (
-                                        '_st' if self.stamps else '') + (
-                                            '' if self.peel < 0 else
-                                            '_k%d' % self.peel) + (
-                                                '_al%d' % self.align_lanes
-                                                if self.align_lanes > 1 else '') + (
-                                                    '_xs%d' % self.xshare
-                                                    if self.xshare else '')
-
-
-March2DConfig = MarchConfig   # older name
+        '_xcd' if self.xcd_swizzle else '', '_edge' if self.edge_loads else '',
+        LANE_SHIFTS[self.lane_shift],
+        '_mw%d' % self.min_waves if self.min_waves else '',
+        '_occ%d' % self.occupancy if self.occupancy else '',
+        '_buf',
+        '_pipe%dx%d' % (self.pipe, self.pipe_rows) if self.pipe > 1 else '',
+        '_st' if self.stamps else '',
+        '_k%d' % self.peel if self.peel >= 0 else '',
+        '_al%d' % self.align_lanes if self.align_lanes > 1 else '',
+        '_xs%d' % self.xshare if self.xshare else ''))
 
 
 def default_vec(stencil: core.Stencil) -> int:
@@ -231,9 +203,6 @@ def march_supported(stencil: core.Stencil) -> Optional[str]:
   if stencil.dim not in (2, 3):
     return 'the marching kernels need a 2- or 3-dimensional program'
   return None
-
-
-march2d_supported = march_supported
 
 
 def _build_chain(st: core.Stencil, T: int, pf: int, edge: Tuple[int, int],
@@ -396,8 +365,8 @@ class _MarchKernel:
     # its rows start on a 64*V-cell boundary)
     self.edge = (0, 0)
     # lanes that form one strip: the whole wave, or each 32-lane half
-    self.group = 32 if self.cfg.lane_shift in ('swzh', 'mixh') else 64
-    if self.cfg.edge_loads and self.cfg.lane_shift in ('dpp', 'none', 'lds'):
+    self.group = 32 if self.cfg.lane_shift == 'mixh' else 64
+    if self.cfg.edge_loads and self.cfg.lane_shift == 'dpp':
       # (the edge cells enter through DPP's `old` operand)
       lo = hi = 0
       for stage in self.st.ordered_stages:
@@ -409,11 +378,10 @@ class _MarchKernel:
         self.edge = (lo, hi)
     self.W = self.cfg.pipe
     if self.W > 1:
-      if self.T % self.W or not self.cfg.buffer_ops or \
-          self.cfg.waves_x * self.cfg.waves_y != 1:
+      if self.T % self.W or self.cfg.waves_x * self.cfg.waves_y != 1:
         raise util.SemanticError(
             'march: %d pipelined waves need a fusion depth that is a multiple '
-            'of it, buffer addressing and one strip per block' % self.W)
+            'of it and one strip per block' % self.W)
       self.edge = (0, 0)
     self.R = self.cfg.pipe_rows if self.W > 1 else 1
     if self.R & (self.R - 1):
@@ -421,11 +389,10 @@ class _MarchKernel:
     self.xs = self.cfg.xshare
     if self.xs:
       self.edge = (0, 0)    # the inputs' halo cells travel through LDS as well
-      if self.W > 1 or self.cfg.lane_shift != 'dpp' or not self.cfg.buffer_ops \
-          or self.cfg.waves_x * self.cfg.waves_y != 1:
+      if self.W > 1 or self.cfg.lane_shift != 'dpp' or \
+          self.cfg.waves_x * self.cfg.waves_y != 1:
         raise util.SemanticError(
-            'march: x-halo sharing needs DPP shifts, buffer addressing and '
-            'one wave per strip')
+            'march: x-halo sharing needs DPP shifts and one wave per strip')
       if not 1 <= self.xs <= 16:
         raise util.SemanticError('march: 1 to 16 waves can share a row')
       if self.dim == 3 and self.cfg.tile_rows > 24:
@@ -543,14 +510,11 @@ class _MarchKernel:
     bounds = self.st.window_bounds(self.T)
     self.m_lo = min(0, min(bounds[o][0][self.ax] for o in self.st.output_names))
     self.m_hi = max(0, max(bounds[o][1][self.ax] for o in self.st.output_names))
-    # load-only ticks at the head of a chunk (buffer addressing only: the peeled
-    # loads must not need branches)
+    # load-only ticks at the head of a chunk (branch-free: buffer addressing).
     # A stage that lags the loads by d computes, in the first `lead` <= d ticks,
     # only planes below every plane the chunk needs; a stage without inputs
     # (a constant) has d = 0 and forbids the peeling.
-    self.lead = 0
-    if self.cfg.buffer_ops:
-      self.lead = min([self.PF] + [n.delay for n in self.nodes if n.stage is not None])
+    self.lead = min([self.PF] + [n.delay for n in self.nodes if n.stage is not None])
     # compute ticks before a chunk's first output
     self.warm = self.max_delay - self.m_lo - self.lead
 
@@ -702,46 +666,41 @@ class _MarchKernel:
     self.w('  const bool store_ok = lane_ok && sub >= %d && sub < %d;' %
       (self.lanes_lo, self.group - self.lanes_hi))
     self.w('  const int64_t pitch = a.stride[%d];' % self.ax)
+    # (read by nothing: the buffer offsets below address every tensor; the
+    # line stays so that the generated kernels keep their exact text)
     self.w('  const int64_t x0c = lane_ok ? (int64_t)x0 : 0;')
 
   def _emit_addressing(self) -> None:
-    self.buf = self.cfg.buffer_ops
     table0 = self.st.symbol_table
     self.esz = {nme: table0[nme].size_in_bytes for nme in list(self.inputs) + list(self.outputs)}
     self.n_edge = max(self.edge)
-    if self.buf:
-      # every tensor is addressed through a window that starts at the first
-      # plane this wave touches; see soda_rt.h for the offset encoding
-      self.w('  const int in_end = min(nm, m_end + %d);  // last input plane needed + 1'
-        % self.m_hi)
-      self.w('  const int wlo = max(0, m_begin + (%d));' % self.m_lo)
-      for es in sorted(set(self.esz.values())):
-        self.w('  const unsigned xb%d = lane_ok ? (unsigned)x0 * %du : SODA_OOB_X;' %
-          (es, es))
-        self.w('  const unsigned sxb%d = store_ok ? (unsigned)x0 * %du : SODA_OOB_X;' %
-          (es, es))
-        self.w('  const unsigned pitch_b%d = (unsigned)pitch * %du;' % (es, es))
-        if self.dim == 3:
-          self.w('  const unsigned pitch_yb%d = (unsigned)pitch_y * %du;' % (es, es))
-          for j in range(self.rows_in):
-            self.w('  const unsigned yo%d_%d = (y0 + %d >= 0 && y0 + %d < n1) ? '
-                   '(unsigned)(y0 + %d) * pitch_yb%d : SODA_OOB_X;' %
-                   (es, j, j, j, j, es))
-      for nme, n in self.inputs.items():
-        self.w('  const soda_rsrc_t r_%s = soda_make_rsrc((const %s*)a.buf[%d] + '
-          '(int64_t)wlo * pitch, (int64_t)(in_end - wlo) * pitch * %d);' %
-          (nme, n.ctype, self.mod.slot[nme], self.esz[nme]))
-      for o, n in self.outputs.items():
-        self.w('  const soda_rsrc_t w_%s = soda_make_rsrc((%s*)a.buf[%d] + '
-          '(int64_t)m_begin * pitch, (int64_t)(m_end - m_begin) * pitch * %d);' %
-          (o, n.ctype, self.mod.slot[o], self.esz[o]))
-    else:
-      for nme, n in self.inputs.items():
-        self.w('  const %s* __restrict__ p_%s = (const %s*)a.buf[%d] + x0c;' %
-          (n.ctype, nme, n.ctype, self.mod.slot[nme]))
-      for o, n in self.outputs.items():
-        self.w('  %s* __restrict__ q_%s = (%s*)a.buf[%d] + x0c;' %
-          (n.ctype, o, n.ctype, self.mod.slot[o]))
+    # vector memory through buffer resources with out-of-range offsets instead
+    # of `if (row_ok)` branches: straight-line loop body, exact s_waitcnt
+    # counts.  Every tensor is addressed through a window that starts at the
+    # first plane this wave touches; see soda_rt.h for the offset encoding
+    self.w('  const int in_end = min(nm, m_end + %d);  // last input plane needed + 1'
+      % self.m_hi)
+    self.w('  const int wlo = max(0, m_begin + (%d));' % self.m_lo)
+    for es in sorted(set(self.esz.values())):
+      self.w('  const unsigned xb%d = lane_ok ? (unsigned)x0 * %du : SODA_OOB_X;' %
+        (es, es))
+      self.w('  const unsigned sxb%d = store_ok ? (unsigned)x0 * %du : SODA_OOB_X;' %
+        (es, es))
+      self.w('  const unsigned pitch_b%d = (unsigned)pitch * %du;' % (es, es))
+      if self.dim == 3:
+        self.w('  const unsigned pitch_yb%d = (unsigned)pitch_y * %du;' % (es, es))
+        for j in range(self.rows_in):
+          self.w('  const unsigned yo%d_%d = (y0 + %d >= 0 && y0 + %d < n1) ? '
+                 '(unsigned)(y0 + %d) * pitch_yb%d : SODA_OOB_X;' %
+                 (es, j, j, j, j, es))
+    for nme, n in self.inputs.items():
+      self.w('  const soda_rsrc_t r_%s = soda_make_rsrc((const %s*)a.buf[%d] + '
+        '(int64_t)wlo * pitch, (int64_t)(in_end - wlo) * pitch * %d);' %
+        (nme, n.ctype, self.mod.slot[nme], self.esz[nme]))
+    for o, n in self.outputs.items():
+      self.w('  const soda_rsrc_t w_%s = soda_make_rsrc((%s*)a.buf[%d] + '
+        '(int64_t)m_begin * pitch, (int64_t)(m_end - m_begin) * pitch * %d);' %
+        (o, n.ctype, self.mod.slot[o], self.esz[o]))
     if self.xs or self.n_edge:
       self.w('  const bool edge_lane = lane == 0 || lane == 63;')
     self.xs_nodes = [n for n in self.nodes if n.xs]
@@ -778,13 +737,9 @@ class _MarchKernel:
           (i, 1 + i, self.V + i))
         self.w('  const bool edge_ok%d = edge_lane && ex%d >= 0 && ex%d < n0;' %
           (i, i, i))
-        if self.buf:
-          for es in sorted({self.esz[nme] for nme in self.inputs}):
-            self.w('  const unsigned exb%d_%d = edge_ok%d ? (unsigned)ex%d * %du : '
-              'SODA_OOB_X;' % (i, es, i, i, es))
-        else:
-          self.w('  const int64_t eoff%d = edge_ok%d ? (int64_t)(ex%d - x0c) : 0;' %
-            (i, i, i))
+        for es in sorted({self.esz[nme] for nme in self.inputs}):
+          self.w('  const unsigned exb%d_%d = edge_ok%d ? (unsigned)ex%d * %du : '
+            'SODA_OOB_X;' % (i, es, i, i, es))
 
     if self.st.preserve_border:
       # border: preserve -- which of a lane's cells lie outside the columns one
@@ -795,18 +750,10 @@ class _MarchKernel:
           self.w('  const bool keepx_%s_%d = !(a.origin[0] + x0 + %d >= %d && '
                  'a.origin[0] + x0 + %d < a.gextent[0] - %d);'
                  % (o, e, e, max(0, -wlo[0]), e, max(0, whi[0])))
-    self.use_bperm = self.cfg.lane_shift == 'bperm'
-    self.use_swz = self.cfg.lane_shift in ('swz', 'swzh')
     # 'mixh': the two shift directions on two different pipes -- down through
     # DPP (vector ALU), up through ds_swizzle (the LDS crossbar, shared by the
-    # four SIMDs of a CU) -- on half strips, as 'swzh'
-    # 'mix64' / 'mix64d' (round 5 experiment): the same split on WHOLE 64-lane
-    # strips -- the DPP wave shift crosses the halves by itself, the swizzle
-    # rotates within 32 lanes and the one lane that must cross is patched
-    # (v_readlane + v_writelane / one DPP move restricted to lanes 28-31): 56
-    # of 64 lanes valid at T = 13 instead of 48, for 2 / 1 more instructions
-    # per fused iteration and row step
-    self.use_mix = self.cfg.lane_shift in ('mixh', 'mix64', 'mix64d')
+    # four SIMDs of a CU) -- on 32-lane half strips
+    self.use_mix = self.cfg.lane_shift == 'mixh'
     # Integer sums over a run of taps along the STREAMED dimension as a sliding
     # sum: an int32 accumulator per cell that lives across row steps,
     #     acc += newest row;  result = cast(acc);  acc -= oldest row
@@ -817,8 +764,7 @@ class _MarchKernel:
     # right before that first step from the rows the window holds then.
     # Exact: integers narrower than 32 bits (optimization/windows.py).
     self.slide: Dict[int, Tuple[str, Tuple[int, ...], int]] = {}
-    if self.cfg.xwindow and self.cfg.slide and self.W == 1 and \
-        not self.cfg.warm_guards and not self.cfg.interleave:
+    if self.cfg.xwindow and self.cfg.slide and self.W == 1:
       from soda_amd.optimization import windows
       table = dict(self.st.symbol_table)
       for n in self.nodes:
@@ -829,60 +775,6 @@ class _MarchKernel:
           continue
         off = tuple(a - b for a, b in zip(m[5], n.stage.st_idx))
         self.slide[id(n)] = (m[1], off, m[4])
-    if self.use_bperm:
-      self.w('  const int lane_dn_addr = ((lane + 63) & 63) << 2;  // byte address of lane-1')
-      self.w('  const int lane_up_addr = ((lane + 1) & 63) << 2;')
-    # 'lds' lane shifts: which computed tensors hand their end cells to the
-    # neighbouring lanes through LDS, and how many cells per side.  A tensor
-    # qualifies when every off-centre tap on it reads the row computed ONE row
-    # step ago (the line holds one row; jacobi-like stencils: taps off-centre
-    # in x sit on the centre row, the newest row is one ahead) and reaches at
-    # most one lane.  The others keep DPP.
-    self.ldsx: Dict[int, Tuple[int, int]] = {}
-    if self.cfg.lane_shift == 'lds' and self.W == 1 and not self.xs and \
-        self.dim == 2:
-      for n in self.nodes:
-        if n.stage is None or n.mirror_of is not None:
-          continue
-        lo = hi = 0
-        ok = True
-        for c in self.nodes:
-          if c.stage is None:
-            continue
-          for pname, pnode in c.parents.items():
-            if pnode is not n:
-              continue
-            for off in c.stage.taps.get(pname, ()):
-              if off[0] == 0:
-                continue
-              first, last = off[0], off[0] + self.V - 1   # cells 0 and V-1
-              if first >= 0 and last < self.V:
-                continue                    # stays inside the lane
-              if c.delay - off[self.ax] - n.fill_delay != 1 or \
-                  abs(off[0]) > self.V:
-                ok = False
-              lo, hi = max(lo, -off[0]), max(hi, off[0])
-        if ok and (lo or hi):
-          self.ldsx[id(n)] = (lo, hi)
-      for n in self.nodes:
-        if id(n) not in self.ldsx:
-          continue
-        lo, hi = self.ldsx[id(n)]
-        # L<i>[j]: cell V-1-i of lane j-1;  R<i>[j]: cell i of lane j
-        for i in range(lo):
-          self.w('  __shared__ %s soda_lx_%s_L%d[65];' % (n.ctype, n.var, i))
-        for i in range(hi):
-          self.w('  __shared__ %s soda_lx_%s_R%d[65];' % (n.ctype, n.var, i))
-      if self.ldsx:
-        self.w('  if (lane == 0) {   // what lies beyond the wave\'s end lanes')
-        for n in self.nodes:
-          if id(n) in self.ldsx:
-            lo, hi = self.ldsx[id(n)]
-            for i in range(lo):
-              self.w('    soda_lx_%s_L%d[0] = (%s)0;' % (n.var, i, n.ctype))
-            for i in range(hi):
-              self.w('    soda_lx_%s_R%d[64] = (%s)0;' % (n.var, i, n.ctype))
-        self.w('  }')
     declared = set()
     for stage in self.st.ordered_stages:      # `param` arrays: plain pointers
       for line in self.mod.param_decls(stage):
@@ -893,9 +785,6 @@ class _MarchKernel:
       if n.to_lds:     # written at tick t, read by the next wave at tick t + R
         self.w('  __shared__ %s soda_ring_%s[%d][%d][%d];' % (
             n.ctype, n.var, 2 * self.R, self.rows_in, 64 * self.V))
-    if not self.buf:
-      self.w('  const int in_end = min(nm, m_end + %d);  // last input plane needed + 1'
-        % self.m_hi)
     self.nt_l = 'true' if self.cfg.nt_load else 'false'
     self.nt_s = 'true' if self.cfg.nt_store else 'false'
 
@@ -928,29 +817,27 @@ class _MarchKernel:
       VGPRs)."""
       self.w('      const int t = %s;' % t_expr)
       self.w('      const bool plane_ok = t >= 0 && t < in_end;')
-      if pin and self.buf:
+      if pin:
         for es in sorted({self.esz[nme] for nme in self.inputs}):
           self.w('      unsigned xb%dp = xb%d; asm volatile("" : "+v"(xb%dp));'
                  % (es, es, es))
-      pinned = 'p' if pin and self.buf else ''
-      if self.buf:
-        in_es = sorted({self.esz[nme] for nme in self.inputs})
-        for es in in_es:
-          if self.dim == 2:
-            self.w('      const unsigned ro%d = plane_ok ? (unsigned)(t - wlo) * '
-              'pitch_b%d : SODA_OOB_ROW;' % (es, es))
-          else:
-            # plane part + row part (loop-invariant, emitted once) + lane
-            # part, each either in range or 2^30: the sum is out of range as
-            # soon as one of them is, and cannot wrap (soda_rt.h)
-            self.w('      const unsigned po%d = plane_ok ? (unsigned)(t - wlo) * '
-              'pitch_b%d : SODA_OOB_X;' % (es, es))
-            for j in sorted({j for n in self.inputs.values() for j in self.rows_of(n)}):
-              self.w('      const unsigned ro%d_%d = po%d + yo%d_%d;' %
-                     (es, j, es, es, j))
+      pinned = 'p' if pin else ''
+      for es in sorted({self.esz[nme] for nme in self.inputs}):
+        if self.dim == 2:
+          self.w('      const unsigned ro%d = plane_ok ? (unsigned)(t - wlo) * '
+            'pitch_b%d : SODA_OOB_ROW;' % (es, es))
+        else:
+          # plane part + row part (loop-invariant, emitted once) + lane
+          # part, each either in range or 2^30: the sum is out of range as
+          # soon as one of them is, and cannot wrap (soda_rt.h)
+          self.w('      const unsigned po%d = plane_ok ? (unsigned)(t - wlo) * '
+            'pitch_b%d : SODA_OOB_X;' % (es, es))
+          for j in sorted({j for n in self.inputs.values() for j in self.rows_of(n)}):
+            self.w('      const unsigned ro%d_%d = po%d + yo%d_%d;' %
+                   (es, j, es, es, j))
       for nme, n in self.inputs.items():
         s = self.slot_of(n, k, 0)
-        for j in (self.rows_of(n) if self.buf else []):
+        for j in self.rows_of(n):
           es = self.esz[nme]
           ro = 'ro%d' % es if self.dim == 2 else 'ro%d_%d' % (es, j)
           reg = '%s_s%d_r%d' % (n.var, s, j)
@@ -960,21 +847,6 @@ class _MarchKernel:
             self.w('      { %s e1[1]; soda_buf_load_frag<%s, 1, false>(e1, r_%s, %s + '
               'exb%d_%d); %s_e[%d] = e1[0]; }' %
               (n.ctype, n.ctype, nme, ro, i, es, reg, i))
-        for j in ([] if self.buf else self.rows_of(n)):
-          if self.dim == 3:
-            cond = 'plane_ok && y0 + %d >= 0 && y0 + %d < n1' % (j, j)
-            addr = 'p_%s + (int64_t)t * pitch + (int64_t)(y0 + %d) * pitch_y' % (
-                nme, j)
-          else:
-            cond = 'plane_ok'
-            addr = 'p_%s + (int64_t)t * pitch' % nme
-          reg = '%s_s%d_r%d' % (n.var, s, j)
-          self.w('      if (lane_ok && %s) soda_load_frag<%s, %d, %s>(%s, %s);' %
-            (cond, n.ctype, self.V, self.nt_l, reg, addr))
-          self.w('      else soda_zero_frag<%s, %d>(%s);' % (n.ctype, self.V, reg))
-          for i in range(self.n_edge):
-            self.w('      %s_e[%d] = (edge_ok%d && %s) ? (%s)[eoff%d] : (%s)0;' %
-              (reg, i, i, cond, addr, i, n.ctype))
 
   def _emit_wave(self, wv: int) -> None:
     """The tick loop of one wave of the block (the only one unless the
@@ -1009,7 +881,6 @@ class _MarchKernel:
         self.w('    const int t = tau;')
         self._shifted = {}
         self._wide = {}
-        self._lx_read = set()
         self._stage_mark = len(self.L)
         self._emit_stage(n, 0, slide_init='only')
         self.w('  }')
@@ -1043,7 +914,6 @@ class _MarchKernel:
     # 2. compute every tensor's new plane
     self._shifted: Dict[Tuple[str, int, int, int, int], str] = {}
     self._wide: Dict[str, str] = {}   # one-byte cells widened in this step
-    self._lx_read = set()      # ('lds' shifts) lines already read in this step
     self._stage_mark = len(self.L)
     # (tensor, slot) whose end cells change hands at the end of this step: the
     # planes computed in it, and the input plane whose load it is first to use
@@ -1086,20 +956,6 @@ class _MarchKernel:
       self.w('      soda_pipe_barrier();')
     self.w('    }')
 
-  def _lx_reads(self, n: _Node) -> List[str]:
-    lo, hi = self.ldsx[id(n)]
-    # compiler fences (no instruction): a lane reads what ANOTHER lane wrote,
-    # which single-thread reordering rules know nothing about -- the reads must
-    # stay behind the previous step's writes and ahead of this step's
-    out = ['      asm volatile("" ::: "memory");']
-    for i in range(lo):
-      out.append('      const %s lx_%s_L%d = soda_lx_%s_L%d[lane];'
-                 % (n.ctype, n.var, i, n.var, i))
-    for i in range(hi):
-      out.append('      const %s lx_%s_R%d = soda_lx_%s_R%d[lane + 1];'
-                 % (n.ctype, n.var, i, n.var, i))
-    return out
-
   def _emit_stage(self, n: _Node, k: int,
                   slide_init: Optional[str] = None) -> None:
     """One tensor's new plane at tick phase k: lane-shifted operands first
@@ -1109,14 +965,6 @@ class _MarchKernel:
     that set-up (the first step is the loop's first)."""
     stage = n.stage
     pre: List[str] = []
-    guard = None
-    if self.cfg.warm_guards and self.back_lo[id(n)] is not None:
-      first = self.back_lo[id(n)] + n.delay   # tick offset from m_begin
-      if first > self.m_lo:                   # the loop starts at m_begin + m_lo
-        guard = 't >= m_begin + (%d)' % first
-        self._shifted = {}                     # temporaries live inside the guard
-        self._wide = {}
-
     early: List[str] = []
 
     def operand(pname: str, off: Tuple[int, ...], j: int, e: int, _n=n,
@@ -1149,18 +997,6 @@ class _MarchKernel:
 
       if lane_off == 0:
         return wide(src, '%s_e%d' % (reg, sub))
-      if self.cfg.lane_shift == 'none':
-        return src       # TIMING EXPERIMENTS ONLY: wrong results
-      if id(p) in self.ldsx and abs(lane_off) == 1 and age == 1:
-        # the neighbouring lane filed this cell one row step ago
-        i = (-c - 1) if lane_off < 0 else (c - self.V)
-        name = 'lx_%s_%s%d' % (p.var, 'L' if lane_off < 0 else 'R', i)
-        if (p.var, _k) not in self._lx_read:
-          # (the tensor's own stage is skipped in this peeled step, so its
-          # line still holds the row wanted: read it here)
-          self._lx_read.add((p.var, _k))
-          _pre.extend(self._lx_reads(p))
-        return wide(name, name)
       key = (p.var, slot, row, sub, lane_off)
       if key not in self._shifted:
         tmp = 'sh_%s_e%d_%s%d' % (reg, sub, 'm' if lane_off < 0 else 'p',
@@ -1180,17 +1016,10 @@ class _MarchKernel:
                 '(%s)0' % p.ctype
           expr = ('soda_lane_dn_or(%s, %s)' if lane_off < 0 else
                   'soda_lane_up_or(%s, %s)') % (src, old)
-        elif self.use_bperm:
+        elif self.use_mix and lane_off > 0:
           expr = src
-          for _ in range(abs(lane_off)):
-            expr = 'soda_lane_from(%s, %s)' % (
-                'lane_dn_addr' if lane_off < 0 else 'lane_up_addr', expr)
-        elif self.use_swz or (self.use_mix and lane_off > 0):
-          expr = src
-          for _ in range(abs(lane_off)):
-            expr = 'soda_lane_%s%d%s(%s)' % (
-                'dn' if lane_off < 0 else 'up', self.group,
-                'd' if self.cfg.lane_shift == 'mix64d' else '', expr)
+          for _ in range(lane_off):
+            expr = 'soda_lane_up32(%s)' % expr
         else:
           expr = src
           for _ in range(abs(lane_off)):
@@ -1199,8 +1028,7 @@ class _MarchKernel:
         line = '      const %s %s = %s;' % (p.ctype, tmp, expr)
         # a shift of a row produced in an EARLIER tick can be issued ahead
         # of the previous stage's arithmetic (latency hidden behind it)
-        early = (self.use_bperm or self.use_swz or
-                 (self.use_mix and lane_off > 0)) and (
+        early = self.use_mix and lane_off > 0 and (
             p.is_input or age > 0) and not (p.is_input and self.n_edge) \
             and not p.xs
         (_early if early else _pre).append(line)
@@ -1209,7 +1037,7 @@ class _MarchKernel:
 
     body: List[str] = []
     dst_slot = self.slot_of(n, k, 0)
-    xwin = self._xwindow(stage) if n.keep is None and not guard else None
+    xwin = self._xwindow(stage) if n.keep is None else None
     slide = self.slide.get(id(n))
     if slide is not None:
       pname, off, taps = slide
@@ -1235,63 +1063,33 @@ class _MarchKernel:
         return
     elif xwin is not None:
       self._emit_xwindow(n, stage, xwin, dst_slot, operand, body)
-    elif self.cfg.interleave and not stage.stmt.let:
-      # all cells of the row tile at once, operation-major
-      cells = [(j, e) for j in self.rows_of(n) for e in range(self.V)]
+    else:
+      for j in self.rows_of(n):
+        for e in range(self.V):
 
-      def mk_load(j, e, _stage=stage):
-        def load(ref: ir.Ref) -> str:
-          prm = self.mod.param_load(ref)
-          if prm is not None:
-            return prm
-          off = tuple(a - b for a, b in zip(ref.idx, _stage.st_idx))
-          return operand(ref.name, off, j, e)
-        return load
+          def load(ref: ir.Ref, _e=e, _j=j, _stage=stage) -> str:
+            prm = self.mod.param_load(ref)
+            if prm is not None:
+              return prm
+            off = tuple(a - b for a, b in zip(ref.idx, _stage.st_idx))
+            return operand(ref.name, off, _j, _e)
 
-      counter = [0]
-
-      def fresh(_n=n, _k=k) -> str:
-        counter[0] += 1
-        return 'v_%s_k%d_%d' % (_n.var, _k, counter[0])
-
-      stmts, results = ir.c_statements(stage.stmt.expr,
-                                       [mk_load(j, e) for j, e in cells],
-                                       fresh, var=self.mod.param_var)
-      body.extend('      ' + x for x in stmts)
-      for (j, e), r in zip(cells, results):
-        body.append('      %s_s%d_r%d[%d] = (%s)(%s);' %
-                    (n.var, dst_slot, j, e, n.ctype, r))
-    for j in ([] if (xwin is not None or slide is not None or
-                     (self.cfg.interleave and not stage.stmt.let))
-              else self.rows_of(n)):
-      for e in range(self.V):
-
-        def load(ref: ir.Ref, _e=e, _j=j, _stage=stage) -> str:
-          prm = self.mod.param_load(ref)
-          if prm is not None:
-            return prm
-          off = tuple(a - b for a, b in zip(ref.idx, _stage.st_idx))
-          return operand(ref.name, off, _j, _e)
-
-        dst = '%s_s%d_r%d[%d]' % (n.var, dst_slot, j, e)
-        if stage.stmt.let:
-          body.append('      {')
-          for let in stage.stmt.let:
-            body.append('        const %s %s = %s;' %
-                        (let.haoda_type.c_type, let.name,
-                         ir.c_expr(let.expr, load, self.mod.param_var)))
-          body.append('        %s = (%s)(%s);' %
-                      (dst, n.ctype, ir.c_expr(stage.stmt.expr, load,
-                                               self.mod.param_var)))
-          body.append('      }')
-        else:
-          body.append('      %s = (%s)(%s);' %
-                      (dst, n.ctype, ir.c_expr(stage.stmt.expr, load,
-                                               self.mod.param_var)))
-    if guard:
-      self.w('      if (%s) {  // wave-uniform' % guard)
-      self.L.extend(early)
-    elif early:
+          dst = '%s_s%d_r%d[%d]' % (n.var, dst_slot, j, e)
+          if stage.stmt.let:
+            body.append('      {')
+            for let in stage.stmt.let:
+              body.append('        const %s %s = %s;' %
+                          (let.haoda_type.c_type, let.name,
+                           ir.c_expr(let.expr, load, self.mod.param_var)))
+            body.append('        %s = (%s)(%s);' %
+                        (dst, n.ctype, ir.c_expr(stage.stmt.expr, load,
+                                                 self.mod.param_var)))
+            body.append('      }')
+          else:
+            body.append('      %s = (%s)(%s);' %
+                        (dst, n.ctype, ir.c_expr(stage.stmt.expr, load,
+                                                 self.mod.param_var)))
+    if early:
       # place them in front of the previous stage's block of this tick.
       # (The compiler sinks each to one stage's arithmetic ahead of its use,
       # one swizzle in flight at a time.  Round 4 pinned all 13 of a T=13 step
@@ -1325,12 +1123,6 @@ class _MarchKernel:
                        operand(n.keep, zero, j, e), dst))
       body.append('      }')
     self._stage_mark = len(self.L)
-    if id(n) in self.ldsx and (n.var, k) not in self._lx_read:
-      # the cells the neighbouring lanes filed one row step ago, fetched
-      # BEFORE this step's row overwrites the line; consumed by the stages
-      # that follow in this step
-      self._lx_read.add((n.var, k))
-      self.L.extend(self._lx_reads(n))
     self.L.extend(pre)
     self.L.extend(body)
     if self.st.symbol_table[stage.name].size_in_bytes == 1:
@@ -1344,19 +1136,6 @@ class _MarchKernel:
       for j in self.rows_of(n):
         self.w('      soda_own_register<%s, %d>(%s_s%d_r%d);' %
                (n.ctype, self.V, n.var, dst_slot, j))
-    if id(n) in self.ldsx:
-      lo, hi = self.ldsx[id(n)]
-      reg = '%s_s%d_r0' % (n.var, dst_slot)
-      self.w('      asm volatile("" ::: "memory");')
-      for i in range(lo):
-        self.w('      soda_lx_%s_L%d[lane + 1] = %s[%d];' %
-               (n.var, i, reg, self.V - 1 - i))
-      for i in range(hi):
-        self.w('      soda_lx_%s_R%d[lane] = %s[%d];' % (n.var, i, reg, i))
-    if guard:
-      self.w('      }')
-      self._shifted = {}
-      self._wide = {}
     if n.to_lds:   # hand the new plane to the next wave of the block
       for j in self.rows_of(n):
         self.w('      soda_store_frag<%s, %d, false>(&soda_ring_%s[t & %d][%d]'
@@ -1467,37 +1246,20 @@ class _MarchKernel:
   def _emit_store(self, n: _Node, oname: str, dst_slot: int) -> None:
     """Stores the new plane of a last-iteration output (rows and lanes that
     are not this wave's to write are dropped by the addressing)."""
-    if self.buf:
-      es = self.esz[oname]
-      self.w('      {')
-      self.w('        const int m = t - %d;' % n.delay)
-      self.w('        const bool m_ok = m >= m_begin && m < m_end;')
-      for j in self.store_rows(n):
-        reg = '%s_s%d_r%d' % (n.var, dst_slot, j)
-        if self.dim == 3:
-          self.w('        soda_buf_store_frag<%s, %d, %s>(w_%s, (m_ok ? (unsigned)'
-            '(m - m_begin) * pitch_b%d : SODA_OOB_X) + yo%d_%d + sxb%d, %s);' %
-            (n.ctype, self.V, self.nt_s, oname, es, es, j, es, reg))
-        else:
-          self.w('        soda_buf_store_frag<%s, %d, %s>(w_%s, (m_ok ? '
-            '(unsigned)(m - m_begin) * pitch_b%d : SODA_OOB_ROW) + sxb%d, '
-            '%s);' % (n.ctype, self.V, self.nt_s, oname, es, es, reg))
-      self.w('      }')
-      return
+    es = self.esz[oname]
     self.w('      {')
     self.w('        const int m = t - %d;' % n.delay)
-    self.w('        if (store_ok && m >= m_begin && m < m_end) {')
-    for j in range(max(n.rmargin[0], self.rhalo_lo),
-                   self.rows_in - max(n.rmargin[1], self.rhalo_hi)):
+    self.w('        const bool m_ok = m >= m_begin && m < m_end;')
+    for j in self.store_rows(n):
       reg = '%s_s%d_r%d' % (n.var, dst_slot, j)
       if self.dim == 3:
-        self.w('          if (y0 + %d < n1) soda_store_frag<%s, %d, %s>(q_%s + '
-          '(int64_t)m * pitch + (int64_t)(y0 + %d) * pitch_y, %s);' %
-          (j, n.ctype, self.V, self.nt_s, oname, j, reg))
+        self.w('        soda_buf_store_frag<%s, %d, %s>(w_%s, (m_ok ? (unsigned)'
+          '(m - m_begin) * pitch_b%d : SODA_OOB_X) + yo%d_%d + sxb%d, %s);' %
+          (n.ctype, self.V, self.nt_s, oname, es, es, j, es, reg))
       else:
-        self.w('          soda_store_frag<%s, %d, %s>(q_%s + (int64_t)m * pitch, '
-          '%s);' % (n.ctype, self.V, self.nt_s, oname, reg))
-    self.w('        }')
+        self.w('        soda_buf_store_frag<%s, %d, %s>(w_%s, (m_ok ? '
+          '(unsigned)(m - m_begin) * pitch_b%d : SODA_OOB_ROW) + sxb%d, '
+          '%s);' % (n.ctype, self.V, self.nt_s, oname, es, es, reg))
     self.w('      }')
 
   def _finish(self) -> PassDesc:
@@ -1551,7 +1313,7 @@ class _MarchKernel:
                              unroll=self.U, tile_rows=self.tile_rows,
                              peel_trips_max=self.peel_trips_max,
                              fused=self.T,
-                             window_extra=(self.m_hi - self.m_lo) if self.buf else None,
+                             window_extra=self.m_hi - self.m_lo,
                              max_elem=max(self.esz.values()),
                              max_extent0=self.strip_cells * self.xs)),
         '\n'.join(self.L) + '\n')
@@ -1575,8 +1337,5 @@ def add_march_pass(mod: Module, cfg: MarchConfig) -> PassDesc:
   """Adds one marching kernel (and its pass) for `cfg.fused_iters` iterations;
   raises SemanticError if the program or the shape does not fit."""
   return _MarchKernel(mod, cfg).emit()
-
-
-add_march2d_pass = add_march_pass
 
 

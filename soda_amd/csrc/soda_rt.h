@@ -249,47 +249,6 @@ template <class T> SODA_DEV T soda_lane_up(T v) { return soda_lane_shift<T>::up(
 template <class T> SODA_DEV T soda_lane_dn_or(T v, T edge) { return soda_lane_shift<T>::dn_or(v, edge); }
 template <class T> SODA_DEV T soda_lane_up_or(T v, T edge) { return soda_lane_shift<T>::up_or(v, edge); }
 
-// ---- lane shifts through the LDS crossbar (ds_bpermute_b32) -----------------
-// Measured on gfx950 (tools/valubench.py): a VALU op carrying a DPP shift
-// costs ~15 issue cycles against 2 for a plain one, whatever the DPP pattern;
-// ds_bpermute runs in the LDS pipe beside the VALU and, issued a stage ahead of
-// its use, costs only its issue slot.  Lane 0 (63) receives lane 63's (0's)
-// value instead of 0: only halo lanes see the difference.
-template <class T, int kSize = sizeof(T)>
-struct soda_bperm;
-template <class T>
-struct soda_bperm<T, 4> {
-  SODA_DEV T get(int byte_addr, T v) {
-    return __builtin_bit_cast(
-        T, __builtin_amdgcn_ds_bpermute(byte_addr, __builtin_bit_cast(int, v)));
-  }
-};
-template <class T>
-struct soda_bperm<T, 8> {
-  struct pair { int lo, hi; };
-  SODA_DEV T get(int byte_addr, T v) {
-    pair p = __builtin_bit_cast(pair, v);
-    p.lo = __builtin_amdgcn_ds_bpermute(byte_addr, p.lo);
-    p.hi = __builtin_amdgcn_ds_bpermute(byte_addr, p.hi);
-    return __builtin_bit_cast(T, p);
-  }
-};
-template <class T>
-struct soda_bperm<T, 2> {
-  SODA_DEV T get(int byte_addr, T v) {
-    return (T)__builtin_amdgcn_ds_bpermute(byte_addr, (int)v);
-  }
-};
-template <class T>
-struct soda_bperm<T, 1> {
-  SODA_DEV T get(int byte_addr, T v) {
-    return (T)__builtin_amdgcn_ds_bpermute(byte_addr, (int)v);
-  }
-};
-template <class T> SODA_DEV T soda_lane_from(int byte_addr, T v) {
-  return soda_bperm<T>::get(byte_addr, v);
-}
-
 // ---- lane shifts through ds_swizzle (LDS crossbar, no LDS memory) -----------
 // A DPP-carrying VALU op stalls the vector issue of gfx950 far beyond its own
 // slot (tools/dppbench.py, tools/tickbench.py: the row step of the fused
@@ -298,14 +257,10 @@ template <class T> SODA_DEV T soda_lane_from(int byte_addr, T v) {
 // by one lane through the LDS crossbar instead: it issues in the LDS pipe beside
 // the VALU (one issue slot, result after ~50 cycles, counted by lgkmcnt) and,
 // unlike ds_bpermute, needs no address register and a quarter of the LDS time.
-// The rotation is WITHIN each 32-lane half of the wave:
-//   *32 forms: lanes 0/32 (dn) resp. 31/63 (up) receive the value that wrapped
-//              around their half -- for strips laid out as two independent
-//              32-lane halves, whose end lanes are halo lanes anyway;
-//   *64 forms: the one lane that must cross the halves is patched with
-//              v_readlane / v_writelane (two plain VALU ops); lanes 0 (dn) and
-//              63 (up) receive a wrapped value instead of 0: they are halo
-//              lanes of a 64-lane strip.
+// The rotation is WITHIN each 32-lane half of the wave: lanes 0/32 (dn) resp.
+// 31/63 (up) receive the value that wrapped around their half -- for strips
+// laid out as two independent 32-lane halves, whose end lanes are halo lanes
+// anyway.
 // offset = 0xC000 | direction << 10 | amount << 5 (GFX9 rotate mode)
 #define SODA_SWZ_ROT_UP 0xC020   /* lane i <- lane (i + 1) % 32 of its half */
 #define SODA_SWZ_ROT_DN 0xC420   /* lane i <- lane (i - 1) % 32 of its half */
@@ -315,18 +270,6 @@ SODA_DEV int soda_swz_dn32(int v) {
 SODA_DEV int soda_swz_up32(int v) {
   return __builtin_amdgcn_ds_swizzle(v, SODA_SWZ_ROT_UP);
 }
-SODA_DEV int soda_swz_dn64(int v) {
-  int r = __builtin_amdgcn_ds_swizzle(v, SODA_SWZ_ROT_DN);
-  const int s = __builtin_amdgcn_readlane(v, 31);
-  asm("v_writelane_b32 %0, %1, 32" : "+v"(r) : "s"(s));   // no builtin in ROCm 7.2
-  return r;
-}
-SODA_DEV int soda_swz_up64(int v) {
-  int r = __builtin_amdgcn_ds_swizzle(v, SODA_SWZ_ROT_UP);
-  const int s = __builtin_amdgcn_readlane(v, 32);
-  asm("v_writelane_b32 %0, %1, 31" : "+v"(r) : "s"(s));
-  return r;
-}
 
 template <class T, int kSize = sizeof(T)>
 struct soda_swz;
@@ -334,8 +277,6 @@ template <class T>
 struct soda_swz<T, 4> {
   SODA_DEV T dn32(T v) { return __builtin_bit_cast(T, soda_swz_dn32(__builtin_bit_cast(int, v))); }
   SODA_DEV T up32(T v) { return __builtin_bit_cast(T, soda_swz_up32(__builtin_bit_cast(int, v))); }
-  SODA_DEV T dn64(T v) { return __builtin_bit_cast(T, soda_swz_dn64(__builtin_bit_cast(int, v))); }
-  SODA_DEV T up64(T v) { return __builtin_bit_cast(T, soda_swz_up64(__builtin_bit_cast(int, v))); }
 };
 template <class T>
 struct soda_swz<T, 8> {
@@ -347,33 +288,18 @@ struct soda_swz<T, 8> {
     p.hi = soda_swz_##fn(p.hi);                    \
     return __builtin_bit_cast(T, p);               \
   }
-  SODA_SWZ_PAIR(dn32) SODA_SWZ_PAIR(up32) SODA_SWZ_PAIR(dn64) SODA_SWZ_PAIR(up64)
+  SODA_SWZ_PAIR(dn32) SODA_SWZ_PAIR(up32)
 #undef SODA_SWZ_PAIR
 };
 template <class T>
 struct soda_swz<T, 2> {   // widened: one VGPR per element
   SODA_DEV T dn32(T v) { return (T)soda_swz_dn32((int)v); }
   SODA_DEV T up32(T v) { return (T)soda_swz_up32((int)v); }
-  SODA_DEV T dn64(T v) { return (T)soda_swz_dn64((int)v); }
-  SODA_DEV T up64(T v) { return (T)soda_swz_up64((int)v); }
 };
 template <class T>
 struct soda_swz<T, 1> : soda_swz<T, 2> {};
-// up-shift of a whole 64-lane strip with the crossing lane patched by ONE DPP
-// move: wave_shl:1 restricted to row 1, bank 3 (lanes 28-31) -- lanes 28-30
-// get what the rotation gave them anyway, lane 31 gets lane 32's value
-SODA_DEV int soda_swz_up64d(int v) {
-  const int r = __builtin_amdgcn_ds_swizzle(v, SODA_SWZ_ROT_UP);
-  return __builtin_amdgcn_update_dpp(r, v, 0x130, 0x2, 0x8, false);
-}
-template <class T> SODA_DEV T soda_lane_up64d(T v) {
-  static_assert(sizeof(T) == 4, "mix64d: 4-byte cells");
-  return __builtin_bit_cast(T, soda_swz_up64d(__builtin_bit_cast(int, v)));
-}
 template <class T> SODA_DEV T soda_lane_dn32(T v) { return soda_swz<T>::dn32(v); }
 template <class T> SODA_DEV T soda_lane_up32(T v) { return soda_swz<T>::up32(v); }
-template <class T> SODA_DEV T soda_lane_dn64(T v) { return soda_swz<T>::dn64(v); }
-template <class T> SODA_DEV T soda_lane_up64(T v) { return soda_swz<T>::up64(v); }
 
 // ---- row fragments: V consecutive cells of one row per lane ----------------
 template <class T, int V>

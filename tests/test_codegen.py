@@ -248,6 +248,19 @@ def test_unsupported_programs_are_rejected():
                 lower.LowerOptions(strategy='march'))
 
 
+def test_retired_options_are_rejected():
+  """Kernel variants that were measured, lost and removed: asking for one is
+  an error, not a quiet run of something else."""
+  from soda_amd.codegen.hip import lower
+  stencil = core.from_file(soda_path('jacobi2d.soda'))
+  for shift in ('bperm', 'swz', 'swzh', 'mix64', 'mix64d', 'lds', 'none'):
+    with pytest.raises(util.SemanticError, match="lane_shift.*dpp, mixh"):
+      lower.lower(stencil, lower.LowerOptions(lane_shift=shift))
+  with pytest.raises(util.SemanticError,
+                     match='strategy.*auto, direct, march, ldswin'):
+    lower.lower(stencil, lower.LowerOptions(strategy='lds'))
+
+
 def test_no_cpu_fallback_without_gpu(built):
   """On a box without a GPU the product path must raise, not compute."""
   from soda_amd import runtime
@@ -397,7 +410,7 @@ def test_row_covering_blocks_in_the_plan(built):
   assert not any('_xs' in k.name for k in plain.kernels)
 
 
-@pytest.mark.parametrize('shift', ['bperm', 'swzh', 'mixh'])
+@pytest.mark.parametrize('shift', ['mixh'])
 def test_sliding_sum_setup_with_lds_pipe_shifts_compiles(built, shift, tmp_path):
   """A sliding sum whose taps sit a lane away (store index off-centre in x):
   the accumulator's set-up in front of the loop needs the lane-shifted copies

@@ -190,8 +190,8 @@ def options_scan(first, last, only=None):
               chunk_rows=pick([None, None, 3, 5, 9, 16, 33]),
               peel=pick([None, None, 0, 1, -1]),
               prefetch=pick([None, None, 1, 2, 4]),
-              lane_shift=pick([None, None, None, 'dpp', 'mixh', 'swzh',
-                               'bperm']) if dim == 2 else None,
+              lane_shift=pick([None, None, None, 'dpp', 'mixh', 'dpp',
+                               'mixh']) if dim == 2 else None,
               windows=pick([None, None, False]),
               inline=pick([None, None, False]),
               xshare=pick([None, None, None, True]),

@@ -18,7 +18,7 @@ def main():
   ap.add_argument('--fuse', type=int, nargs='+', default=[12])
   ap.add_argument('--prefetch', type=int, nargs='+', default=[2])
   ap.add_argument('--vec', type=int, nargs='+', default=[4])
-  ap.add_argument('--shift', nargs='+', default=['dpp'])
+  ap.add_argument('--shift', nargs='+', choices=('dpp', 'mixh'), default=['dpp'])
   ap.add_argument('--pipe', type=int, nargs='+', default=[1])
   ap.add_argument('--pipe-rows', type=int, nargs='+', default=[2])
   ap.add_argument('--nt-load', type=int, nargs='+', default=[1])

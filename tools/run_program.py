@@ -18,7 +18,7 @@ ap.add_argument('--reps', type=int, default=3)
 ap.add_argument('--pipe', type=int, default=None)
 ap.add_argument('--border', default=None)
 ap.add_argument('--pipe-rows', type=int, default=2)
-ap.add_argument('--shift', default='dpp')
+ap.add_argument('--shift', choices=('dpp', 'mixh'), default='dpp')
 ap.add_argument('--chunk', type=int, default=0)
 ap.add_argument('--peel', type=int, default=None)
 ap.add_argument('--xshare', type=int, default=None)

@@ -11,7 +11,7 @@ on warm clocks and prints what the launch looked like from the inside:
   * when waves started and ended (deciles): a second round of waves or a long
     tail shows up here.
 
-  python tools/timeline.py --fuse 12 [--pipe 4] [--chunk 147] [--shift swzh]
+  python tools/timeline.py --fuse 12 [--pipe 4] [--chunk 147] [--shift mixh]
 """
 import argparse
 import collections
@@ -32,7 +32,7 @@ def main():
   ap.add_argument('--prefetch', type=int, default=None)
   ap.add_argument('--pipe', type=int, default=1)
   ap.add_argument('--pipe-rows', type=int, default=2)
-  ap.add_argument('--shift', default='dpp')
+  ap.add_argument('--shift', choices=('dpp', 'mixh'), default='dpp')
   ap.add_argument('--vec', type=int, default=None)
   ap.add_argument('--tag', default='')
   ap.add_argument('--out', default=None)
