@@ -42,15 +42,17 @@ def add_arguments(parser) -> None:
   parser.add_argument('--hip-strategy', type=str, dest='hip_strategy',
                       choices=lower.STRATEGIES, default='auto',
                       help='kernel family: register-marching wavefront strips '
-                      '(2-D / 3-D programs), the LDS window ring (2-D) or the '
-                      'direct kernels')
+                      '(2-D / 3-D programs), the LDS window ring (2-D), the '
+                      'direct kernels, or tile3d: LDS-tiled 3-D kernels that '
+                      'fuse every depth of --hip-fuse (never picked by auto)')
   parser.add_argument('--hip-fuse', type=int, nargs='*', dest='hip_fuse',
                       metavar='T', default=list(lower.DEFAULT_FUSE),
                       help='temporal blocking: the numbers of iterations a '
                       'launch may fuse; the library mixes them per extent '
                       '(default: %s; depths that do not fit the registers ' %
                       ' '.join(map(str, lower.DEFAULT_FUSE)) +
-                      'are dropped, 3-D programs fuse at most 2)')
+                      'are dropped, 3-D programs fuse at most 2 unless '
+                      '--hip-strategy tile3d)')
   parser.add_argument('--hip-vec', type=int, dest='hip_vec', metavar='V',
                       help='cells per lane per row (default: 16 bytes worth)')
   parser.add_argument('--hip-chunk-rows', type=int, dest='hip_chunk_rows',

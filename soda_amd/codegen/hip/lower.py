@@ -3,7 +3,7 @@
 What the reference's HLS emitter does for an FPGA (reference
 src/soda/codegen/xilinx/hls_kernel.py:338-410 `print_code`, :665-886
 `print_module_definition`; src/soda/dataflow.py:336-625) is done here for a
-GPU.  Three families of kernels are generated:
+GPU.  Four families of kernels are generated:
 
 `direct`   one kernel per stage, 16 bytes' worth of cells per thread, parents
            read straight from global memory into per-thread row buffers
@@ -34,13 +34,17 @@ GPU.  Three families of kernels are generated:
            the window rows live in an LDS ring that a block's waves fill
            together, every lane computes 8 cells, no lane shifts.
 
+`tile3d`   3-D programs, on request only: a block marches a tile along
+           dimension 2 with the planes of every fused level in LDS rings, so
+           the fusion depth is bounded by LDS, not by registers (tile3d.py).
+
 Floating-point results are bit-identical to the CPU oracle because the kernels
 compile the same C expression text with -ffp-contract=off.
 
 Layout of the package: module.py (Module, descriptors, the device runtime
-text), march.py (`march2d` / `march3d`), ldswin.py, direct.py; this file holds
-the options and `lower()`, which picks the family and the shape (DESIGN.md
-section 4.3).
+text), march.py (`march2d` / `march3d`), ldswin.py, tile3d.py, direct.py; this
+file holds the options and `lower()`, which picks the family and the shape
+(DESIGN.md section 4.3).
 """
 import dataclasses
 import os
@@ -59,6 +63,8 @@ from soda_amd.codegen.hip.march import (LANE_SHIFTS, MAX_FUSE_3D,  # noqa: F401
                                         MAX_UNROLL, REG_BUDGET, MarchConfig,
                                         add_march_pass, default_vec,
                                         march_supported)
+from soda_amd.codegen.hip.tile3d import (add_tile3d_pass,  # noqa: F401
+                                         tile3d_supported)
 
 # ---------------------------------------------------------------------------
 # whole module
@@ -76,7 +82,7 @@ SLIDING_SUMS = os.environ.get('SODA_HIP_SLIDE', '1') != '0'
 
 
 # kernel families lower() can be asked for (LowerOptions.strategy)
-STRATEGIES = ('auto', 'direct', 'march', 'ldswin')
+STRATEGIES = ('auto', 'direct', 'march', 'ldswin', 'tile3d')
 
 
 @dataclasses.dataclass(kw_only=True, eq=False)
@@ -144,6 +150,13 @@ class LowerOptions:
   # consumers (optimization/pointwise.py): denoise3d is 4 tensors instead
   # of 10.  SODA_HIP_INLINE=0/1 overrides for A/B runs
   inline: Optional[bool] = None
+  # `tile3d`: cells along x (a multiple of 64) and rows along y of a block's
+  # LDS tile, ghost cells included, and the waves of the block (they divide
+  # the rows); None: tile3d.py picks (64 cells, the height its LDS rule
+  # allows, 8 / 4 / 2 / 1 waves)
+  tile3d_w: Optional[int] = None
+  tile3d_h: Optional[int] = None
+  tile3d_waves: Optional[int] = None
 
   def __post_init__(self):
     self.fuse = tuple(self.fuse)
@@ -262,6 +275,8 @@ def lower(stencil: core.Stencil, opts: Optional[LowerOptions] = None) -> Module:
                              (opts.lane_shift, ', '.join(LANE_SHIFTS)))
   _check_native(stencil)
   stencil.check_preserve()
+  if opts.strategy == 'tile3d' and tile3d_supported(stencil):
+    raise util.SemanticError('tile3d: %s' % tile3d_supported(stencil))
   # arithmetic per cell of one iteration AS WRITTEN (the rewrites below fold
   # and split statements; what the shape ladder wants to know is how much the
   # program computes)
@@ -322,7 +337,7 @@ def lower(stencil: core.Stencil, opts: Optional[LowerOptions] = None) -> Module:
     from soda_amd.optimization import windows
     # (the marching kernels reduce dimension-0 windows themselves, all cells
     # of a lane jointly; `direct` kernels get chains in every dimension)
-    marching = opts.strategy in ('auto', 'march') and \
+    marching = opts.strategy in ('auto', 'march', 'tile3d') and \
         march_supported(stencil) is None
     skip = ()
     if marching:
@@ -338,7 +353,7 @@ def lower(stencil: core.Stencil, opts: Optional[LowerOptions] = None) -> Module:
   from soda_amd.codegen.hip import exact
   stencil = exact.specialize(stencil)
   mod = Module(stencil)
-  use_march = opts.strategy in ('auto', 'march') and \
+  use_march = opts.strategy in ('auto', 'march', 'tile3d') and \
       march_supported(stencil) is None
   if opts.strategy == 'march' and not use_march:
     raise util.SemanticError('march: %s' % march_supported(stencil))
@@ -363,6 +378,10 @@ def lower(stencil: core.Stencil, opts: Optional[LowerOptions] = None) -> Module:
       cap = min(cap, MAX_FUSE_PRESERVE)
     depths = sorted({min(t, cap) for t in opts.fuse if iterable} - {0, 1},
                     reverse=True)
+    if opts.strategy == 'tile3d':
+      # the fused passes are tile3d's (below); the marching family supplies
+      # the one-iteration pass, as under `auto`
+      depths = []
 
     def peel_for(t: int) -> int:
       if opts.peel is None:
@@ -490,5 +509,28 @@ def lower(stencil: core.Stencil, opts: Optional[LowerOptions] = None) -> Module:
         add_march_pass(mod, config(1, vec, pf1, rows1))
   if not use_march:
     add_direct_pass(mod, opts.vec or 1)
+  if opts.strategy == 'tile3d':
+    # one pass per requested depth, clipped to the iteration count only: the
+    # planes live in LDS, MAX_FUSE_3D (registers) does not bind.  A depth whose
+    # rings do not fit is dropped; an explicit request that ends with no fused
+    # pass at all hears why
+    depths = sorted({min(t, stencil.iterate) for t in opts.fuse} - {0, 1},
+                    reverse=True)
+    refusal = None
+    built = 0
+    for t in depths:
+      try:
+        add_tile3d_pass(mod, t, tile_w=opts.tile3d_w, tile_h=opts.tile3d_h,
+                        waves=opts.tile3d_waves, chunk=opts.chunk_rows,
+                        nt_load=bool(opts.nt_load),
+                        nt_store=bool(opts.nt_store),
+                        xcd_swizzle=opts.xcd_swizzle)
+        built += 1
+      except util.SemanticError as e:
+        refusal = refusal or e
+    if not built:
+      raise refusal or util.SemanticError(
+          'tile3d: no fusion depth of 2 or more to build (iterate %d, fuse %s)'
+          % (stencil.iterate, list(opts.fuse)))
   return mod
 

@@ -482,7 +482,9 @@ def make_plan(mod: lower.Module,
       d.step_ns = float(tune.get('step_ops') or 0.0) * NS_PER_VALU_OP * (
           MIXH_FACTOR if tune.get('lane_shift') == 'mixh' else 1.0)
       d.warm_saved = float(tune.get('warm_saved') or 0.0)
-      d.bytes_per_cell = io_bytes
+      # (a kernel the time model has no constants for stays unmodelled: the
+      # scheduler then goes deepest first until the clock has timed the passes)
+      d.bytes_per_cell = 0.0 if tune.get('unmodelled') else io_bytes
       d.lane_redundancy = float(tune.get('lane_redundancy') or 1.0)
       d.max_extent0 = int(tune.get('max_extent0') or 0)
   passes = mod.sorted_passes()
@@ -840,13 +842,19 @@ def resolve_options(stencil: core.Stencil,
     if shape:
       out.vec, out.prefetch = shape
       out.reg_budget = 1 << 20
-  if out.peel is None and out.strategy in ('auto', 'march') and \
+  if out.peel is None and out.strategy in ('auto', 'march', 'tile3d') and \
       lower.march_supported(stencil) is None:
     if not probe or os.environ.get('SODA_HIP_NO_PROBE'):
       out.peel = 0
     else:
+      asked = out
+      if out.strategy == 'tile3d':
+        # its one marching kernel is the one-iteration pass `auto` builds:
+        # probe that one, without compiling the tile3d kernels per trial
+        asked = copy.copy(out)
+        asked.strategy, asked.fuse = 'auto', ()
       try:
-        out.peel = select_peel(stencil, out, extent)
+        out.peel = select_peel(stencil, asked, extent)
       except (util.SodaError, OSError):
         out.peel = 0
   return out
