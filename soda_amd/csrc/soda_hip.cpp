@@ -500,14 +500,19 @@ int kernel_geometry(const soda_hip_kernel_desc_t& d, const int32_t* extent,
                  "strategy", d.name, (long long)plane);
         return fail(SODA_HIP_ERR_INVALID, buf);
       }
-      if (per_wave > limit) {
-        if (d.chunk_fixed) {
+      if (d.chunk_fixed) {
+        // a fixed chunk keeps its length.  The kernels clip a chunk's windows
+        // to the grid (m_end, in_end <= nm): on a grid shorter than the chunk
+        // it is the grid's length that has to fit
+        const int64_t span = per_wave < extent[axis] ? per_wave : extent[axis];
+        if (span > limit) {
           snprintf(buf, sizeof buf,
                    "%s: chunks of %d planes exceed the 1 GiB buffer window on "
                    "this extent (at most %lld)", d.name, per_wave,
                    (long long)limit);
           return fail(SODA_HIP_ERR_INVALID, buf);
         }
+      } else if (per_wave > limit) {
         per_wave = (int32_t)limit;
       }
     }

@@ -860,6 +860,16 @@ def resolve_options(stencil: core.Stencil,
   return out
 
 
+def clipped_box(box, extent: Sequence[int]):
+  """A valid box (lo, hi) as the library takes it: inside the array, hi >= lo.
+  An EMPTY box may come with lo beyond the array -- a program that reaches one
+  way only loses `iterate x reach` cells at one end, more than a small grid
+  has -- or with hi below lo; the library refuses a box outside the array."""
+  lo = [min(max(l, 0), e) for l, e in zip(box[0], extent)]
+  hi = [min(max(h, l), e) for l, h, e in zip(lo, box[1], extent)]
+  return lo, hi
+
+
 class Program:
   """A SODA program JIT-built for gfx950 and loaded on one GPU."""
 
@@ -1116,9 +1126,9 @@ class Program:
     ])
     lo, hi = [], []
     for n in st.output_names:
-      l, h = st.valid_box(extent, n, iterate)
+      l, h = clipped_box(st.valid_box(extent, n, iterate), extent)
       lo.extend(l)
-      hi.extend(max(a, b) for a, b in zip(h, l))
+      hi.extend(h)
     vlo = (ctypes.c_int32 * len(lo))(*lo)
     vhi = (ctypes.c_int32 * len(hi))(*hi)
     check(
@@ -1307,9 +1317,9 @@ class Group:
         for n, t in zip(st.output_names, st.output_types)])
     lo, hi = [], []
     for n in st.output_names:
-      l, h = st.valid_box(self.extent, n, iterate)
+      l, h = clipped_box(st.valid_box(self.extent, n, iterate), self.extent)
       lo.extend(l)
-      hi.extend(max(a, b) for a, b in zip(h, l))
+      hi.extend(h)
     vlo = (ctypes.c_int32 * len(lo))(*lo)
     vhi = (ctypes.c_int32 * len(hi))(*hi)
     check(self._lib.soda_hip_group_store(self._handle, outs, vlo, vhi),

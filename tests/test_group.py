@@ -44,6 +44,10 @@ def _plan(name, extent, fuse, iterate=None, **kw):
     ('heat3d.soda', (512, 512, 80), (2,), 8, 8),
     ('heat3d.soda', (64, 48, 40), (2,), 3, 4),
     ('blur.soda', (2048, 600), (), 1, 2),
+    # tile3d: chunks of a fixed length (`fuse` as a dict: the lowering options)
+    ('heat3d.soda', (64, 48, 600), dict(strategy='tile3d', fuse=(4,)), 8, 8),
+    ('heat3d.soda', (64, 48, 100),
+     dict(strategy='tile3d', fuse=(4,), chunk_rows=16), 8, 8),
 ])
 def test_split_passes_keep_clear_of_the_exchange(built, name, extent, fuse,
                                                  iterate, ghost):
@@ -51,7 +55,12 @@ def test_split_passes_keep_clear_of_the_exchange(built, name, extent, fuse,
   first pass reads no ghost row, an interior chunk of the last pass delivers no
   row a neighbour fetches and writes no ghost row of the result."""
   from soda_amd import runtime
-  stencil, plan = _plan(name, extent, fuse, iterate if iterate > 1 else None)
+  kw = dict(fuse) if isinstance(fuse, dict) else dict(fuse=fuse)
+  stencil, plan = _plan(name, extent, kw.pop('fuse'),
+                        iterate if iterate > 1 else None, **kw)
+  if kw.get('strategy') == 'tile3d':
+    assert any(b'_tile3d_T4_' in plan.kernels[k].name and
+               plan.kernels[k].chunk_fixed for k in range(plan.num_kernels))
   reach_lo, reach_hi = stencil.reach_along(stencil.dim - 1)
   rows = extent[-1]
   seen_split = 0
@@ -80,6 +89,8 @@ def test_split_passes_keep_clear_of_the_exchange(built, name, extent, fuse,
         assert l['bnd_lo'] > 0 or l['bnd_hi'] < l['chunks']
         n = l['hi'] - l['lo']
         assert l['chunks'] == -(-n // l['chunk'])
+        if kw.get('strategy') == 'tile3d':     # the chunk as declared
+          assert l['chunk'] == kw.get('chunk_rows', 128)
         t = l['fused_iters']
         for c in range(l['bnd_lo'], l['bnd_hi']):
           first = l['lo'] + c * l['chunk']
