@@ -73,6 +73,12 @@ def add_arguments(parser) -> None:
                       'kernel over W wavefronts of a block (rows handed on '
                       'through LDS); the fusion depth must be a multiple '
                       '(default 1)')
+  parser.add_argument('--hip-xshare-block', type=int, dest='hip_xshare_block',
+                      default=None, metavar='B', help='fused kernels on blocks '
+                      'of B wavefronts (2..16) side by side on a segment of '
+                      'the row, x-halos shared through LDS inside the block: '
+                      'any row length, none needed at build time (default: '
+                      'not used)')
   parser.add_argument('--hip-nt-store', action='store_true',
                       dest='hip_nt_store',
                       help='non-temporal instead of plain output stores')
@@ -114,7 +120,8 @@ def options_from_args(args: argparse.Namespace) -> lower.LowerOptions:
                             nt_load=False if args.hip_no_nt_load else None,
                             tile_rows=args.hip_tile_rows,
                             xcd_swizzle=not args.hip_no_xcd_swizzle,
-                            pipe=args.hip_pipe)
+                            pipe=args.hip_pipe,
+                            xshare_block=args.hip_xshare_block)
 
 
 def print_code(stencil: core.Stencil, args: argparse.Namespace) -> None:

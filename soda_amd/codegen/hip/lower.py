@@ -141,6 +141,14 @@ class LowerOptions:
   # 2-D; SODA_HIP_XSHARE=0/1 overrides for A/B runs
   xshare: Optional[bool] = None
   row_cells: Optional[int] = None
+  # segmented x-halo sharing (MarchConfig.xshare_block): the fused kernels'
+  # blocks are this many waves (2..16) side by side on a SEGMENT of the row,
+  # x-halos shared through LDS inside it, overlap only between blocks.  Needs
+  # no row length and runs any; wins over xshare / row_cells.  The
+  # one-iteration kernel takes the form only if `xshare` is True as well (as
+  # it shares whole rows only on request).  None: not used (`auto` never
+  # picks it); SODA_HIP_XSHARE_BLOCK=B overrides for A/B runs
+  xshare_block: Optional[int] = None
   # long integer window reductions (erosion's 19-tap min, xcorr's 19-tap
   # sums) as chains of power-of-two windows: 6 instead of 18 operations per
   # cell, bit-exact (optimization/windows.py).  SODA_HIP_WINDOWS=0/1
@@ -166,6 +174,8 @@ class LowerOptions:
       self.windows = os.environ.get('SODA_HIP_WINDOWS', '1') != '0'
     if self.xshare is None and os.environ.get('SODA_HIP_XSHARE'):
       self.xshare = os.environ['SODA_HIP_XSHARE'] == '1'
+    if self.xshare_block is None and os.environ.get('SODA_HIP_XSHARE_BLOCK'):
+      self.xshare_block = int(os.environ['SODA_HIP_XSHARE_BLOCK'])
     if self.align_lanes is None and os.environ.get('SODA_HIP_ALIGN_LANES'):
       self.align_lanes = int(os.environ['SODA_HIP_ALIGN_LANES'])
 
@@ -273,6 +283,9 @@ def lower(stencil: core.Stencil, opts: Optional[LowerOptions] = None) -> Module:
   if opts.lane_shift is not None and opts.lane_shift not in LANE_SHIFTS:
     raise util.SemanticError('lane_shift %r: None or one of %s' %
                              (opts.lane_shift, ', '.join(LANE_SHIFTS)))
+  if opts.xshare_block is not None and not 2 <= opts.xshare_block <= 16:
+    raise util.SemanticError('xshare_block %r: None or 2 to 16 waves per block'
+                             % (opts.xshare_block,))
   _check_native(stencil)
   stencil.check_preserve()
   if opts.strategy == 'tile3d' and tile3d_supported(stencil):
@@ -406,8 +419,9 @@ def lower(stencil: core.Stencil, opts: Optional[LowerOptions] = None) -> Module:
       return default_lane_shift(t, stencil.dim)
 
     def config(t: int, vec: int, pf: Optional[int],
-               rows: Optional[int] = None, xshare: int = 0) -> MarchConfig:
-      shift = shift_for(t, xshare)
+               rows: Optional[int] = None, xshare: int = 0,
+               xshare_block: int = 0) -> MarchConfig:
+      shift = shift_for(t, xshare or xshare_block)
       if pf is None:
         pf = default_prefetch(t, shift)
       if opts.align_lanes is not None:
@@ -423,6 +437,7 @@ def lower(stencil: core.Stencil, opts: Optional[LowerOptions] = None) -> Module:
           min_waves=opts.min_waves, occupancy=opts.occupancy,
           pipe=pipe_for(t), pipe_rows=opts.pipe_rows, stamps=opts.stamps,
           peel=peel_for(t), align_lanes=align, xshare=xshare,
+          xshare_block=xshare_block,
           xwindow=bool(opts.windows),
           slide=bool(opts.windows) and SLIDING_SUMS)
       cfg.chunk_fixed = opts.chunk_rows is not None
@@ -484,12 +499,23 @@ def lower(stencil: core.Stencil, opts: Optional[LowerOptions] = None) -> Module:
         share = -(-opts.row_cells // (64 * vec))
         if share > (4 if opts.xshare is None else 16):
           share = 0
+      # ... or a segment of it, on request (then instead of the whole row)
+      seg = opts.xshare_block or 0
+      if seg:
+        share = 0
       for t in depths:
         keep = (len(mod.kernels), len(mod.passes), len(mod.chunks))
-        for xs in ([share, 0] if share and t > 1 else [0]):
+        # (xshare, xshare_block) to try in turn; overlapping strips last
+        if seg:
+          forms = [(0, seg), (0, 0)]
+        elif share and t > 1:
+          forms = [(share, 0), (0, 0)]
+        else:
+          forms = [(0, 0)]
+        for xs, xb in forms:
           try:
             add_march_pass(mod, config(t, vec, opts.prefetch or None,
-                                       xshare=xs))
+                                       xshare=xs, xshare_block=xb))
             break
           except util.SemanticError:
             # this shape does not fit: try without sharing; if the depth does
@@ -498,10 +524,11 @@ def lower(stencil: core.Stencil, opts: Optional[LowerOptions] = None) -> Module:
                 mod.chunks[keep[2]:]
       # (the one-iteration kernel shares x-halos only on request: measured)
       done1 = False
-      if share and opts.xshare:
+      if (share or seg) and opts.xshare:
         keep = (len(mod.kernels), len(mod.passes), len(mod.chunks))
         try:
-          add_march_pass(mod, config(1, vec, pf1, rows1, xshare=share))
+          add_march_pass(mod, config(1, vec, pf1, rows1, xshare=share,
+                                     xshare_block=seg))
           done1 = True
         except util.SemanticError:
           del mod.kernels[keep[0]:], mod.passes[keep[1]:], mod.chunks[keep[2]:]

@@ -45,6 +45,10 @@ class _Node:
     # x-halo sharing: the strip's neighbours hand this tensor's end cells over
     # through LDS (one register per row slot holds them, like edge loads)
     self.xs = False
+    # segmented x-halo sharing: invalid cells at the two OUTER ends of the
+    # block's segment, the sides no wave of the block hands cells over to
+    # (`margin` then describes the sides between the block's waves)
+    self.omargin = [0, 0]
 
   def tap_bounds(self, pname: str):
     """Bounds of the taps on parent `pname`, the offset-0 tap of a preserved
@@ -100,7 +104,8 @@ class MarchConfig:
                min_waves: int = 0, occupancy: int = 0,
                pipe: int = 1, pipe_rows: int = 4, stamps: bool = False,
                peel: int = -1, align_lanes: int = 1, xshare: int = 0,
-               xwindow: bool = True, slide: bool = True):
+               xwindow: bool = True, slide: bool = True,
+               xshare_block: int = 0):
     # integer window reductions along dimension 0 evaluated for all cells of
     # a lane jointly (_emit_xwindow); integer sums along the streamed
     # dimension as sliding sums
@@ -116,6 +121,16 @@ class MarchConfig:
     # Without it a T = 2 strip of heat3d has 62 valid lanes = 248 cells and a
     # 512-cell row needs THREE waves, the third nearly idle.
     self.xshare = int(xshare)
+    # segmented x-halo sharing: a block of `xshare_block` waves side by side
+    # covers a SEGMENT of the row, S = (64 * xshare_block - lanes_lo -
+    # lanes_hi) * vec cells of it stored.  Between the block's waves the end
+    # cells change hands exactly as above; the segment's two outer sides have
+    # no neighbour in the block, read the cell that stays zero and lose a
+    # fused iteration's x-reach per level, as an overlapping strip does, so
+    # neighbouring blocks overlap by lanes_lo + lanes_hi lanes.  Halo lanes
+    # are lanes_lo + lanes_hi of 64 * xshare_block instead of every 64; any
+    # row length runs, none is needed at build time.  Wins over `xshare`.
+    self.xshare_block = int(xshare_block)
     # valid lanes of a strip rounded down to a multiple of this (extra halo
     # lanes on the high side): 4 makes a strip's rows start and end on 64-byte
     # boundaries.  Pays where rows are written with non-temporal stores -- a
@@ -189,7 +204,9 @@ class MarchConfig:
         '_st' if self.stamps else '',
         '_k%d' % self.peel if self.peel >= 0 else '',
         '_al%d' % self.align_lanes if self.align_lanes > 1 else '',
-        '_xs%d' % self.xshare if self.xshare else ''))
+        '_xs%d' % self.xshare if self.xshare and not self.xshare_block
+        else '',
+        '_xb%d' % self.xshare_block if self.xshare_block else ''))
 
 
 def default_vec(stencil: core.Stencil) -> int:
@@ -221,6 +238,7 @@ def _build_chain(st: core.Stencil, T: int, pf: int, edge: Tuple[int, int],
     n = _Node(('in', name), table[name].c_type, None, -1)
     n.delay = pf
     n.margin = [-edge[0], -edge[1]]    # edge lanes fetch that many halo cells
+    n.omargin = [-edge[0], -edge[1]]
     inputs[name] = n
     nodes.append(n)
   cur_inputs = dict(inputs)
@@ -273,6 +291,9 @@ def _build_chain(st: core.Stencil, T: int, pf: int, edge: Tuple[int, int],
                 'march: x-halo sharing needs a row step between a plane and '
                 'its off-centre taps (%s reads %s)' % (c.var, n.var))
     if reach:
+      # (`margin`: the sides a neighbouring strip of the block serves.  The
+      # outer sides of a segment -- `omargin` -- have no neighbour and may
+      # well be invalid: they are the overlap with the next block)
       if reach > 1 or n.margin[0] > 0 or n.margin[1] > 0:
         raise util.SemanticError(
             'march: x-halo sharing hands over one valid cell per side')
@@ -290,12 +311,16 @@ def _build_chain(st: core.Stencil, T: int, pf: int, edge: Tuple[int, int],
       # MIRROR_PREFETCH ticks after that
       n.delay = src.delay + pipe_rows + MIRROR_PREFETCH
       n.margin = list(src.margin)
+      n.omargin = list(src.omargin)
       n.rmargin = list(src.rmargin)
       continue
     if n.stage is None:
       continue
     delay = None
     margin = [0, 0]
+    # (kept for every chain: without sharing nothing lowers `margin` and the
+    # two are equal; only a segmented kernel reads `omargin`)
+    omargin = [0, 0]
     rmargin = [0, 0]
     for pname, p in n.parents.items():
       tlo, thi = n.tap_bounds(pname)
@@ -303,11 +328,14 @@ def _build_chain(st: core.Stencil, T: int, pf: int, edge: Tuple[int, int],
       delay = d if delay is None else max(delay, d)
       margin[0] = max(margin[0], p.margin[0] + max(0, -tlo[0]))
       margin[1] = max(margin[1], p.margin[1] + max(0, thi[0]))
+      omargin[0] = max(omargin[0], p.omargin[0] + max(0, -tlo[0]))
+      omargin[1] = max(omargin[1], p.omargin[1] + max(0, thi[0]))
       if dim == 3:
         rmargin[0] = max(rmargin[0], p.rmargin[0] + max(0, -tlo[1]))
         rmargin[1] = max(rmargin[1], p.rmargin[1] + max(0, thi[1]))
     n.delay = delay if delay is not None else 0
     n.margin = margin
+    n.omargin = omargin
     n.rmargin = rmargin
     if xshare:
       share(n)
@@ -387,6 +415,14 @@ class _MarchKernel:
     if self.R & (self.R - 1):
       raise util.SemanticError('march: rows per barrier must be a power of two')
     self.xs = self.cfg.xshare
+    # segmented sharing: the block's waves cover a segment, not the row
+    self.seg = bool(self.cfg.xshare_block)
+    if self.seg:
+      if not 2 <= self.cfg.xshare_block <= 16:
+        raise util.SemanticError(
+            'march: xshare_block = %d: 2 to 16 waves share a segment of a row'
+            % self.cfg.xshare_block)
+      self.xs = self.cfg.xshare_block
     if self.xs:
       self.edge = (0, 0)    # the inputs' halo cells travel through LDS as well
       if self.W > 1 or self.cfg.lane_shift != 'dpp' or \
@@ -402,6 +438,9 @@ class _MarchKernel:
     self.out_nodes = list(self.outputs.values())
     self.margin_lo = max(0, max(n.margin[0] for n in self.out_nodes))
     self.margin_hi = max(0, max(n.margin[1] for n in self.out_nodes))
+    if self.seg:     # the halo lanes of a segment are those of its outer sides
+      self.margin_lo = max(0, max(n.omargin[0] for n in self.out_nodes))
+      self.margin_hi = max(0, max(n.omargin[1] for n in self.out_nodes))
     self.lanes_lo = -(-self.margin_lo // self.V)
     self.lanes_hi = -(-self.margin_hi // self.V)
     if self.edge != (0, 0) and not self.xs:
@@ -506,6 +545,12 @@ class _MarchKernel:
     self.group_lanes = self.group - self.lanes_lo - self.lanes_hi
     self.strip_lanes = self.group_lanes * (64 // self.group)
     self.strip_cells = self.strip_lanes * self.V
+    # segmented sharing: cells a block stores, lanes of a block per lane that
+    # stores
+    self.seg_cells = (64 * self.xs - self.lanes_lo - self.lanes_hi) * self.V
+    self.lane_redundancy = 64.0 / self.strip_lanes
+    if self.seg:
+      self.lane_redundancy = 64.0 * self.xs * self.V / self.seg_cells
     self.max_delay = max(n.delay for n in self.out_nodes)
     bounds = self.st.window_bounds(self.T)
     self.m_lo = min(0, min(bounds[o][0][self.ax] for o in self.st.output_names))
@@ -593,6 +638,10 @@ class _MarchKernel:
       'pipeline depth %d' % (self.strip_lanes, self.margin_lo, self.margin_hi,
                              self.edge[0], self.edge[1],
                              self.warm))
+    if self.seg:
+      self.w('// segment: %d waves side by side store %d cells; x-halos shared '
+             'through LDS between them, %d+%d halo lanes at the outer sides' %
+             (self.xs, self.seg_cells, self.lanes_lo, self.lanes_hi))
     if self.dim == 3:
       self.w('// tile: %d rows held in registers for %d output rows (halo %d+%d)' %
         (self.rows_in, self.tile_rows, self.rhalo_lo, self.rhalo_hi))
@@ -642,7 +691,12 @@ class _MarchKernel:
       self.w('  const int y0 = tile_y * %d - %d;  // first row held' %
         (self.tile_rows, self.rhalo_lo))
       self.w('  const int64_t pitch_y = a.stride[1];')
-    if self.group == 64:
+    if self.seg:
+      # wave `strip` of the block's segment: 64 lanes right of its neighbour's
+      self.w('  const int sub = lane;')
+      self.w('  const int x0 = tile_x * %d + (strip * 64 + lane - %d) * %d;' %
+        (self.seg_cells, self.lanes_lo, self.V))
+    elif self.group == 64:
       self.w('  const int sub = lane;')
       self.w('  const int x0 = strip * %d + (lane - %d) * %d;' %
         (self.strip_cells, self.lanes_lo, self.V))
@@ -663,8 +717,14 @@ class _MarchKernel:
       self.w('  if (m_begin >= nm || strip * %d >= n0) return;  // wave-uniform' %
         self.strip_cells)
     self.w('  const bool lane_ok = x0 >= 0 && x0 + %d <= n0;' % self.V)
-    self.w('  const bool store_ok = lane_ok && sub >= %d && sub < %d;' %
-      (self.lanes_lo, self.group - self.lanes_hi))
+    if self.seg:
+      # the halo lanes are the first of the first wave and the last of the last
+      self.w('  const bool store_ok = lane_ok && (strip > 0 || sub >= %d) && '
+             '(strip < %d || sub < %d);' %
+             (self.lanes_lo, self.xs - 1, 64 - self.lanes_hi))
+    else:
+      self.w('  const bool store_ok = lane_ok && sub >= %d && sub < %d;' %
+        (self.lanes_lo, self.group - self.lanes_hi))
     self.w('  const int64_t pitch = a.stride[%d];' % self.ax)
     # (read by nothing: the buffer offsets below address every tensor; the
     # line stays so that the generated kernels keep their exact text)
@@ -1293,6 +1353,8 @@ class _MarchKernel:
     else:
       tile = (self.strip_cells * (self.xs or 1), self.tile_rows,
               self.cfg.chunk_rows)
+    if self.seg:
+      tile = (self.seg_cells,) + tile[1:]
     lds_pad = 0
     if self.cfg.occupancy:
       blocks_per_cu = max(1, 4 * self.cfg.occupancy // self.waves)
@@ -1308,19 +1370,20 @@ class _MarchKernel:
                              pipe=self.W, vec=self.V, step_ops=step_ops,
                              lane_shift=self.cfg.lane_shift,
                              warm_saved=saved,
-                             lane_redundancy=64.0 / self.strip_lanes,
+                             lane_redundancy=self.lane_redundancy,
                              peel_trips=self.peeled // self.U,
                              unroll=self.U, tile_rows=self.tile_rows,
                              peel_trips_max=self.peel_trips_max,
                              fused=self.T,
                              window_extra=self.m_hi - self.m_lo,
                              max_elem=max(self.esz.values()),
-                             max_extent0=self.strip_cells * self.xs)),
+                             max_extent0=0 if self.seg else
+                             self.strip_cells * self.xs)),
         '\n'.join(self.L) + '\n')
     table = self.st.symbol_table
     bytes_in = sum(table[i].size_in_bytes for i in self.st.input_names)
     bytes_out = sum(table[o].size_in_bytes for o in self.st.output_names)
-    redundancy = (64.0 / self.strip_lanes) * (
+    redundancy = self.lane_redundancy * (
         (self.cfg.chunk_rows + self.warm) / float(self.cfg.chunk_rows)) * (
             self.rows_in / float(self.tile_rows))
     p = PassDesc(
