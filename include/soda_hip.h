@@ -52,7 +52,9 @@ extern "C" {
 /* Bumped when a struct that crosses the boundary changes layout (7: the plan
  * carries the program's per-iteration reach).  Entry points added since, under
  * the same number (no struct changed): soda_hip_host_register / _unregister,
- * soda_hip_host_weave_banks, soda_hip_stream_set_device_dense_min_tile; and
+ * soda_hip_host_weave_banks, soda_hip_stream_set_device_dense_min_tile,
+ * soda_hip_stream_set_banked / _set_banked_pair (kargs.reserved[0] carries
+ * the stream length to their programs); and
  * soda_hip_stream_create accepts wire[o] == NULL for an output on one bank
  * that the program stores at its wire position itself. */
 #define SODA_HIP_ABI_VERSION 7
@@ -679,8 +681,45 @@ int soda_hip_stream_run_device(soda_hip_stream_t* stream,
 int soda_hip_stream_run_host(soda_hip_stream_t* stream, void* const* out_banks,
                              const void* const* in_banks,
                              uint64_t coalesced_data_num);
-/* 1: the last run used the dense n-D form, 2: the linear form, 0: none yet */
+/* 1: the last run used the dense n-D form, 2: the linear form, 3: the banked
+ * form of the dense program (soda_hip_stream_set_banked), 0: none yet */
 int soda_hip_stream_last_mode(soda_hip_stream_t* stream);
+/* Opt-in: `program` is the BANKED form of the stream's dense program -- ONE
+ * marching kernel that runs all `iterate` iterations and, for every tensor t
+ * (inputs first, then outputs) with in_kernel[t] != 0, addresses the tensor's
+ * banks itself, each through a buffer resource of its own, (de)interleaving
+ * in registers.  Its plan is a one-pass, one-iteration plan that lists every
+ * bank of such a tensor as a tensor of its own (banks[t] consecutive slots);
+ * every other tensor is one dense array to it.  A tensor may be in_kernel if
+ * it is on 2 or 4 banks, that count divides tile[0] and its shift (inputs:
+ * the kernel starts shift / banks elements into each bank; outputs: shift 0,
+ * born at their wire positions).  soda_hip_stream_run_device then takes this
+ * program whenever the stream has a dense view, the device-dense tile rule
+ * admits it and every bank of every in_kernel tensor is 16-byte aligned: no
+ * unwire_ / wire_ kernel and no staging array for those tensors.  Stream
+ * elements beyond the dense view (the partial last row, the void tail) stay
+ * as the caller left them.  Otherwise the call runs as without it.
+ * soda_hip_stream_run_host is unaffected.  The stream borrows the program;
+ * NULL unsets it. */
+int soda_hip_stream_set_banked(soda_hip_stream_t* stream,
+                               soda_hip_program_t* program,
+                               const int32_t* in_kernel);
+/* Two-iteration programs, after soda_hip_stream_set_banked: `first` is the
+ * ONE-iteration kernel with the in_kernel inputs bank by bank (outputs dense),
+ * `last` the one with the in_kernel outputs bank by bank (inputs dense), plans
+ * as above.  A run on banks takes the launches the dense program's MODEL
+ * schedule names for the stream's extent (soda_hip_stream_set_banked turns the
+ * clock's calibration of the stream's dense program off, so both paths of the
+ * stream are scheduled from one source): one fused launch -> `program`; two
+ * one-iteration launches -> `first`, a dense temporary per output, `last`; any
+ * other schedule, or that one without a pair, keeps the copy pass.  Border
+ * cells no host reads depend on that split; a stream WITHOUT a banked program
+ * whose dense program times its passes may split otherwise and then differs
+ * on those cells only.
+ * NULL, NULL unsets the pair. */
+int soda_hip_stream_set_banked_pair(soda_hip_stream_t* stream,
+                                    soda_hip_program_t* first,
+                                    soda_hip_program_t* last);
 /* soda_hip_stream_run_device takes the dense view only for tiles at least this
  * wide in dimension 0 (default 256: narrower ones leave most of a marching
  * strip idle and the linear form is faster on the GPU; 0: whenever there is a

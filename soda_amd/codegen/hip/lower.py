@@ -165,6 +165,14 @@ class LowerOptions:
   tile3d_w: Optional[int] = None
   tile3d_h: Optional[int] = None
   tile3d_waves: Optional[int] = None
+  # the banked form of a wire stream's dense program (stream.py
+  # `dense_banked`): {input or output: 2 or 4}, the tensor is that many banks
+  # the marching kernels address themselves (MarchConfig.banks), and
+  # {input: elements} the kernels start into the banks of a delayed input.
+  # `march2d` / `march3d` only: a program that lowers to another family, or to
+  # stage-pipelined blocks, is refused with a SemanticError
+  banks: Optional[Dict[str, int]] = None
+  bank_lead: Optional[Dict[str, int]] = None
 
   def __post_init__(self):
     self.fuse = tuple(self.fuse)
@@ -288,6 +296,9 @@ def lower(stencil: core.Stencil, opts: Optional[LowerOptions] = None) -> Module:
                              % (opts.xshare_block,))
   _check_native(stencil)
   stencil.check_preserve()
+  if opts.banks and opts.strategy not in ('auto', 'march'):
+    raise util.SemanticError('banks: `%s` kernels read and write dense arrays'
+                             % opts.strategy)
   if opts.strategy == 'tile3d' and tile3d_supported(stencil):
     raise util.SemanticError('tile3d: %s' % tile3d_supported(stencil))
   # arithmetic per cell of one iteration AS WRITTEN (the rewrites below fold
@@ -327,6 +338,9 @@ def lower(stencil: core.Stencil, opts: Optional[LowerOptions] = None) -> Module:
         (opts.strategy == 'ldswin' and ldswin_supported(whole) is None) or
         (opts.strategy == 'auto' and ldswin_pays(whole) and
          (opts.vec is None or opts.vec % 4 == 0))):
+      if opts.banks:
+        raise util.SemanticError(
+            'banks: `ldswin` kernels read and write dense arrays')
       mod = Module(whole)
       try:
         add_ldswin_pass(mod, chunk=opts.chunk_rows or 64,
@@ -365,7 +379,7 @@ def lower(stencil: core.Stencil, opts: Optional[LowerOptions] = None) -> Module:
   # the same bits (exact.py; the program as written unless one is enabled)
   from soda_amd.codegen.hip import exact
   stencil = exact.specialize(stencil)
-  mod = Module(stencil)
+  mod = Module(stencil, opts.banks)
   use_march = opts.strategy in ('auto', 'march', 'tile3d') and \
       march_supported(stencil) is None
   if opts.strategy == 'march' and not use_march:
@@ -439,7 +453,8 @@ def lower(stencil: core.Stencil, opts: Optional[LowerOptions] = None) -> Module:
           peel=peel_for(t), align_lanes=align, xshare=xshare,
           xshare_block=xshare_block,
           xwindow=bool(opts.windows),
-          slide=bool(opts.windows) and SLIDING_SUMS)
+          slide=bool(opts.windows) and SLIDING_SUMS,
+          banks=opts.banks, bank_lead=opts.bank_lead)
       cfg.chunk_fixed = opts.chunk_rows is not None
       return cfg
 
@@ -471,7 +486,7 @@ def lower(stencil: core.Stencil, opts: Optional[LowerOptions] = None) -> Module:
     for v in vecs:
       for rows in rows_list:
         for pf in pfs:
-          trial = Module(stencil)
+          trial = Module(stencil, opts.banks)
           try:
             est = add_march_pass(trial, config(1, v, pf, rows)).traffic_model[
                 'est_window_regs']
@@ -535,6 +550,9 @@ def lower(stencil: core.Stencil, opts: Optional[LowerOptions] = None) -> Module:
       if not done1:
         add_march_pass(mod, config(1, vec, pf1, rows1))
   if not use_march:
+    if opts.banks:
+      raise util.SemanticError(
+          'banks: `direct` kernels read and write dense arrays')
     add_direct_pass(mod, opts.vec or 1)
   if opts.strategy == 'tile3d':
     # one pass per requested depth, clipped to the iteration count only: the

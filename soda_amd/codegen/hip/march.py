@@ -105,7 +105,20 @@ class MarchConfig:
                pipe: int = 1, pipe_rows: int = 4, stamps: bool = False,
                peel: int = -1, align_lanes: int = 1, xshare: int = 0,
                xwindow: bool = True, slide: bool = True,
-               xshare_block: int = 0):
+               xshare_block: int = 0,
+               banks: Optional[Dict[str, int]] = None,
+               bank_lead: Optional[Dict[str, int]] = None):
+    # the banked form of a wire stream's dense program: {input or output: NB}.
+    # Such a tensor is not one dense array but NB banks, stream element k in
+    # bank k % NB at index k / NB; the kernel addresses every bank through a
+    # resource of its own and (de)interleaves in registers (soda_rt_banked.h,
+    # bank_fragment_map).  The tensor takes NB consecutive a.buf[] slots.
+    # `bank_lead`: {input: elements}, the delay of the reference host that the
+    # kernel undoes by starting lead / NB elements into every bank; dense
+    # element k + lead of such an input is read as zero from
+    # a.reserved[0] (the stream's length) on.
+    self.banks = dict(banks or {})
+    self.bank_lead = {n: int(v) for n, v in (bank_lead or {}).items() if v}
     # integer window reductions along dimension 0 evaluated for all cells of
     # a lane jointly (_emit_xwindow); integer sums along the streamed
     # dimension as sliding sums
@@ -206,13 +219,44 @@ class MarchConfig:
         '_al%d' % self.align_lanes if self.align_lanes > 1 else '',
         '_xs%d' % self.xshare if self.xshare and not self.xshare_block
         else '',
-        '_xb%d' % self.xshare_block if self.xshare_block else ''))
+        '_xb%d' % self.xshare_block if self.xshare_block else '',
+        '_bk_' + '_'.join('%sx%d' % (n, nb) + (
+            'l%d' % self.bank_lead[n] if n in self.bank_lead else '')
+                         for n, nb in sorted(self.banks.items()))
+        if self.banks else ''))
 
 
 def default_vec(stencil: core.Stencil) -> int:
   """16 bytes per lane per row for the widest tensor."""
   widest = max(t.size_in_bytes for t in stencil.symbol_table.values())
   return max(1, 16 // widest)
+
+
+def bank_fragment_map(vec: int, nb: int) -> List[Tuple[int, int]]:
+  """(bank, element of the lane's piece of that bank) of every cell of a
+  fragment of `vec` cells that starts on a bank-group boundary (`nb` divides
+  its first stream element): stream element k is bank k % nb, index k / nb.
+  A restatement, for the record and for the CPU test against numpy's strided
+  views, of what soda_buf_load_frag_banked / _store_frag_banked
+  (csrc/soda_rt_banked.h: `dst[j * NB + b] = part[j]`) do in registers: the
+  generator calls it only to refuse a `vec` that is no whole number of bank
+  groups and emits no code from it, so the helpers themselves are guarded by
+  the GPU cases of tests/test_wire_banked.py, not by this function."""
+  if nb < 1 or vec % nb:
+    raise util.SemanticError(
+        'banks: %d cells per lane are no whole number of groups of %d banks' %
+        (vec, nb))
+  return [(j % nb, j // nb) for j in range(vec)]
+
+
+def edge_cell_banks(i: int, vec: int, nb: int) -> Tuple[int, int]:
+  """Banks of the i-th halo cell left of a strip (cell -1 - i relative to the
+  strip's first) and right of it (cell vec + i relative to the first cell of
+  the strip's LAST lane): strips and lanes start on bank-group boundaries, so
+  both are constants of the kernel."""
+  if nb < 1 or vec % nb:
+    raise util.SemanticError('banks: %d cells per lane, %d banks' % (vec, nb))
+  return (-1 - i) % nb, (vec + i) % nb
 
 
 def march_supported(stencil: core.Stencil) -> Optional[str]:
@@ -412,6 +456,22 @@ class _MarchKernel:
             'of it and one strip per block' % self.W)
       self.edge = (0, 0)
     self.R = self.cfg.pipe_rows if self.W > 1 else 1
+    self.banks = self.cfg.banks
+    for nme, nb in self.banks.items():
+      if self.mod.banks.get(nme) != nb:
+        raise util.InternalError('march: banks of `%s` and the module\'s slots '
+                                 'differ' % nme)
+      if self.W > 1:
+        raise util.SemanticError(
+            'march: stage-pipelined blocks read and write dense arrays')
+      bank_fragment_map(self.V, nb)       # NB | V, or refused
+    for nme in self.cfg.bank_lead:
+      if nme not in self.banks or nme not in self.st.input_names or \
+          self.cfg.bank_lead[nme] % self.banks[nme] or \
+          self.cfg.bank_lead[nme] < 0:
+        raise util.SemanticError(
+            'march: bank_lead of `%s`: a banked input, a multiple of its bank '
+            'count' % nme)
     if self.R & (self.R - 1):
       raise util.SemanticError('march: rows per barrier must be a power of two')
     self.xs = self.cfg.xshare
@@ -642,6 +702,12 @@ class _MarchKernel:
       self.w('// segment: %d waves side by side store %d cells; x-halos shared '
              'through LDS between them, %d+%d halo lanes at the outer sides' %
              (self.xs, self.seg_cells, self.lanes_lo, self.lanes_hi))
+    for nme, nb in sorted(self.banks.items()):
+      self.w('// banked: %s on %d banks (a.buf[%d..%d]), cell j of a fragment = '
+             'element j / %d of bank j %% %d%s' %
+             (nme, nb, self.mod.slot[nme], self.mod.slot[nme] + nb - 1, nb, nb,
+              ', read %d elements on' % self.cfg.bank_lead[nme]
+              if nme in self.cfg.bank_lead else ''))
     if self.dim == 3:
       self.w('// tile: %d rows held in registers for %d output rows (halo %d+%d)' %
         (self.rows_in, self.tile_rows, self.rhalo_lo, self.rhalo_hi))
@@ -754,10 +820,40 @@ class _MarchKernel:
                  '(unsigned)(y0 + %d) * pitch_yb%d : SODA_OOB_X;' %
                  (es, j, j, j, j, es))
     for nme, n in self.inputs.items():
+      if nme in self.banks:
+        # every bank's window: 1 / NB of the dense window, from 1 / NB of its
+        # first element on (NB divides the row pitch and the lead: the library
+        # admits no other stream).  A delayed input ends `lead` elements
+        # early: what lies beyond the stream reads as zero.  The clipped end,
+        # element n - lead, is a fragment boundary (stream.banked_tensors
+        # offers a delayed input only where V divides the lead and the
+        # stream's length n), so no access straddles it: every fragment is
+        # wholly inside the window or wholly dropped, as `unwire_` zeroes
+        nb, lead = self.banks[nme], self.cfg.bank_lead.get(nme, 0)
+        size = '(int64_t)(in_end - wlo) * pitch'
+        if lead:
+          self.w('  const int64_t left_%s = (int64_t)a.reserved[0] - %d - '
+                 '(int64_t)wlo * pitch;  // elements of the stream from wlo on'
+                 % (nme, lead))
+          size = '(%s < left_%s ? %s : left_%s)' % (size, nme, size, nme)
+        for b in range(nb):
+          self.w('  const soda_rsrc_t r_%s_b%d = soda_make_rsrc_bank<%d>((const '
+                 '%s*)a.buf[%d] + ((int64_t)wlo * pitch + %d) / %d, %s * %d);' %
+                 (nme, b, nb, n.ctype, self.mod.slot[nme] + b, lead, nb, size,
+                  self.esz[nme]))
+        continue
       self.w('  const soda_rsrc_t r_%s = soda_make_rsrc((const %s*)a.buf[%d] + '
         '(int64_t)wlo * pitch, (int64_t)(in_end - wlo) * pitch * %d);' %
         (nme, n.ctype, self.mod.slot[nme], self.esz[nme]))
     for o, n in self.outputs.items():
+      if o in self.banks:
+        nb = self.banks[o]
+        for b in range(nb):
+          self.w('  const soda_rsrc_t w_%s_b%d = soda_make_rsrc_bank<%d>((%s*)'
+                 'a.buf[%d] + ((int64_t)m_begin * pitch) / %d, (int64_t)(m_end - '
+                 'm_begin) * pitch * %d);' %
+                 (o, b, nb, n.ctype, self.mod.slot[o] + b, nb, self.esz[o]))
+        continue
       self.w('  const soda_rsrc_t w_%s = soda_make_rsrc((%s*)a.buf[%d] + '
         '(int64_t)m_begin * pitch, (int64_t)(m_end - m_begin) * pitch * %d);' %
         (o, n.ctype, self.mod.slot[o], self.esz[o]))
@@ -901,6 +997,24 @@ class _MarchKernel:
           es = self.esz[nme]
           ro = 'ro%d' % es if self.dim == 2 else 'ro%d_%d' % (es, j)
           reg = '%s_s%d_r%d' % (n.var, s, j)
+          if nme in self.banks:
+            nb = self.banks[nme]
+            self.w('      soda_buf_load_frag_banked<%s, %d, %d, %s>(%s, %s + '
+                   'xb%d%s, %s);' %
+                   (n.ctype, self.V, nb, self.nt_l, reg, ro, es, pinned,
+                    ', '.join('r_%s_b%d' % (nme, b) for b in range(nb))))
+            for i in range(self.n_edge):
+              # lane 0's cell and lane 63's lie in different banks as a rule:
+              # one load each, the other lanes' offsets out of range
+              left, right = edge_cell_banks(i, self.V, nb)
+              self.w('      { %s e1[1], e2[1]; soda_buf_load_cell_banked<%s, %d>('
+                     'e1, r_%s_b%d, lane == 0 ? %s + exb%d_%d : SODA_OOB_X); '
+                     'soda_buf_load_cell_banked<%s, %d>(e2, r_%s_b%d, lane == 0 '
+                     '? SODA_OOB_X : %s + exb%d_%d); %s_e[%d] = lane == 0 ? '
+                     'e1[0] : e2[0]; }' %
+                     (n.ctype, n.ctype, nb, nme, left, ro, i, es,
+                      n.ctype, nb, nme, right, ro, i, es, reg, i))
+            continue
           self.w('      soda_buf_load_frag<%s, %d, %s>(%s, r_%s, %s + xb%d%s);' %
             (n.ctype, self.V, self.nt_l, reg, nme, ro, es, pinned))
           for i in range(self.n_edge):
@@ -1312,6 +1426,16 @@ class _MarchKernel:
     self.w('        const bool m_ok = m >= m_begin && m < m_end;')
     for j in self.store_rows(n):
       reg = '%s_s%d_r%d' % (n.var, dst_slot, j)
+      if oname in self.banks:
+        nb = self.banks[oname]
+        off = ('(m_ok ? (unsigned)(m - m_begin) * pitch_b%d : SODA_OOB_X) + '
+               'yo%d_%d + sxb%d' % (es, es, j, es)) if self.dim == 3 else (
+                   '(m_ok ? (unsigned)(m - m_begin) * pitch_b%d : SODA_OOB_ROW) '
+                   '+ sxb%d' % (es, es))
+        self.w('        soda_buf_store_frag_banked<%s, %d, %d, %s>(%s, %s, %s);' %
+               (n.ctype, self.V, nb, self.nt_s, off, reg,
+                ', '.join('w_%s_b%d' % (oname, b) for b in range(nb))))
+        continue
       if self.dim == 3:
         self.w('        soda_buf_store_frag<%s, %d, %s>(w_%s, (m_ok ? (unsigned)'
           '(m - m_begin) * pitch_b%d : SODA_OOB_X) + yo%d_%d + sxb%d, %s);' %

@@ -964,6 +964,14 @@ int run_core(soda_hip_program_t* p, void* const* outputs,
   }
 
   if (p->debug) base.buf[SODA_HIP_MAX_TENSORS - 1] = p->debug;
+  // the banked form of a wire stream's program: the stream's length, beyond
+  // which a delayed input reads as zero (0 for every other program).  Such a
+  // program's plan is not truthful in two fields, which is why it only ever
+  // comes here with iterate = 1 and no slab: its one pass says fused_iters = 1
+  // for a kernel that runs all of the stream's iterations, and num_locals = 0
+  // (the marching kernel holds them in registers; its a.buf[] slots end with
+  // the output banks) -- stream.py `banked_spec`
+  base.reserved[0] = p->stream_elems;
   const int in0 = 0, out0 = plan.num_inputs, loc0 = out0 + plan.num_outputs;
   const int prm0 = loc0 + plan.num_locals;
   for (int k = 0; k < plan.num_params; ++k)   // the same in every iteration
@@ -1378,6 +1386,25 @@ struct soda_hip_stream {
   // take the dense view whenever there is one -- there the copies dominate and
   // the dense view is what lets them overlap in bands.
   int device_dense_min_tile0 = 256;
+  // The banked form of the dense program (soda_hip_stream_set_banked): one
+  // kernel that runs all `iterate` iterations and addresses the banks of the
+  // tensors marked in `in_kernel` itself -- to run_core a one-pass program of
+  // one iteration with every such bank a tensor of its own.  So it meets
+  // neither of run_core's one-shape-per-tensor assumptions: a stream run has
+  // no slab, hence no row-range offset, and iterate is 1 there.
+  soda_hip_program* banked = nullptr;
+  std::vector<int32_t> in_kernel;     // per tensor, inputs first
+  // Two-iteration programs (soda_hip_stream_set_banked_pair): the
+  // one-iteration kernel with the in_kernel INPUTS bank by bank, and with the
+  // in_kernel OUTPUTS bank by bank.  Where the dense program's schedule for
+  // the stream's extent is two one-iteration launches, these two run instead
+  // of `banked`, a dense temporary per output between them: the banked path
+  // then computes every cell of the dense view -- the array's border cells
+  // included, which a fused kernel and two launches do not agree on -- as the
+  // dense program does.
+  soda_hip_program* banked_first = nullptr;
+  soda_hip_program* banked_last = nullptr;
+  std::vector<DeviceBuffer> banked_tmp;
 };
 
 int soda_hip_stream_create(const soda_hip_stream_desc_t* desc,
@@ -1433,7 +1460,7 @@ int soda_hip_stream_create(const soda_hip_stream_desc_t* desc,
 
 int soda_hip_stream_destroy(soda_hip_stream_t* s) {
   if (!s) return SODA_HIP_OK;
-  for (auto* v : {&s->dense_in, &s->dense_out, &s->host_banks})
+  for (auto* v : {&s->dense_in, &s->dense_out, &s->host_banks, &s->banked_tmp})
     for (auto& b : *v)
       if (b.ptr) (void)hipFree(b.ptr);
   delete s;
@@ -1447,6 +1474,92 @@ int soda_hip_stream_set_device_dense_min_tile(soda_hip_stream_t* s,
   if (!s || min_tile0 < 0)
     return fail(SODA_HIP_ERR_INVALID, "stream_set_device_dense_min_tile");
   s->device_dense_min_tile0 = min_tile0;
+  return SODA_HIP_OK;
+}
+
+int soda_hip_stream_set_banked(soda_hip_stream_t* s, soda_hip_program_t* program,
+                               const int32_t* in_kernel) {
+  if (!s) return fail(SODA_HIP_ERR_INVALID, "stream_set_banked: NULL stream");
+  if (!program) {
+    s->banked = s->banked_first = s->banked_last = nullptr;
+    s->in_kernel.clear();
+    if (s->dense) s->dense->auto_calibrate = !getenv("SODA_HIP_NO_CALIBRATE");
+    return SODA_HIP_OK;
+  }
+  if (!in_kernel)
+    return fail(SODA_HIP_ERR_INVALID, "stream_set_banked: NULL mask");
+  const soda_hip_stream_desc_t& d = s->desc;
+  const soda_hip_plan_t& plan = program->plan;
+  int ins = 0, outs = 0;
+  bool any = false;
+  for (int t = 0; t < d.num_inputs + d.num_outputs; ++t) {
+    const bool input = t < d.num_inputs;
+    const int nb = d.banks[t];
+    if (in_kernel[t]) {
+      // fragments start on bank-group boundaries only if NB divides the tile
+      // row; a delay is undone by starting shift / NB elements into each bank
+      if ((nb != 2 && nb != 4) || d.tile[0] % nb || d.shift[t] % nb ||
+          (!input && d.shift[t]))
+        return fail(SODA_HIP_ERR_INVALID,
+                    "stream_set_banked: a tensor the program cannot address "
+                    "bank by bank");
+      any = true;
+    } else if (!input && !s->wire[t - d.num_inputs] && nb != 1) {
+      return fail(SODA_HIP_ERR_INVALID, "stream_set_banked: missing wire kernel");
+    }
+    (input ? ins : outs) += in_kernel[t] ? nb : 1;
+  }
+  if (!any || d.dim < 2 || plan.dim != d.dim || plan.num_inputs != ins ||
+      plan.num_outputs != outs || plan.num_passes != 1 ||
+      plan.passes[0].num_kernels != 1 ||
+      plan.kernels[plan.passes[0].kernel[0]].march_dim != plan.dim ||
+      ins + outs >= SODA_HIP_MAX_TENSORS)
+    return fail(SODA_HIP_ERR_INVALID,
+                "stream_set_banked: not the one-launch banked form of this "
+                "stream's program");
+  s->banked = program;
+  s->banked_first = s->banked_last = nullptr;
+  s->in_kernel.assign(in_kernel, in_kernel + d.num_inputs + d.num_outputs);
+  // one source for both paths of this stream: which launches a run takes is
+  // asked of the dense program's MODEL schedule (banked_launches), so the
+  // copy path of the same stream must not re-schedule from the clock
+  if (s->dense) s->dense->auto_calibrate = false;
+  return SODA_HIP_OK;
+}
+
+int soda_hip_stream_set_banked_pair(soda_hip_stream_t* s,
+                                    soda_hip_program_t* first,
+                                    soda_hip_program_t* last) {
+  if (!s || !s->banked)
+    return fail(SODA_HIP_ERR_INVALID,
+                "stream_set_banked_pair: no banked program is set");
+  if (!first && !last) {
+    s->banked_first = s->banked_last = nullptr;
+    return SODA_HIP_OK;
+  }
+  const soda_hip_stream_desc_t& d = s->desc;
+  const soda_hip_plan_t& whole = s->banked->plan;
+  auto one_kernel = [&](const soda_hip_plan_t& plan) {
+    return plan.dim == d.dim && plan.num_passes == 1 &&
+           plan.passes[0].num_kernels == 1 &&
+           plan.kernels[plan.passes[0].kernel[0]].march_dim == plan.dim;
+  };
+  if (d.iterate != 2 || d.num_inputs != d.num_outputs || !first || !last ||
+      !one_kernel(first->plan) || !one_kernel(last->plan) ||
+      first->plan.num_inputs != whole.num_inputs ||
+      first->plan.num_outputs != d.num_outputs ||
+      last->plan.num_inputs != d.num_inputs ||
+      last->plan.num_outputs != whole.num_outputs)
+    return fail(SODA_HIP_ERR_INVALID,
+                "stream_set_banked_pair: not the two one-iteration launches of "
+                "this stream's two-iteration program");
+  for (int o = 0; o < d.num_outputs; ++o)
+    if (d.elem_size[o] != d.elem_size[d.num_inputs + o])
+      return fail(SODA_HIP_ERR_INVALID,
+                  "stream_set_banked_pair: input and output cell sizes differ");
+  s->banked_first = first;
+  s->banked_last = last;
+  s->banked_tmp.resize(d.num_outputs);
   return SODA_HIP_OK;
 }
 
@@ -1470,6 +1583,69 @@ static bool dense_view(const soda_hip_stream* s, int64_t n, int32_t* ext) {
   return true;
 }
 
+// Does this call run the banked form of the dense program?  Every reason not
+// to is found HERE, before anything is launched: no dense view, a tile the
+// device-dense rule keeps on the linear form, a bank of an in_kernel tensor
+// that is not 16-byte aligned, an extent the kernels refuse, a schedule of the
+// dense program that the banked programs do not cover.  *launches: 0 = no (the
+// call runs as without a banked program), 1 = `banked`, 2 = `banked_first`
+// then `banked_last`.
+//
+// The schedule is the MODEL's (soda_hip_stream_set_banked turns the clock's
+// calibration of the stream's dense program off, so the copy path of the same
+// stream is scheduled from the same source): the one fused launch, or -- two
+// iterations -- two launches of the one-iteration kernel.
+static int banked_launches(soda_hip_stream* s, void* const* out_banks,
+                           const void* const* in_banks, int32_t n, int32_t* ext,
+                           int* launches) {
+  const soda_hip_stream_desc_t& d = s->desc;
+  *launches = 0;
+  if (!s->banked || d.tile[0] < s->device_dense_min_tile0 ||
+      !dense_view(s, n, ext))
+    return SODA_HIP_OK;
+  int want = 1;
+  if (d.iterate > 1) {
+    if (!s->dense) return SODA_HIP_OK;
+    int32_t count[SODA_HIP_MAX_PASSES];
+    const int rc = soda_hip_program_schedule(s->dense, ext, d.iterate, count);
+    if (rc == SODA_HIP_ERR_INVALID) return SODA_HIP_OK;   // no dense run either
+    if (rc) return rc;
+    const soda_hip_plan_t& dp = s->dense->plan;
+    int total = 0, deepest = 0;
+    for (int i = 0; i < dp.num_passes; ++i) {
+      total += count[i];
+      if (count[i] && !deepest) deepest = dp.passes[i].fused_iters;
+    }
+    if (total == 1 && deepest == d.iterate)
+      want = 1;
+    else if (total == 2 && deepest == 1 && s->banked_first && s->banked_last)
+      want = 2;
+    else
+      return SODA_HIP_OK;
+  }
+  for (soda_hip_program* p : {want == 1 ? s->banked : s->banked_first,
+                              want == 1 ? s->banked : s->banked_last}) {
+    const int rc = plan_geometry_c(&p->plan, ext, nullptr, nullptr);
+    if (rc == SODA_HIP_ERR_INVALID) return SODA_HIP_OK;
+    if (rc) return rc;
+  }
+  int bank0 = 0;
+  for (int i = 0; i < d.num_inputs; bank0 += d.banks[i], ++i)
+    for (int b = 0; s->in_kernel[i] && b < d.banks[i]; ++b)
+      if (!in_banks[bank0 + b] ||
+          (reinterpret_cast<uintptr_t>(in_banks[bank0 + b]) & 15))
+        return SODA_HIP_OK;      // (a NULL bank: the path below says so)
+  bank0 = 0;
+  for (int o = 0; o < d.num_outputs; bank0 += d.banks[d.num_inputs + o], ++o)
+    for (int b = 0; s->in_kernel[d.num_inputs + o] &&
+                    b < d.banks[d.num_inputs + o]; ++b)
+      if (!out_banks[bank0 + b] ||
+          (reinterpret_cast<uintptr_t>(out_banks[bank0 + b]) & 15))
+        return SODA_HIP_OK;
+  *launches = want;
+  return SODA_HIP_OK;
+}
+
 int soda_hip_stream_run_device(soda_hip_stream_t* s, void* const* out_banks,
                                const void* const* in_banks,
                                uint64_t coalesced_data_num, void* hip_stream) {
@@ -1482,42 +1658,59 @@ int soda_hip_stream_run_device(soda_hip_stream_t* s, void* const* out_banks,
   const int32_t n = (int32_t)n64;
   const int32_t ext1[1] = {n};
   HIP_TRY(hipSetDevice(s->linear.back()->device));
+  // the banked form of the dense program: the tensors marked in_kernel go to
+  // it bank by bank -- no copy kernel, no staging array -- every other tensor
+  // as always (`kern` stays NULL where the call does not take the form)
+  int32_t bext[SODA_HIP_MAX_DIM];
+  int banked = 0;
+  if (s->banked)
+    if (int rc = banked_launches(s, out_banks, in_banks, n, bext, &banked))
+      return rc;
+  const int32_t* kern = banked ? s->in_kernel.data() : nullptr;
   // 1. un-interleave (and un-delay) the inputs
-  std::vector<const void*> din(d.num_inputs);
+  std::vector<const void*> din;     // one entry per tensor, NB per in_kernel one
   int bank0 = 0;
   for (int i = 0; i < d.num_inputs; ++i) {
     const int nb = d.banks[i];
     for (int b = 0; b < nb; ++b)
       if (!in_banks[bank0 + b])
         return fail(SODA_HIP_ERR_INVALID, "stream_run: NULL input bank");
-    if (nb == 1 && d.shift[i] == 0) {
+    if (kern && kern[i]) {
+      din.insert(din.end(), in_banks + bank0, in_banks + bank0 + nb);
+    } else if (nb == 1 && d.shift[i] == 0) {
       if (reinterpret_cast<uintptr_t>(in_banks[bank0]) & 15)
         return fail(SODA_HIP_ERR_INVALID,
                     "stream_run: a bank the program reads in place must be "
                     "16-byte aligned");
-      din[i] = in_banks[bank0];     // the bank IS the dense stream
+      din.push_back(in_banks[bank0]);     // the bank IS the dense stream
     } else {
       if (int rc = ensure(s->dense_in[i], (size_t)n * d.elem_size[i])) return rc;
       void* outs[1] = {s->dense_in[i].ptr};
       if (int rc = soda_hip_run_device(s->unwire[i], outs, in_banks + bank0, ext1,
                                        1, hip_stream))
         return rc;
-      din[i] = s->dense_in[i].ptr;
+      din.push_back(s->dense_in[i].ptr);
     }
     bank0 += nb;
   }
-  std::vector<void*> dout(d.num_outputs);
+  std::vector<void*> dout;          // likewise
+  std::vector<void*> staged(d.num_outputs, nullptr);   // what wire_<o> reads
   bank0 = 0;
   for (int o = 0; o < d.num_outputs; bank0 += d.banks[d.num_inputs + o], ++o) {
-    for (int b = 0; b < d.banks[d.num_inputs + o]; ++b)
+    const int nb = d.banks[d.num_inputs + o];
+    for (int b = 0; b < nb; ++b)
       if (!out_banks[bank0 + b])
         return fail(SODA_HIP_ERR_INVALID, "stream_run: NULL output bank");
+    if (kern && kern[d.num_inputs + o]) {
+      dout.insert(dout.end(), out_banks + bank0, out_banks + bank0 + nb);
+      continue;
+    }
     if (!s->wire[o]) {
       if (reinterpret_cast<uintptr_t>(out_banks[bank0]) & 15)
         return fail(SODA_HIP_ERR_INVALID,
                     "stream_run: a bank the program writes in place must be "
                     "16-byte aligned");
-      dout[o] = out_banks[bank0];   // born at its wire position, in place
+      dout.push_back(out_banks[bank0]);   // born at its wire position, in place
       continue;
     }
     const size_t bytes = (size_t)n * d.elem_size[d.num_inputs + o];
@@ -1528,11 +1721,39 @@ int soda_hip_stream_run_device(soda_hip_stream_t* s, void* const* out_banks,
     if (s->dense_out[o].ptr != before)
       HIP_TRY(hipMemsetAsync(s->dense_out[o].ptr, 0, s->dense_out[o].bytes,
                              static_cast<hipStream_t>(hip_stream)));
-    dout[o] = s->dense_out[o].ptr;
+    dout.push_back(s->dense_out[o].ptr);
+    staged[o] = s->dense_out[o].ptr;
   }
   // 2. the program, on the dense view where there is one
   bool done = false;
-  {
+  if (banked == 2) {
+    // two one-iteration launches, a dense temporary per output between them
+    std::vector<void*> tmp(d.num_outputs);
+    for (int o = 0; o < d.num_outputs; ++o) {
+      if (int rc = ensure(s->banked_tmp[o],
+                          (size_t)n * d.elem_size[d.num_inputs + o]))
+        return rc;
+      tmp[o] = s->banked_tmp[o].ptr;
+    }
+    s->banked_first->stream_elems = n;
+    if (int rc = soda_hip_run_device(s->banked_first, tmp.data(), din.data(),
+                                     bext, 1, hip_stream))
+      return rc;
+    std::vector<const void*> from(tmp.begin(), tmp.end());
+    s->banked_last->stream_elems = n;
+    if (int rc = soda_hip_run_device(s->banked_last, dout.data(), from.data(),
+                                     bext, 1, hip_stream))
+      return rc;
+    done = true;
+    s->last_mode = 3;
+  } else if (banked == 1) {
+    s->banked->stream_elems = n;
+    if (int rc = soda_hip_run_device(s->banked, dout.data(), din.data(), bext, 1,
+                                     hip_stream))
+      return rc;
+    done = true;
+    s->last_mode = 3;
+  } else {
     int32_t ext[SODA_HIP_MAX_DIM];
     if (d.tile[0] >= s->device_dense_min_tile0 && dense_view(s, n, ext)) {
       int rc = soda_hip_run_device(s->dense, dout.data(), din.data(), ext,
@@ -1557,8 +1778,8 @@ int soda_hip_stream_run_device(soda_hip_stream_t* s, void* const* out_banks,
   // 3. outputs: shifted by the stencil offset, re-interleaved
   bank0 = 0;
   for (int o = 0; o < d.num_outputs; bank0 += d.banks[d.num_inputs + o], ++o) {
-    if (!s->wire[o]) continue;
-    const void* ins[1] = {dout[o]};
+    if (!staged[o]) continue;
+    const void* ins[1] = {staged[o]};
     if (int rc = soda_hip_run_device(s->wire[o], out_banks + bank0, ins, ext1, 1,
                                      hip_stream))
       return rc;

@@ -106,6 +106,9 @@ struct soda_hip_program {
   int32_t last_split = 0;    // passes of the last run launched in two parts
   int64_t last_rows = 0;     // cells along the last dimension, summed over passes
   void* debug = nullptr;     // time-stamp buffer of diagnostic builds
+  // kargs.reserved[0] of every launch: the length of the wire stream a banked
+  // program runs on (soda_hip_stream_set_banked), 0 for every other program
+  int32_t stream_elems = 0;
   // time every pass on an extent the first time it is run (a few ms, once):
   // on unless SODA_HIP_NO_CALIBRATE is set or the caller turns it off
   bool auto_calibrate = true;

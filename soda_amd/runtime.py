@@ -271,6 +271,8 @@ API = {
                                                 ctypes.c_uint64]),
     'soda_hip_stream_last_mode': (ctypes.c_int, [_vp]),
     'soda_hip_stream_set_device_dense_min_tile': (ctypes.c_int, [_vp, _i32]),
+    'soda_hip_stream_set_banked': (ctypes.c_int, [_vp, _vp, _pi32]),
+    'soda_hip_stream_set_banked_pair': (ctypes.c_int, [_vp, _vp, _vp]),
     'soda_hip_malloc': (ctypes.c_int, [_i32, ctypes.c_size_t, _pvp]),
     'soda_hip_free': (ctypes.c_int, [_i32, _vp]),
     'soda_hip_memcpy_h2d': (ctypes.c_int, [_vp, _vp, ctypes.c_size_t, _vp]),
@@ -441,8 +443,11 @@ def make_plan(mod: lower.Module,
   plan = Plan()
   plan.abi_version = ABI_VERSION
   plan.dim = st.dim
-  plan.num_inputs = len(st.input_names)
-  plan.num_outputs = len(st.output_names)
+  # (a tensor the kernels address bank by bank -- Module.banks -- is as many
+  # tensors to the library, which only passes pointers on)
+  banks = getattr(mod, 'banks', None) or {}
+  plan.num_inputs = sum(banks.get(n, 1) for n in st.input_names)
+  plan.num_outputs = sum(banks.get(n, 1) for n in st.output_names)
   plan.num_locals = len(st.local_names)
   if len(st.param_stmts) > MAX_PARAMS:
     raise util.SemanticError('more than %d param arrays' % MAX_PARAMS)

@@ -297,6 +297,8 @@ class ProgramSpec:
                kernel_names: Sequence[str]):
     self.tag, self.source, self.plan = tag, source, plan
     self.kernel_names = list(kernel_names)
+    # `dense_banked` only: {tensor: banks} the kernel addresses itself
+    self.in_kernel: Dict[str, int] = {}
 
 
 def _copy_plan(name: str, n_in: int, n_out: int, elem: int,
@@ -332,12 +334,51 @@ def input_shifts(stencil: core.Stencil) -> Dict[str, int]:
   return stencil.produce_offsets()
 
 
+BANKED_COUNTS = (2, 4)     # banks per tensor the marching kernels address
+
+
+def banked_tensors(stencil: core.Stencil, vec: int, late: bool,
+                   shifts: Dict[str, int]) -> Dict[str, int]:
+  """{tensor: banks} of the tensors the banked form of the dense program
+  addresses itself, decided one by one.  Every fragment of a marching kernel
+  starts at a multiple of its `vec` cells per lane from the start of a tile
+  row (strips, segments and half strips all do: march.py `x0`), and rows
+  start at multiples of tile[0] in the stream; so a fragment covers whole
+  bank groups iff NB divides both.  An input's delay becomes a start
+  `shift / NB` elements into every bank and a window that ends `shift`
+  elements early (what lies beyond the stream reads as zero).  Both must fall
+  on FRAGMENT boundaries -- `vec` divides the shift and the stream's length,
+  which is a multiple of the tensor's elements per cycle -- so that every
+  bank access stays naturally aligned and none straddles the window's end (a
+  buffer access that does is not dropped cell by cell, whereas `unwire_`
+  zeroes exactly from element n - shift on).  An output must be born at its
+  wire position (`late`), since nothing is left to shift it afterwards."""
+  table = stencil.symbol_table
+  picked = {}
+  for s in stencil.input_stmts + stencil.output_stmts:
+    nb = len(s.dram)
+    if nb not in BANKED_COUNTS or vec % nb or stencil.tile_size[0] % nb:
+      continue
+    if s in stencil.input_stmts:
+      shift = shifts.get(s.name, 0)
+      epc = stencil.burst_width // table[s.name].width_in_bits * nb
+      if shift and (shift % vec or epc % vec):
+        continue
+    elif not late:
+      continue
+    picked[s.name] = nb
+  return picked
+
+
 def stream_specs(stencil: core.Stencil, dense: Optional[bool] = None,
-                 direct: bool = True):
+                 direct: bool = True, banked: bool = False):
   """(StreamDesc, {tag: ProgramSpec}) of `<app>_kernel` for `stencil`.  Tags:
   `dense` (optional), `linear<V>`, `unwire_<input>`, `wire_<output>` (absent
   for an output the program writes in place).  `direct=False`: every output
-  through the shift + copy pass, as before round 5."""
+  through the shift + copy pass, as before round 5.  `banked=True`: also
+  `dense_banked`, the dense program as ONE marching kernel that addresses the
+  banks of the tensors `ProgramSpec.in_kernel` names itself -- where there is
+  such a kernel and such a tensor (banked_tensors), else no such tag."""
   if stencil.param_stmts:
     raise util.SemanticError('stream mode does not support param tensors')
   if stencil.preserve_border:
@@ -377,6 +418,83 @@ def stream_specs(stencil: core.Stencil, dense: Optional[bool] = None,
         runtime.compile_source(mod.source, '%s.hip' % sten.app_name))
     specs[tag] = ProgramSpec(tag, mod.source, runtime.make_plan(mod, res),
                              [k.name for k in mod.kernels])
+    return mod, opts
+
+  def banked_spec(dense_mod, dense_opts):
+    # the whole `iterate` as ONE launch: the marching kernel of exactly that
+    # depth, if the dense program has one (programs of more launches ping-pong
+    # through dense temporaries and keep the copy pass; two one-iteration
+    # launches of a two-iteration program are covered below)
+    import copy
+    from soda_amd.codegen.hip.module import PassDesc
+    kinds = ('march2d', 'march3d')
+    one = [p for p in dense_mod.passes
+           if p.fused_iters == st.iterate and p.kind in kinds and
+           len(p.kernels) == 1]
+    if not one:
+      return
+    tune = dense_mod.kernels[one[0].kernels[0]].tune or {}
+    if int(tune.get('pipe') or 1) != 1:
+      return
+    vec = int(tune['vec'])
+    picked = banked_tensors(st, vec, late is not None, shifts)
+    if not picked:
+      return
+    leads = {n: shifts[n] for n in st.input_names
+             if n in picked and shifts.get(n)}
+
+    def launch(tag, depth, banks, lead):
+      # the dense kernel of that depth in its own shape (cells per lane,
+      # prefetch, peel) with `banks` addressed bank by bank
+      opts = copy.copy(dense_opts)
+      opts.fuse = (depth,) if depth > 1 else ()
+      opts.banks, opts.bank_lead = banks, lead
+      mod = lower.lower(run, opts)
+      one = [p for p in mod.passes
+             if p.fused_iters == depth and p.kind in kinds and
+             len(p.kernels) == 1]
+      if not one or int(mod.kernels[one[0].kernels[0]].tune['vec']) != vec \
+          or int(mod.kernels[one[0].kernels[0]].tune.get('pipe') or 1) != 1:
+        return False
+      k = one[0].kernels[0]
+      # to the library a one-pass program of ONE iteration (the kernel runs
+      # `depth` of them) with every bank of a picked tensor a tensor of its own
+      mod.kernels, mod.chunks = [mod.kernels[k]], [mod.chunks[k]]
+      mod.passes = [PassDesc(1, [0], one[0].kind, one[0].traffic_model)]
+      res = runtime.kernel_resources(
+          runtime.compile_source(mod.source, '%s_banked.hip' % run.app_name))
+      plan = runtime.make_plan(mod, res)
+      # (two fields of this plan are not truthful, see run_core in
+      # soda_hip.cpp: fused_iters = 1 above for a kernel that runs `depth`
+      # iterations, and no locals -- the kernel holds them in registers and
+      # its a.buf[] slots end with the output tensors)
+      plan.num_locals = 0
+      spec = ProgramSpec(tag, mod.source, plan,
+                         [mod.kernels[0].name])
+      spec.in_kernel = dict(banks)
+      specs[tag] = spec
+      return True
+
+    if not launch('dense_banked', st.iterate, picked, leads):
+      return
+    # Two iterations: the dense program may also run them as two launches of
+    # its one-iteration kernel (where that is what its schedule says, the
+    # library does the same: the first launch reads the banks, the second
+    # writes them, one dense temporary per output in between -- the same
+    # arithmetic on every cell, the array's border cells included)
+    ins = {n: b for n, b in picked.items() if n in st.input_names}
+    outs = {n: b for n, b in picked.items() if n in st.output_names}
+    if st.iterate == 2 and any(p.fused_iters == 1 and p.kind in kinds
+                               for p in dense_mod.passes):
+      try:
+        ok = bool(ins) and bool(outs) and \
+            launch('dense_banked_first', 1, ins, leads) and \
+            launch('dense_banked_last', 1, outs, {})
+      except util.SodaError:
+        ok = False
+      if not ok:
+        specs.pop('dense_banked_first', None)
+        specs.pop('dense_banked_last', None)
 
   # the linearised 1-D program, widest vector first, always ending in 1
   vecs = []
@@ -402,10 +520,16 @@ def stream_specs(stencil: core.Stencil, dense: Optional[bool] = None,
     try:
       # (iterated programs: the depths the n-D entry offers; lower() clips
       # them to `iterate`, the library mixes them per stream length)
-      program_spec('dense', run, lower.LowerOptions(fuse=lower.DEFAULT_FUSE),
-                   tuple(st.tile_size[:-1]) + (1 << 20,))
+      built = program_spec('dense', run,
+                           lower.LowerOptions(fuse=lower.DEFAULT_FUSE),
+                           tuple(st.tile_size[:-1]) + (1 << 20,))
     except util.SodaError:
-      pass
+      built = None
+    if banked and built:
+      try:
+        banked_spec(*built)
+      except util.SodaError:
+        pass
   chunks = [lower.runtime_text()]
   copies = []
   for s_ in st.input_stmts:
@@ -460,14 +584,19 @@ class StreamProgram:
   DENSE_MIN_TILE0 = 256
 
   def __init__(self, stencil: core.Stencil, device: int = 0,
-               dense: Optional[bool] = None, direct: bool = True):
+               dense: Optional[bool] = None, direct: bool = True,
+               banked: bool = False):
     """`dense`: None = use the n-D marching kernels when the stream allows it
     and -- for device-resident banks -- the tile is wide enough to fill them
     (host banks: whenever the stream allows it), True = whenever the stream
-    allows it, False = always the linear form.  `direct`: see stream_specs."""
+    allows it, False = always the linear form.  `direct`: see stream_specs.
+    `banked`: run_banked_device takes the dense program's banked form where
+    the program has one (stream_specs) and the call allows it -- the marching
+    kernel reads and writes 2 or 4 device-resident banks of a tensor itself,
+    no copy kernel, no staging array; `last_mode` is then 'banked'."""
     self.stencil = stencil
     self.device = device
-    self.desc, self.specs = stream_specs(stencil, dense, direct)
+    self.desc, self.specs = stream_specs(stencil, dense, direct, banked)
     self.banks = {s.name: len(s.dram)
                   for s in stencil.input_stmts + stencil.output_stmts}
     self.stencil_offset = stencil_offsets(stencil)   # a program constant
@@ -502,10 +631,25 @@ class StreamProgram:
         lib.soda_hip_stream_set_device_dense_min_tile(
             self._handle, 0 if dense else self.DENSE_MIN_TILE0),
         'dense policy of `%s`' % stencil.app_name)
+    if 'dense_banked' in self.specs:
+      picked = self.specs['dense_banked'].in_kernel
+      mask = (ctypes.c_int32 * (d.num_inputs + d.num_outputs))(*[
+          1 if n in picked else 0
+          for n in list(stencil.input_names) + list(stencil.output_names)])
+      runtime.check(
+          lib.soda_hip_stream_set_banked(
+              self._handle, self._programs['dense_banked'], mask),
+          'banked form of `%s`' % stencil.app_name)
+      first = self._programs.get('dense_banked_first')
+      last = self._programs.get('dense_banked_last')
+      if first or last:
+        runtime.check(
+            lib.soda_hip_stream_set_banked_pair(self._handle, first, last),
+            'two-launch banked form of `%s`' % stencil.app_name)
 
   @property
   def last_mode(self) -> Optional[str]:
-    return {1: 'dense', 2: 'linear'}.get(
+    return {1: 'dense', 2: 'linear', 3: 'banked'}.get(
         self._lib.soda_hip_stream_last_mode(self._handle))
 
   def _flat(self, banks_by_name, names) -> 'ctypes.Array':
