@@ -50,14 +50,17 @@ extern "C" {
 #endif
 
 /* Bumped when a struct that crosses the boundary changes layout (7: the plan
- * carries the program's per-iteration reach).  Entry points added since, under
- * the same number (no struct changed): soda_hip_host_register / _unregister,
+ * carries the program's per-iteration reach; 8: the plan says whether its
+ * kernels are batched, with soda_hip_run_device_batch,
+ * soda_hip_plan_geometry_batch / _schedule_batch and the _batch forms of
+ * calibrate / pass_times / schedule).  Entry points added under 7 (no struct
+ * changed): soda_hip_host_register / _unregister,
  * soda_hip_host_weave_banks, soda_hip_stream_set_device_dense_min_tile,
  * soda_hip_stream_set_banked / _set_banked_pair (kargs.reserved[0] carries
  * the stream length to their programs); and
  * soda_hip_stream_create accepts wire[o] == NULL for an output on one bank
  * that the program stores at its wire position itself. */
-#define SODA_HIP_ABI_VERSION 7
+#define SODA_HIP_ABI_VERSION 8
 #define SODA_HIP_MAX_DIM 4
 #define SODA_HIP_MAX_TENSORS 16
 #define SODA_HIP_MAX_KERNELS 32
@@ -197,6 +200,12 @@ typedef struct soda_hip_plan {
    * i; without it they copy in, run, copy out. */
   int32_t has_reach;
   int32_t reach_lo, reach_hi;
+  /* ABI 8: != 0 -- every kernel of the plan is a batched one: it takes
+   * blockIdx.y as the item of a batch of grids that lie one behind the other
+   * in every input, output and local (not in the param arrays) and is
+   * launched on (blocks, batch, 1).  Only such a plan runs through
+   * soda_hip_run_device_batch; every other entry runs it as a batch of 1. */
+  int32_t batched;
 } soda_hip_plan_t;
 
 typedef struct soda_hip_program soda_hip_program_t;   /* opaque */
@@ -240,6 +249,18 @@ int soda_hip_plan_geometry(const soda_hip_plan_t* plan, const int32_t* extent,
  * (num_passes values): the multiset of least total modelled time. */
 int soda_hip_plan_schedule(const soda_hip_plan_t* plan, const int32_t* extent,
                            int32_t iterate, int32_t* count);
+/* The same two for ONE launch over `batch` grids of `extent`
+ * (soda_hip_run_device_batch): the batch multiplies the independent tiles the
+ * chunk lengths are sized for and the cells and waves of the time model; the
+ * 1 GiB buffer-window check is per item.  batch = 1 is what the two functions
+ * above return; batch outside 1..SODA_HIP_MAX_BATCH: SODA_HIP_ERR_INVALID. */
+#define SODA_HIP_MAX_BATCH 65535       /* gridDim.y */
+int soda_hip_plan_geometry_batch(const soda_hip_plan_t* plan,
+                                 const int32_t* extent, int32_t batch,
+                                 int32_t* tiles, float* pass_ns);
+int soda_hip_plan_schedule_batch(const soda_hip_plan_t* plan,
+                                 const int32_t* extent, int32_t batch,
+                                 int32_t iterate, int32_t* count);
 
 /* -- program = code object + plan, bound to one device -------------------- */
 int soda_hip_program_create(const void* code, size_t code_size,
@@ -359,6 +380,23 @@ int soda_hip_last_rows(soda_hip_program_t* program, int64_t* rows);
 int soda_hip_run_device(soda_hip_program_t* program, void* const* outputs,
                         const void* const* inputs, const int32_t* extent,
                         int32_t iterate, void* stream);
+/* soda_hip_run_device on `batch` independent grids of `extent` in ONE launch
+ * per kernel: every input and output pointer addresses `batch` dense items,
+ * one behind the other like a contiguous [batch, ...] array; the param arrays
+ * are shared by all items.  Per item the semantics (and the bits) are those of
+ * soda_hip_run_device; asynchronous on `stream`.  The program's scratch -- the
+ * ping-pong temporaries, the locals of passes made of several kernels -- is
+ * sized for the batch and grows when a later call brings a larger one; chunk
+ * lengths, the schedule and its calibration are chosen for the whole launch
+ * and remembered per (extent, batch).  No tensor of the call may overlap
+ * another, each taken as `batch` items long.  SODA_HIP_ERR_INVALID, text in
+ * last_error: batch outside 1..SODA_HIP_MAX_BATCH, or a program whose plan is
+ * not batched (LowerOptions.batch / sodac --hip-batch) -- the entry never
+ * falls back to a loop of launches.  batch = 1 is legal. */
+int soda_hip_run_device_batch(soda_hip_program_t* program,
+                              void* const* outputs, const void* const* inputs,
+                              const int32_t* extent, int32_t batch,
+                              int32_t iterate, void* stream);
 
 /* Replaces soda::app::<app>(): host arrays described by (ptr, extent, stride,
  * min) per tensor, inputs then outputs; copies in, runs, copies the outputs
@@ -469,6 +507,20 @@ int soda_hip_program_pass_times(soda_hip_program_t* program,
 int soda_hip_program_schedule(soda_hip_program_t* program,
                               const int32_t* extent, int32_t iterate,
                               int32_t* count);
+/* The three above for launches over `batch` grids of `extent`
+ * (soda_hip_run_device_batch; batched programs only, batch in
+ * 1..SODA_HIP_MAX_BATCH): times and schedules are remembered per (extent,
+ * batch), batch = 1 being the entries above.  A batched run calibrates by
+ * itself under the same rules as a one-grid run. */
+int soda_hip_program_calibrate_batch(soda_hip_program_t* program,
+                                     const int32_t* extent, int32_t batch,
+                                     int32_t launches, void* stream);
+int soda_hip_program_pass_times_batch(soda_hip_program_t* program,
+                                      const int32_t* extent, int32_t batch,
+                                      float* pass_ns, int32_t* measured);
+int soda_hip_program_schedule_batch(soda_hip_program_t* program,
+                                    const int32_t* extent, int32_t batch,
+                                    int32_t iterate, int32_t* count);
 
 /* Diagnostics: kernels generated with time stamps (sodac --hip-stamps) write
  * four 64-bit words per wavefront -- s_memtime at entry and exit, HW_ID,

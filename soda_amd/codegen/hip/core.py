@@ -79,6 +79,10 @@ def add_arguments(parser) -> None:
                       'the row, x-halos shared through LDS inside the block: '
                       'any row length, none needed at build time (default: '
                       'not used)')
+  parser.add_argument('--hip-batch', action='store_true', dest='hip_batch',
+                      help='batched kernels (names end in _bt): a launch runs '
+                      'many independent grids of one extent, blockIdx.y is '
+                      'the item (soda_hip_run_device_batch)')
   parser.add_argument('--hip-nt-store', action='store_true',
                       dest='hip_nt_store',
                       help='non-temporal instead of plain output stores')
@@ -121,7 +125,8 @@ def options_from_args(args: argparse.Namespace) -> lower.LowerOptions:
                             tile_rows=args.hip_tile_rows,
                             xcd_swizzle=not args.hip_no_xcd_swizzle,
                             pipe=args.hip_pipe,
-                            xshare_block=args.hip_xshare_block)
+                            xshare_block=args.hip_xshare_block,
+                            batch=bool(getattr(args, 'hip_batch', False)))
 
 
 def print_code(stencil: core.Stencil, args: argparse.Namespace) -> None:

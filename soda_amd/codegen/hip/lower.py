@@ -173,6 +173,13 @@ class LowerOptions:
   # stage-pipelined blocks, is refused with a SemanticError
   banks: Optional[Dict[str, int]] = None
   bank_lead: Optional[Dict[str, int]] = None
+  # batched kernels in every family (Module._batched, soda_rt_batch.h): a
+  # launch of (blocks, batch, 1) runs `batch` independent grids of one extent,
+  # item after item in every tensor (soda_hip_run_device_batch; the one-grid
+  # entries refuse such a program's kernels nothing, they run them as batch
+  # 1).  For callers and A/B runs: `auto` never sets it, no environment
+  # override.  Not with `banks`
+  batch: bool = False
 
   def __post_init__(self):
     self.fuse = tuple(self.fuse)
@@ -294,6 +301,10 @@ def lower(stencil: core.Stencil, opts: Optional[LowerOptions] = None) -> Module:
   if opts.xshare_block is not None and not 2 <= opts.xshare_block <= 16:
     raise util.SemanticError('xshare_block %r: None or 2 to 16 waves per block'
                              % (opts.xshare_block,))
+  if opts.batch and opts.banks:
+    raise util.SemanticError(
+        'batch: the wire format has no batch, `banks` cannot be combined with '
+        'it')
   _check_native(stencil)
   stencil.check_preserve()
   if opts.banks and opts.strategy not in ('auto', 'march'):
@@ -341,7 +352,7 @@ def lower(stencil: core.Stencil, opts: Optional[LowerOptions] = None) -> Module:
       if opts.banks:
         raise util.SemanticError(
             'banks: `ldswin` kernels read and write dense arrays')
-      mod = Module(whole)
+      mod = Module(whole, batch=opts.batch)
       try:
         add_ldswin_pass(mod, chunk=opts.chunk_rows or 64,
                         step=opts.waves_y if opts.waves_y > 1 else None)
@@ -379,7 +390,7 @@ def lower(stencil: core.Stencil, opts: Optional[LowerOptions] = None) -> Module:
   # the same bits (exact.py; the program as written unless one is enabled)
   from soda_amd.codegen.hip import exact
   stencil = exact.specialize(stencil)
-  mod = Module(stencil, opts.banks)
+  mod = Module(stencil, opts.banks, opts.batch)
   use_march = opts.strategy in ('auto', 'march', 'tile3d') and \
       march_supported(stencil) is None
   if opts.strategy == 'march' and not use_march:
@@ -486,7 +497,7 @@ def lower(stencil: core.Stencil, opts: Optional[LowerOptions] = None) -> Module:
     for v in vecs:
       for rows in rows_list:
         for pf in pfs:
-          trial = Module(stencil, opts.banks)
+          trial = Module(stencil, opts.banks, opts.batch)
           try:
             est = add_march_pass(trial, config(1, v, pf, rows)).traffic_model[
                 'est_window_regs']

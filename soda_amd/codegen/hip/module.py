@@ -8,6 +8,7 @@ from soda_amd import core, util
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _RT_PATH = os.path.join(_HERE, '..', '..', 'csrc', 'soda_rt.h')
 _RT_BANKED_PATH = os.path.join(_HERE, '..', '..', 'csrc', 'soda_rt_banked.h')
+_RT_BATCH_PATH = os.path.join(_HERE, '..', '..', 'csrc', 'soda_rt_batch.h')
 _COORDS = util.COORDS_IN_ORIG
 
 
@@ -23,6 +24,17 @@ def banked_runtime_text() -> str:
   with open(_RT_BANKED_PATH) as f:
     return f.read()
 
+
+def batch_runtime_text() -> str:
+  """The helpers of batched kernels (soda_rt_batch.h): pasted behind
+  runtime_text() into modules lowered with LowerOptions.batch, and only those."""
+  with open(_RT_BATCH_PATH) as f:
+    return f.read()
+
+
+# what every generated kernel's head ends in, and a batched kernel's instead
+_KERNEL_ARGS = '(soda_hip_kargs_t a) {'
+_BATCH_SUFFIX = '_bt'
 
 # slots of soda_hip_kargs_t.buf a banked module may use: the last one stays
 # the debug slot
@@ -60,8 +72,15 @@ class Module:
   """HIP source text + plan for one program at one vector width."""
 
   def __init__(self, stencil: core.Stencil,
-               banks: Optional[Dict[str, int]] = None):
+               banks: Optional[Dict[str, int]] = None, batch: bool = False):
     self.stencil = stencil
+    # LowerOptions.batch: every kernel is emitted in its batched form
+    # (add_kernel)
+    self.batch = bool(batch)
+    if self.batch and banks:
+      raise util.SemanticError(
+          'batch: the wire format has no batch, `banks` cannot be combined '
+          'with it')
     self.chunks: List[str] = []
     self.kernels: List[KernelDesc] = []
     self.passes: List[PassDesc] = []
@@ -112,7 +131,33 @@ class Module:
       return 'prm_%s[0]' % v.name
     return v.text()
 
+  def _batched(self, desc: KernelDesc, text: str) -> str:
+    """The batched form of a kernel of any family (soda_rt_batch.h): the same
+    text behind a head that takes blockIdx.y as the item and moves the slots
+    of the inputs, outputs and locals -- not the param arrays' -- of a copy of
+    the argument block by that many items.  The kernel's name, in `desc` too,
+    gets the suffix `_bt`."""
+    head = desc.name + _KERNEL_ARGS
+    if text.count(head) != 1:
+      raise util.InternalError('batch: kernel head of %s not found' % desc.name)
+    st = self.stencil
+    moved = list(st.input_names) + list(st.output_names) + list(st.local_names)
+    lines = [desc.name + _BATCH_SUFFIX + '(soda_hip_kargs_t soda_a0) {',
+             '  // batched: blockIdx.y is the item; the items of every tensor '
+             'lie one behind the other',
+             '  soda_hip_kargs_t a = soda_a0;',
+             '  const int64_t soda_item = soda_batch_cells<%d>(soda_a0) * '
+             '(int64_t)blockIdx.y;' % st.dim]
+    for n in moved:
+      lines.append('  a.buf[%d] = soda_batch_base<%d>(soda_a0.buf[%d], '
+                   'soda_item);  // %s' %
+                   (self.slot[n], self.elem_size[self.slot[n]], self.slot[n], n))
+    desc.name += _BATCH_SUFFIX
+    return text.replace(head, '\n'.join(lines))
+
   def add_kernel(self, desc: KernelDesc, text: str) -> int:
+    if self.batch:
+      text = self._batched(desc, text)
     self.kernels.append(desc)
     self.chunks.append(text)
     return len(self.kernels) - 1
@@ -135,6 +180,7 @@ class Module:
     from soda_amd.codegen.hip import exact
     return (head + runtime_text() +
             (banked_runtime_text() if self.banks else '') +
+            (batch_runtime_text() if self.batch else '') +
             exact.helper_text(self.stencil) + '\n' + '\n'.join(self.chunks))
 
   def sorted_passes(self) -> List[PassDesc]:

@@ -177,9 +177,9 @@ int soda_hip_compiler_version(int32_t* major, int32_t* minor) {
 
 static int check_plan(const soda_hip_plan_t* p);
 static int plan_geometry_c(const soda_hip_plan_t* plan, const int32_t* extent,
-                           int32_t* tiles, float* pass_ns);
+                           int32_t* tiles, float* pass_ns, int32_t batch = 1);
 static int plan_schedule_c(const soda_hip_plan_t* plan, const int32_t* extent,
-                           int32_t iterate, int32_t* count);
+                           int32_t iterate, int32_t* count, int32_t batch = 1);
 
 int soda_hip_plan_geometry(const soda_hip_plan_t* plan, const int32_t* extent,
                            int32_t* tiles, float* pass_ns) {
@@ -189,6 +189,28 @@ int soda_hip_plan_geometry(const soda_hip_plan_t* plan, const int32_t* extent,
 int soda_hip_plan_schedule(const soda_hip_plan_t* plan, const int32_t* extent,
                            int32_t iterate, int32_t* count) {
   return plan_schedule_c(plan, extent, iterate, count);
+}
+
+static int check_batch(int32_t batch, const char* who) {
+  if (batch >= 1 && batch <= SODA_HIP_MAX_BATCH) return SODA_HIP_OK;
+  char buf[160];
+  snprintf(buf, sizeof buf, "%s: batch = %d, must be 1 to %d (the grid's y "
+           "dimension)", who, batch, SODA_HIP_MAX_BATCH);
+  return fail(SODA_HIP_ERR_INVALID, buf);
+}
+
+int soda_hip_plan_geometry_batch(const soda_hip_plan_t* plan,
+                                 const int32_t* extent, int32_t batch,
+                                 int32_t* tiles, float* pass_ns) {
+  if (int rc = check_batch(batch, "plan_geometry_batch")) return rc;
+  return plan_geometry_c(plan, extent, tiles, pass_ns, batch);
+}
+
+int soda_hip_plan_schedule_batch(const soda_hip_plan_t* plan,
+                                 const int32_t* extent, int32_t batch,
+                                 int32_t iterate, int32_t* count) {
+  if (int rc = check_batch(batch, "plan_schedule_batch")) return rc;
+  return plan_schedule_c(plan, extent, iterate, count, batch);
 }
 
 static int check_plan(const soda_hip_plan_t* p) {
@@ -451,10 +473,14 @@ int32_t tuned_chunk(const soda_hip_kernel_desc_t& d, const int32_t* tile,
   return (int32_t)((n + chunks - 1) / chunks);   // same count, equal lengths
 }
 
+// `batch` grids of `extent` in one launch (soda_hip_run_device_batch): as many
+// times the independent tiles for the chunk rule, the cells and the waves for
+// the time model; what a kernel can run at all -- row lengths, the buffer
+// window, which is relative to an item's own base -- is judged per item
 int kernel_geometry(const soda_hip_kernel_desc_t& d, const int32_t* extent,
-                    int dim, Geometry* g) {
+                    int dim, int32_t batch, Geometry* g) {
   char buf[384];
-  int64_t cells = 1;
+  int64_t cells = batch;
   for (int i = 0; i < SODA_HIP_MAX_DIM; ++i) {
     g->tile[i] = i < dim ? d.tile[i] : 1;
     if (i < dim) cells *= extent[i];
@@ -482,7 +508,7 @@ int kernel_geometry(const soda_hip_kernel_desc_t& d, const int32_t* extent,
     const int axis = d.march_dim - 1;
     const int along = d.waves_along > 0 ? d.waves_along : 1;
     const int wpb = (d.block[0] * d.block[1] * d.block[2] + 63) / 64;
-    int64_t others = 1;
+    int64_t others = batch;
     for (int i = 0; i < dim; ++i)
       if (i != axis) others *= (extent[i] + g->tile[i] - 1) / g->tile[i];
     int32_t per_wave = g->tile[axis] / along;
@@ -552,10 +578,12 @@ int kernel_geometry(const soda_hip_kernel_desc_t& d, const int32_t* extent,
 
 // tiles of every kernel and time of every pass for `extent`
 int plan_geometry(const soda_hip_plan_t& plan, const int32_t* extent,
-                  std::vector<Geometry>* geo, std::vector<double>* pass_ns) {
+                  int32_t batch, std::vector<Geometry>* geo,
+                  std::vector<double>* pass_ns) {
   geo->resize(plan.num_kernels);
   for (int k = 0; k < plan.num_kernels; ++k)
-    if (int rc = kernel_geometry(plan.kernels[k], extent, plan.dim, &(*geo)[k]))
+    if (int rc = kernel_geometry(plan.kernels[k], extent, plan.dim, batch,
+                                 &(*geo)[k]))
       return rc;
   pass_ns->assign(plan.num_passes, 0.0);
   for (int i = 0; i < plan.num_passes; ++i) {
@@ -586,7 +614,7 @@ struct TileRange {
 
 int launch(soda_hip_program* p, int k, const soda_hip_kargs_t& base,
            const int32_t* tile, hipStream_t stream,
-           const TileRange* range = nullptr) {
+           const TileRange* range = nullptr, int32_t batch = 1) {
   const soda_hip_kernel_desc_t& d = p->plan.kernels[k];
   soda_hip_kargs_t args = base;
   int64_t blocks = 1;
@@ -604,7 +632,10 @@ int launch(soda_hip_program* p, int k, const soda_hip_kargs_t& base,
   size_t size = sizeof args;
   void* extra[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &args,
                    HIP_LAUNCH_PARAM_BUFFER_SIZE, &size, HIP_LAUNCH_PARAM_END};
-  HIP_TRY(hipModuleLaunchKernel(p->functions[k], (unsigned)blocks, 1, 1,
+  // (a batched kernel takes blockIdx.y as the item; every other kernel is
+  // launched with batch = 1 and never looks)
+  HIP_TRY(hipModuleLaunchKernel(p->functions[k], (unsigned)blocks,
+                                (unsigned)batch, 1,
                                 d.block[0], d.block[1], d.block[2],
                                 d.lds_bytes, stream, nullptr, extra));
   return SODA_HIP_OK;
@@ -667,13 +698,14 @@ int schedule(const soda_hip_plan_t& plan, const std::vector<double>& pass_ns,
 
 int extent_plan(const soda_hip_plan_t& plan,
                 std::map<ExtentKey, ExtentPlan>* cache, const int32_t* ext,
-                const ExtentPlan** out) {
+                const ExtentPlan** out, int32_t batch) {
   ExtentKey key;
   for (int d = 0; d < SODA_HIP_MAX_DIM; ++d) key[d] = ext[d];
   auto it = cache->find(key);
   if (it == cache->end()) {
     ExtentPlan ep;
-    if (int rc = plan_geometry(plan, ext, &ep.geo, &ep.model_ns)) return rc;
+    if (int rc = plan_geometry(plan, ext, batch, &ep.geo, &ep.model_ns))
+      return rc;
     if (cache->size() > 4096) cache->clear();
     it = cache->emplace(key, std::move(ep)).first;
   }
@@ -684,7 +716,7 @@ int extent_plan(const soda_hip_plan_t& plan,
 }  // namespace soda_detail
 
 static int plan_geometry_c(const soda_hip_plan_t* plan, const int32_t* extent,
-                           int32_t* tiles, float* pass_ns) {
+                           int32_t* tiles, float* pass_ns, int32_t batch) {
   if (!plan || !extent) return fail(SODA_HIP_ERR_INVALID, "geometry: NULL argument");
   if (int rc = check_plan(plan)) return rc;
   int32_t ext[SODA_HIP_MAX_DIM];
@@ -694,7 +726,7 @@ static int plan_geometry_c(const soda_hip_plan_t* plan, const int32_t* extent,
   }
   std::vector<Geometry> geo;
   std::vector<double> ns;
-  if (int rc = plan_geometry(*plan, ext, &geo, &ns)) return rc;
+  if (int rc = plan_geometry(*plan, ext, batch, &geo, &ns)) return rc;
   if (tiles)
     for (int k = 0; k < plan->num_kernels; ++k)
       for (int d = 0; d < SODA_HIP_MAX_DIM; ++d)
@@ -705,7 +737,7 @@ static int plan_geometry_c(const soda_hip_plan_t* plan, const int32_t* extent,
 }
 
 static int plan_schedule_c(const soda_hip_plan_t* plan, const int32_t* extent,
-                           int32_t iterate, int32_t* count) {
+                           int32_t iterate, int32_t* count, int32_t batch) {
   if (!plan || !extent || !count)
     return fail(SODA_HIP_ERR_INVALID, "schedule: NULL argument");
   if (iterate < 1) return fail(SODA_HIP_ERR_INVALID, "cannot iterate < 1 times");
@@ -717,7 +749,7 @@ static int plan_schedule_c(const soda_hip_plan_t* plan, const int32_t* extent,
   }
   std::vector<Geometry> geo;
   std::vector<double> ns;
-  if (int rc = plan_geometry(*plan, ext, &geo, &ns)) return rc;
+  if (int rc = plan_geometry(*plan, ext, batch, &geo, &ns)) return rc;
   int32_t total = 0;
   return schedule(*plan, ns, iterate, count, &total);
 }
@@ -865,10 +897,15 @@ int run_core(soda_hip_program_t* p, void* const* outputs,
              const void* const* inputs, const int32_t* extent,
              const int32_t* origin, const int32_t* global_extent,
              int32_t iterate, void* stream_, int force_pass,
-             const SlabRun* slab) {
+             const SlabRun* slab, int32_t batch) {
   if (!p || !outputs || !inputs || !extent)
     return fail(SODA_HIP_ERR_INVALID, "run_device: NULL argument");
   const soda_hip_plan_t& plan = p->plan;
+  if (batch < 1 || (batch > 1 && (!plan.batched || slab)))
+    return fail(SODA_HIP_ERR_INVALID, "run_core: bad batch");
+  // plans, schedules and measured times of this batch size
+  std::map<ExtentKey, ExtentPlan>& extents = extents_of(p, batch);
+  std::map<ExtentKey, std::vector<double>>& measured = measured_of(p, batch);
   if (iterate < 1) return fail(SODA_HIP_ERR_INVALID, "cannot iterate < 1 times");
   if (iterate > 1 && plan.num_inputs != plan.num_outputs)
     return fail(SODA_HIP_ERR_INVALID,
@@ -909,7 +946,7 @@ int run_core(soda_hip_program_t* p, void* const* outputs,
   // 8 x 12 + 4); without costs, as many of the deepest kind as fit, then the
   // next...  Remembered per (extent, iterate).
   const ExtentPlan* ep = nullptr;
-  if (int rc = extent_plan(plan, &p->extents, base.extent, &ep)) return rc;
+  if (int rc = extent_plan(plan, &extents, base.extent, &ep, batch)) return rc;
   int32_t count[SODA_HIP_MAX_PASSES];
   int32_t total = 0;
   if (force_pass >= 0) {
@@ -937,22 +974,24 @@ int run_core(soda_hip_program_t* p, void* const* outputs,
     if (p->auto_calibrate && !p->calibrating && !beside_exchange &&
         capture == hipStreamCaptureStatusNone && iterate > 1 &&
         plan.num_passes > 1 && plan.num_inputs == plan.num_outputs &&
-        !p->measured.count(key)) {
+        !measured.count(key)) {
       // first run on this extent: let the clock rank the passes
       p->calibrating = true;
-      int rc = soda_hip_program_calibrate(p, base.extent, 4, stream_);
+      int rc = soda_hip_program_calibrate_batch(p, base.extent, batch, 4,
+                                                stream_);
       p->calibrating = false;
       if (rc) return rc;
-      if (int rc2 = extent_plan(plan, &p->extents, base.extent, &ep)) return rc2;
+      if (int rc2 = extent_plan(plan, &extents, base.extent, &ep, batch))
+        return rc2;
     }
     auto& memo = const_cast<ExtentPlan*>(ep)->sched;
     auto hit = memo.find(iterate);
     if (hit == memo.end()) {
       // measured launch times of this very extent (soda_hip_program_calibrate)
       // outrank the model
-      auto it = p->measured.find(key);
+      auto it = measured.find(key);
       const std::vector<double>& pass_ns =
-          it != p->measured.end() ? it->second : ep->model_ns;
+          it != measured.end() ? it->second : ep->model_ns;
       if (int rc = schedule(plan, pass_ns, iterate, count, &total)) return rc;
       std::vector<int32_t> row(count, count + plan.num_passes);
       row.push_back(total);
@@ -983,19 +1022,23 @@ int run_core(soda_hip_program_t* p, void* const* outputs,
     for (int k = 0; count[i] && k < plan.passes[i].num_kernels; ++k)
       need_locals = need_locals ||
                     plan.kernels[plan.passes[i].kernel[k]].march_dim == 0;
+  // (all of it for the whole batch: item i of a local or a temporary lies i
+  // grids behind its start, like the caller's tensors; a larger batch regrows)
   for (int l = 0; need_locals && l < plan.num_locals; ++l) {
-    int rc = ensure(p->locals[l], (size_t)cells * plan.elem_size[loc0 + l]);
+    int rc = ensure(p->locals[l],
+                    (size_t)cells * batch * plan.elem_size[loc0 + l]);
     if (rc) return rc;
     base.buf[loc0 + l] = p->locals[l].ptr;
   }
   if (total > 1)
     for (int o = 0; o < plan.num_outputs; ++o) {
-      int rc = ensure(p->temps[o], (size_t)cells * plan.elem_size[out0 + o]);
+      int rc = ensure(p->temps[o],
+                      (size_t)cells * batch * plan.elem_size[out0 + o]);
       if (rc) return rc;
     }
 
   std::vector<PassLaunch> launches;
-  if (int rc = plan_launches(plan, &p->extents, base.extent, count, total,
+  if (int rc = plan_launches(plan, &extents, base.extent, count, total,
                              iterate, slab, &launches))
     return rc;
   p->last_launches = 0;
@@ -1024,7 +1067,8 @@ int run_core(soda_hip_program_t* p, void* const* outputs,
                       (int64_t)L.lo * base.stride[ax] * plan.elem_size[t];
     }
     const ExtentPlan* use = nullptr;
-    if (int rc = extent_plan(plan, &p->extents, args.extent, &use)) return rc;
+    if (int rc = extent_plan(plan, &extents, args.extent, &use, batch))
+      return rc;
     p->last_rows += L.hi - L.lo;
     const int k0 = plan.passes[i].kernel[0];
     if (L.split && split_in_order()) {
@@ -1077,7 +1121,7 @@ int run_core(soda_hip_program_t* p, void* const* outputs,
       if (L.wait) HIP_TRY(hipStreamWaitEvent(stream, slab->ghosts_ready, 0));
       for (int k = 0; k < plan.passes[i].num_kernels; ++k) {
         const int kk = plan.passes[i].kernel[k];
-        int rc = launch(p, kk, args, use->geo[kk].tile, stream);
+        int rc = launch(p, kk, args, use->geo[kk].tile, stream, nullptr, batch);
         if (rc) return rc;
         ++p->last_launches;
         if (i == 0) ++p->last_fused;
@@ -1099,6 +1143,52 @@ int soda_hip_run_device(soda_hip_program_t* p, void* const* outputs,
                         int32_t iterate, void* stream_) {
   return run_core(p, outputs, inputs, extent, nullptr, nullptr, iterate,
                   stream_, -1, nullptr);
+}
+
+int soda_hip_run_device_batch(soda_hip_program_t* p, void* const* outputs,
+                              const void* const* inputs, const int32_t* extent,
+                              int32_t batch, int32_t iterate, void* stream_) {
+  if (!p || !outputs || !inputs || !extent)
+    return fail(SODA_HIP_ERR_INVALID, "run_device_batch: NULL argument");
+  if (int rc = check_batch(batch, "run_device_batch")) return rc;
+  const soda_hip_plan_t& plan = p->plan;
+  if (!plan.batched)
+    return fail(SODA_HIP_ERR_INVALID,
+                "run_device_batch: the program's kernels are not batched "
+                "(build it with LowerOptions.batch / sodac --hip-batch); "
+                "nothing was launched");
+  // no tensor may overlap another, each `batch` items long (inputs may share:
+  // they are only read)
+  int64_t cells = batch;
+  for (int d = 0; d < plan.dim; ++d) {
+    if (extent[d] < 1)
+      return fail(SODA_HIP_ERR_INVALID, "run_device_batch: extent < 1");
+    cells *= extent[d];
+  }
+  const int out0 = plan.num_inputs;
+  auto overlap = [&](const void* a, int sa, const void* b, int sb) {
+    const uintptr_t a0 = reinterpret_cast<uintptr_t>(a);
+    const uintptr_t b0 = reinterpret_cast<uintptr_t>(b);
+    return a0 < b0 + (uint64_t)cells * plan.elem_size[sb] &&
+           b0 < a0 + (uint64_t)cells * plan.elem_size[sa];
+  };
+  for (int o = 0; o < plan.num_outputs; ++o) {
+    if (!outputs[o])
+      return fail(SODA_HIP_ERR_INVALID, "run_device_batch: NULL output");
+    for (int i = 0; i < plan.num_inputs; ++i)
+      if (inputs[i] && overlap(outputs[o], out0 + o, inputs[i], i))
+        return fail(SODA_HIP_ERR_INVALID,
+                    "run_device_batch: an output overlaps an input (each "
+                    "tensor is `batch` items long; in-place runs are not "
+                    "supported)");
+    for (int q = 0; q < o; ++q)
+      if (overlap(outputs[o], out0 + o, outputs[q], out0 + q))
+        return fail(SODA_HIP_ERR_INVALID,
+                    "run_device_batch: two outputs overlap (each tensor is "
+                    "`batch` items long)");
+  }
+  return run_core(p, outputs, inputs, extent, nullptr, nullptr, iterate,
+                  stream_, -1, nullptr, batch);
 }
 
 int soda_hip_run_device_window(soda_hip_program_t* p, void* const* outputs,
@@ -1203,8 +1293,27 @@ static int slab_run(const soda_hip_slab_run_t* run, const int32_t* extent,
 
 int soda_hip_program_calibrate(soda_hip_program_t* p, const int32_t* extent,
                                int32_t launches, void* stream_) {
+  return soda_hip_program_calibrate_batch(p, extent, 1, launches, stream_);
+}
+
+// a program handle's batch argument: in range, and > 1 only for batched plans
+static int check_program_batch(const soda_hip_program* p, int32_t batch,
+                               const char* who) {
+  if (int rc = check_batch(batch, who)) return rc;
+  if (batch > 1 && !p->plan.batched)
+    return fail(SODA_HIP_ERR_INVALID,
+                std::string(who) + ": the program's kernels are not batched");
+  return SODA_HIP_OK;
+}
+
+int soda_hip_program_calibrate_batch(soda_hip_program_t* p,
+                                     const int32_t* extent, int32_t batch,
+                                     int32_t launches, void* stream_) {
   if (!p || !extent) return fail(SODA_HIP_ERR_INVALID, "calibrate: NULL argument");
+  if (int rc = check_program_batch(p, batch, "calibrate")) return rc;
   const soda_hip_plan_t& plan = p->plan;
+  std::map<ExtentKey, ExtentPlan>& extents = extents_of(p, batch);
+  std::map<ExtentKey, std::vector<double>>& measured = measured_of(p, batch);
   if (launches < 2) launches = 4;
   hipStream_t stream = static_cast<hipStream_t>(stream_);
   HIP_TRY(hipSetDevice(p->device));
@@ -1216,9 +1325,9 @@ int soda_hip_program_calibrate(soda_hip_program_t* p, const int32_t* extent,
     cells *= key[d];
   }
   if (plan.num_passes < 2 || plan.num_inputs != plan.num_outputs) {
-    p->measured.erase(key);          // nothing to choose between
-    auto it = p->extents.find(key);
-    if (it != p->extents.end()) it->second.sched.clear();
+    measured.erase(key);          // nothing to choose between
+    auto it = extents.find(key);
+    if (it != extents.end()) it->second.sched.clear();
     return SODA_HIP_OK;
   }
   // stand-in arrays: inputs (a byte pattern that reads as ~0.75 in fp32, small
@@ -1232,7 +1341,7 @@ int soda_hip_program_calibrate(soda_hip_program_t* p, const int32_t* extent,
   for (size_t b = 0; b < bufs.size() && rc == SODA_HIP_OK; ++b) {
     size_t bytes;
     if ((int)b < plan.num_inputs + plan.num_outputs)
-      bytes = (size_t)cells * plan.elem_size[b];
+      bytes = (size_t)cells * batch * plan.elem_size[b];
     else
       bytes = (size_t)plan.param_elems[b - plan.num_inputs - plan.num_outputs] *
               plan.elem_size[prm0 + (b - plan.num_inputs - plan.num_outputs)];
@@ -1269,19 +1378,19 @@ int soda_hip_program_calibrate(soda_hip_program_t* p, const int32_t* extent,
       for (int i = 0; i < plan.num_passes && rc == SODA_HIP_OK; ++i)
         rc = run_core(p, outs.data(), ins.data(), key.data(), nullptr, nullptr,
                       plan.passes[i].fused_iters * launches, stream_, i,
-                      nullptr);
+                      nullptr, batch);
     for (int round = 0; round < kTimedRounds && rc == SODA_HIP_OK; ++round)
       for (int i = 0; i < plan.num_passes && rc == SODA_HIP_OK; ++i) {
         const int32_t one = plan.passes[i].fused_iters;
         hipEvent_t* pair = &ev[2 * (round * plan.num_passes + i)];
         rc = run_core(p, outs.data(), ins.data(), key.data(), nullptr, nullptr,
-                      one, stream_, i, nullptr);
+                      one, stream_, i, nullptr, batch);
         if (rc != SODA_HIP_OK) break;
         if (hipEventRecord(pair[0], stream) != hipSuccess)
           rc = fail(SODA_HIP_ERR_RUNTIME, "calibrate: hipEventRecord");
         if (rc != SODA_HIP_OK) break;
         rc = run_core(p, outs.data(), ins.data(), key.data(), nullptr, nullptr,
-                      one * launches, stream_, i, nullptr);
+                      one * launches, stream_, i, nullptr, batch);
         if (rc == SODA_HIP_OK && hipEventRecord(pair[1], stream) != hipSuccess)
           rc = fail(SODA_HIP_ERR_RUNTIME, "calibrate: hipEventRecord");
       }
@@ -1302,9 +1411,9 @@ int soda_hip_program_calibrate(soda_hip_program_t* p, const int32_t* extent,
   for (auto& b : bufs)
     if (b.ptr) (void)hipFree(b.ptr);
   if (rc == SODA_HIP_OK) {
-    p->measured[key] = ns;
-    auto it = p->extents.find(key);        // schedules made from the model
-    if (it != p->extents.end()) it->second.sched.clear();
+    measured[key] = ns;
+    auto it = extents.find(key);        // schedules made from the model
+    if (it != extents.end()) it->second.sched.clear();
   }
   return rc;
 }
@@ -1317,27 +1426,42 @@ int soda_hip_program_set_auto_calibrate(soda_hip_program_t* p, int on) {
 
 int soda_hip_program_pass_times(soda_hip_program_t* p, const int32_t* extent,
                                 float* pass_ns, int32_t* measured) {
+  return soda_hip_program_pass_times_batch(p, extent, 1, pass_ns, measured);
+}
+
+int soda_hip_program_pass_times_batch(soda_hip_program_t* p,
+                                      const int32_t* extent, int32_t batch,
+                                      float* pass_ns, int32_t* measured) {
   if (!p || !extent || !pass_ns)
     return fail(SODA_HIP_ERR_INVALID, "pass_times: NULL argument");
+  if (int rc = check_program_batch(p, batch, "pass_times")) return rc;
   const soda_hip_plan_t& plan = p->plan;
   std::array<int32_t, SODA_HIP_MAX_DIM> key;
   for (int d = 0; d < SODA_HIP_MAX_DIM; ++d) key[d] = d < plan.dim ? extent[d] : 1;
-  auto it = p->measured.find(key);
-  if (measured) *measured = it != p->measured.end();
-  if (it != p->measured.end()) {
+  const std::map<ExtentKey, std::vector<double>>& known = measured_of(p, batch);
+  auto it = known.find(key);
+  if (measured) *measured = it != known.end();
+  if (it != known.end()) {
     for (int i = 0; i < plan.num_passes; ++i) pass_ns[i] = (float)it->second[i];
     return SODA_HIP_OK;
   }
-  return plan_geometry_c(&plan, key.data(), nullptr, pass_ns);
+  return plan_geometry_c(&plan, key.data(), nullptr, pass_ns, batch);
 }
 
 int soda_hip_program_schedule(soda_hip_program_t* p, const int32_t* extent,
                               int32_t iterate, int32_t* count) {
+  return soda_hip_program_schedule_batch(p, extent, 1, iterate, count);
+}
+
+int soda_hip_program_schedule_batch(soda_hip_program_t* p,
+                                    const int32_t* extent, int32_t batch,
+                                    int32_t iterate, int32_t* count) {
   if (!p || !extent || !count)
     return fail(SODA_HIP_ERR_INVALID, "program_schedule: NULL argument");
   if (iterate < 1) return fail(SODA_HIP_ERR_INVALID, "cannot iterate < 1 times");
   std::vector<float> ns(p->plan.num_passes);
-  if (int rc = soda_hip_program_pass_times(p, extent, ns.data(), nullptr))
+  if (int rc = soda_hip_program_pass_times_batch(p, extent, batch, ns.data(),
+                                                 nullptr))
     return rc;
   std::vector<double> t(ns.begin(), ns.end());
   int32_t total = 0;

@@ -116,6 +116,15 @@ struct soda_hip_program {
   // measured time of one launch of every pass, per extent (calibrate)
   std::map<soda_detail::ExtentKey, std::vector<double>> measured;
   std::map<soda_detail::ExtentKey, soda_detail::ExtentPlan> extents;
+  // the same two for launches over a batch of grids
+  // (soda_hip_run_device_batch), per batch size > 1: a plan, a schedule and a
+  // measured time hold for one (extent, batch) only.  measured_of /
+  // extents_of pick the map of a batch size
+  std::map<int32_t, std::map<soda_detail::ExtentKey, std::vector<double>>>
+      measured_bt;
+  std::map<int32_t,
+           std::map<soda_detail::ExtentKey, soda_detail::ExtentPlan>>
+      extents_bt;
   // split passes: the chunks next to a slab's ghost rows run on a stream of
   // their own, beside the interior on the caller's stream
   hipStream_t side = nullptr;
@@ -126,12 +135,29 @@ struct soda_hip_program {
 
 namespace soda_detail {
 
-// force_pass >= 0: use only that pass (calibration)
+// force_pass >= 0: use only that pass (calibration).  batch > 1: every
+// tensor holds that many grids of `extent`, one launch runs them all (a
+// batched plan, no slab: soda_hip_run_device_batch checks)
 int run_core(soda_hip_program* p, void* const* outputs,
              const void* const* inputs, const int32_t* extent,
              const int32_t* origin, const int32_t* global_extent,
              int32_t iterate, void* stream, int force_pass,
-             const SlabRun* slab);
+             const SlabRun* slab, int32_t batch = 1);
+
+inline std::map<ExtentKey, std::vector<double>>& measured_of(
+    soda_hip_program* p, int32_t batch) {
+  if (batch <= 1) return p->measured;
+  if (p->measured_bt.size() > 64 && !p->measured_bt.count(batch))
+    p->measured_bt.clear();
+  return p->measured_bt[batch];
+}
+inline std::map<ExtentKey, ExtentPlan>& extents_of(soda_hip_program* p,
+                                                   int32_t batch) {
+  if (batch <= 1) return p->extents;
+  if (p->extents_bt.size() > 64 && !p->extents_bt.count(batch))
+    p->extents_bt.clear();
+  return p->extents_bt[batch];
+}
 
 // one launch (or, split, one pair of launches) of a run
 struct PassLaunch {
@@ -147,10 +173,11 @@ int plan_launches(const soda_hip_plan_t& plan,
                   const SlabRun* slab, std::vector<PassLaunch>* out);
 
 // tiles, modelled pass times and schedules of `plan` on `ext` (all
-// SODA_HIP_MAX_DIM entries filled), remembered in `cache`
+// SODA_HIP_MAX_DIM entries filled) for launches over `batch` grids,
+// remembered in `cache` (which holds one batch size's: extents_of)
 int extent_plan(const soda_hip_plan_t& plan,
                 std::map<ExtentKey, ExtentPlan>* cache, const int32_t* ext,
-                const ExtentPlan** out);
+                const ExtentPlan** out, int32_t batch = 1);
 
 // launches of every pass for `iterate` iterations by the given pass times
 int schedule(const soda_hip_plan_t& plan, const std::vector<double>& pass_ns,

@@ -54,7 +54,8 @@ NAME_LEN = 96
 GROUP_NO_OVERLAP = 1
 GROUP_CALIBRATE = 2
 GROUP_THREADS = 4
-ABI_VERSION = 7
+ABI_VERSION = 8
+MAX_BATCH = 65535      # SODA_HIP_MAX_BATCH: gridDim.y
 
 
 class KernelDesc(ctypes.Structure):
@@ -97,7 +98,7 @@ class Plan(ctypes.Structure):
               ('num_passes', ctypes.c_int32),
               ('passes', PassDesc * MAX_PASSES),
               ('has_reach', ctypes.c_int32), ('reach_lo', ctypes.c_int32),
-              ('reach_hi', ctypes.c_int32)]
+              ('reach_hi', ctypes.c_int32), ('batched', ctypes.c_int32)]
 
 
 class StreamDesc(ctypes.Structure):
@@ -192,11 +193,20 @@ API = {
     'soda_hip_plan_schedule': (ctypes.c_int, [
         ctypes.POINTER(Plan), _pi32, _i32, _pi32
     ]),
+    'soda_hip_plan_geometry_batch': (ctypes.c_int, [
+        ctypes.POINTER(Plan), _pi32, _i32, _pi32,
+        ctypes.POINTER(ctypes.c_float)
+    ]),
+    'soda_hip_plan_schedule_batch': (ctypes.c_int, [
+        ctypes.POINTER(Plan), _pi32, _i32, _i32, _pi32
+    ]),
     'soda_hip_program_create': (ctypes.c_int, [
         _vp, ctypes.c_size_t, ctypes.POINTER(Plan), _i32, _pvp
     ]),
     'soda_hip_program_destroy': (ctypes.c_int, [_vp]),
     'soda_hip_run_device': (ctypes.c_int, [_vp, _pvp, _pvp, _pi32, _i32, _vp]),
+    'soda_hip_run_device_batch': (ctypes.c_int, [_vp, _pvp, _pvp, _pi32, _i32,
+                                                 _i32, _vp]),
     'soda_hip_run_device_window': (ctypes.c_int, [_vp, _pvp, _pvp, _pi32, _pi32,
                                                   _pi32, _i32, _vp]),
     'soda_hip_run_device_cone': (ctypes.c_int, [_vp, _pvp, _pvp, _pi32, _pi32,
@@ -259,6 +269,13 @@ API = {
     'soda_hip_program_schedule': (ctypes.c_int, [_vp, _pi32, _i32, _pi32]),
     'soda_hip_program_pass_times': (ctypes.c_int, [
         _vp, _pi32, ctypes.POINTER(ctypes.c_float), _pi32
+    ]),
+    'soda_hip_program_calibrate_batch': (ctypes.c_int, [_vp, _pi32, _i32, _i32,
+                                                        _vp]),
+    'soda_hip_program_schedule_batch': (ctypes.c_int, [_vp, _pi32, _i32, _i32,
+                                                       _pi32]),
+    'soda_hip_program_pass_times_batch': (ctypes.c_int, [
+        _vp, _pi32, _i32, ctypes.POINTER(ctypes.c_float), _pi32
     ]),
     'soda_hip_stream_create': (ctypes.c_int, [
         ctypes.POINTER(StreamDesc), _vp, _pvp, _pvp, _pvp, _pvp
@@ -508,6 +525,7 @@ def make_plan(mod: lower.Module,
       plan.passes[i].kernel[j] = k
   plan.has_reach = 1
   plan.reach_lo, plan.reach_hi = st.reach_along(st.dim - 1)
+  plan.batched = 1 if getattr(mod, 'batch', False) else 0
   return plan
 
 
@@ -600,6 +618,33 @@ def plan_geometry(plan: Plan, extent: Sequence[int]):
         'launch geometry for extent %s' % (tuple(extent),))
   return ([tuple(tiles[k * MAX_DIM:(k + 1) * MAX_DIM])
            for k in range(plan.num_kernels)], list(ns))
+
+
+def plan_geometry_batch(plan: Plan, extent: Sequence[int], batch: int):
+  """plan_geometry for ONE launch over `batch` grids of `extent`
+  (soda_hip_plan_geometry_batch): the chunk lengths and the pass times of the
+  whole launch.  batch = 1 is plan_geometry."""
+  lib = library()
+  ext = (ctypes.c_int32 * MAX_DIM)(*(list(extent) + [1] * (MAX_DIM - len(extent))))
+  tiles = (ctypes.c_int32 * (MAX_DIM * plan.num_kernels))()
+  ns = (ctypes.c_float * plan.num_passes)()
+  check(lib.soda_hip_plan_geometry_batch(ctypes.byref(plan), ext, batch, tiles,
+                                         ns),
+        'launch geometry for %d x extent %s' % (batch, tuple(extent)))
+  return ([tuple(tiles[k * MAX_DIM:(k + 1) * MAX_DIM])
+           for k in range(plan.num_kernels)], list(ns))
+
+
+def plan_schedule_batch(plan: Plan, extent: Sequence[int], batch: int,
+                        iterate: int):
+  """plan_schedule for launches over `batch` grids of `extent`."""
+  lib = library()
+  ext = (ctypes.c_int32 * MAX_DIM)(*(list(extent) + [1] * (MAX_DIM - len(extent))))
+  count = (ctypes.c_int32 * plan.num_passes)()
+  check(lib.soda_hip_plan_schedule_batch(ctypes.byref(plan), ext, batch,
+                                         iterate, count),
+        'schedule of %d iterations on a batch of %d' % (iterate, batch))
+  return list(count)
 
 
 def plan_schedule(plan: Plan, extent: Sequence[int], iterate: int):
@@ -915,47 +960,56 @@ class Program:
       self.calibrate(extent)
 
   # -- launch geometry ------------------------------------------------------
-  def geometry(self, extent: Sequence[int]):
-    """What a run on `extent` uses: ({kernel name: tile}, {fused iterations
-    of a pass: modelled microseconds})."""
-    tiles, ns = plan_geometry(self.plan, extent)
+  def geometry(self, extent: Sequence[int], batch: int = 1):
+    """What a run on `extent` -- on `batch` grids of it in one launch -- uses:
+    ({kernel name: tile}, {fused iterations of a pass: modelled
+    microseconds})."""
+    if batch == 1:
+      tiles, ns = plan_geometry(self.plan, extent)
+    else:
+      tiles, ns = plan_geometry_batch(self.plan, extent, batch)
     passes = self.module.sorted_passes()
     return ({k.name: t[:self.stencil.dim]
              for k, t in zip(self.module.kernels, tiles)},
             {p.fused_iters: v / 1e3 for p, v in zip(passes, ns)})
 
   def calibrate(self, extent: Sequence[int], launches: int = 4,
-                stream: int = 0) -> Dict[int, float]:
-    """Times one launch of every pass on `extent` on the GPU (a few ms, once)
-    so that runs on this extent are scheduled by the clock; returns {fused
-    iterations: microseconds}."""
+                stream: int = 0, batch: int = 1) -> Dict[int, float]:
+    """Times one launch of every pass on `extent` -- on `batch` grids of it --
+    on the GPU (a few ms, once) so that such runs are scheduled by the clock;
+    returns {fused iterations: microseconds}."""
     ext = (ctypes.c_int32 * MAX_DIM)(*(list(extent) +
                                         [1] * (MAX_DIM - len(extent))))
-    check(self._lib.soda_hip_program_calibrate(self._handle, ext, launches,
-                                               ctypes.c_void_p(stream)),
+    check(self._lib.soda_hip_program_calibrate_batch(self._handle, ext, batch,
+                                                     launches,
+                                                     ctypes.c_void_p(stream)),
           'calibrating `%s`' % self.stencil.app_name)
-    return self.pass_times(extent)[0]
+    return self.pass_times(extent, batch)[0]
 
-  def pass_times(self, extent: Sequence[int]):
+  def pass_times(self, extent: Sequence[int], batch: int = 1):
     """({fused iterations: microseconds per launch}, measured?)"""
     ext = (ctypes.c_int32 * MAX_DIM)(*(list(extent) +
                                         [1] * (MAX_DIM - len(extent))))
     ns = (ctypes.c_float * self.plan.num_passes)()
     measured = ctypes.c_int32(0)
-    check(self._lib.soda_hip_program_pass_times(self._handle, ext, ns,
-                                                ctypes.byref(measured)),
+    check(self._lib.soda_hip_program_pass_times_batch(self._handle, ext, batch,
+                                                      ns,
+                                                      ctypes.byref(measured)),
           'pass_times')
     return ({p.fused_iters: v / 1e3
              for p, v in zip(self.module.sorted_passes(), ns)},
             bool(measured.value))
 
-  def schedule(self, extent: Sequence[int], iterate: int) -> Dict[int, int]:
-    """{fused iterations of a pass: launches} for `iterate` iterations."""
+  def schedule(self, extent: Sequence[int], iterate: int,
+               batch: int = 1) -> Dict[int, int]:
+    """{fused iterations of a pass: launches} for `iterate` iterations (on
+    `batch` grids per launch)."""
     ext = (ctypes.c_int32 * MAX_DIM)(*(list(extent) +
                                         [1] * (MAX_DIM - len(extent))))
     count = (ctypes.c_int32 * self.plan.num_passes)()
-    check(self._lib.soda_hip_program_schedule(self._handle, ext, iterate,
-                                              count), 'schedule')
+    check(self._lib.soda_hip_program_schedule_batch(self._handle, ext, batch,
+                                                    iterate, count),
+          'schedule')
     return {p.fused_iters: c
             for p, c in zip(self.module.sorted_passes(), count) if c}
 
@@ -992,7 +1046,8 @@ class Program:
                  keep: Optional[Sequence[int]] = None,
                  ghosts: Optional[Sequence[int]] = None,
                  sends: Optional[Sequence[int]] = None,
-                 ghosts_ready: int = 0, sendable: int = 0) -> None:
+                 ghosts_ready: int = 0, sendable: int = 0,
+                 batch: Optional[int] = None) -> None:
     """`outputs` / `inputs` are device addresses (e.g. tensor.data_ptr()) of
     dense dim-0-fastest arrays; asynchronous on `stream`.  `inputs` holds the
     input tensors followed by the program's `param` arrays (C order).  For a
@@ -1010,7 +1065,13 @@ class Program:
     on another stream is writing, complete when the hipEvent_t `ghosts_ready`
     fires; `sends` = (lo, hi) rows at either end of the kept range the
     neighbours fetch next, complete when `sendable` (recorded by this call)
-    fires."""
+    fires.
+    `batch` = N: every input and output holds N independent grids of `extent`,
+    one behind the other like a contiguous [N, ...] array (the param arrays
+    are shared), and one launch per kernel runs them all
+    (soda_hip_run_device_batch).  Needs a program built with
+    LowerOptions.batch; not together with `keep` / `ghosts` / `sends` /
+    `origin`."""
     st = self.stencil
     iterate = st.iterate if iterate is None else iterate
     self._check_extent(extent)
@@ -1020,6 +1081,19 @@ class Program:
     outs = (ctypes.c_void_p * len(outputs))(*outputs)
     ins = (ctypes.c_void_p * len(inputs))(*inputs)
     ext = (ctypes.c_int32 * len(extent))(*extent)
+    if batch is not None:
+      if keep is not None or ghosts is not None or sends is not None or \
+          origin is not None or global_extent is not None or ghosts_ready or \
+          sendable:
+        raise util.InputError(
+            'run_device: a batched run is a run on whole grids: no keep / '
+            'ghosts / sends / origin')
+      check(
+          self._lib.soda_hip_run_device_batch(self._handle, outs, ins, ext,
+                                              int(batch), iterate,
+                                              ctypes.c_void_p(stream)),
+          'running `%s` on a batch of %d' % (st.app_name, batch))
+      return
     org = (ctypes.c_int32 * len(extent))(*(origin or [0] * len(extent)))
     gext = (ctypes.c_int32 * len(extent))(*(global_extent or extent))
     if ghosts is not None or sends is not None or ghosts_ready or sendable:
@@ -1139,6 +1213,72 @@ class Program:
     check(
         self._lib.soda_hip_run_host_box(self._handle, ins, outs, iterate, vlo,
                                         vhi), 'running `%s`' % st.app_name)
+    return result
+
+  def run_batch(self, inputs: Dict[str, 'numpy.ndarray'],
+                iterate: Optional[int] = None) -> Dict[str, 'numpy.ndarray']:
+    """`run` on N independent grids in one launch per kernel: numpy arrays of
+    shape (N,) + extent reversed in, the same out; params as in `run`, shared
+    by all items.  A plain allocate / copy in / run_device(batch=N) / copy out
+    through the library's own memory calls (not the banded host path).  Like
+    `run`, the outputs start as zeros and only each item's valid box is
+    written.  Needs a program built with LowerOptions.batch."""
+    import numpy as np
+    st = self.stencil
+    lib = self._lib
+    iterate = st.iterate if iterate is None else iterate
+    first = np.asarray(inputs[st.input_names[0]])
+    if first.ndim != st.dim + 1 or first.shape[0] < 1:
+      raise util.InputError('run_batch: arrays of shape (N,) + extent[::-1]')
+    batch = int(first.shape[0])
+    extent = tuple(first.shape[:0:-1])
+    self._check_extent(extent)
+    host_in = []
+    for n, t in zip(st.input_names, st.input_types):
+      arr = np.ascontiguousarray(inputs[n])
+      if arr.dtype != np.dtype(t.np_name):
+        raise util.InputError('expected dtype %s, got %s' % (t.np_name,
+                                                             arr.dtype))
+      if arr.shape != first.shape:
+        raise util.InputError('all tensors must share one shape')
+      host_in.append(arr)
+    for pstmt in st.param_stmts:        # param arrays follow, C order
+      arr = np.ascontiguousarray(inputs[pstmt.name]).reshape(-1)
+      if arr.dtype != np.dtype(pstmt.haoda_type.np_name) or \
+          arr.size != st.param_elems(pstmt):
+        raise util.InputError('param %s must be %d x %s' % (
+            pstmt.name, st.param_elems(pstmt), pstmt.haoda_type.np_name))
+      host_in.append(arr)
+    dense = [np.empty(first.shape, dtype=np.dtype(t.np_name))
+             for t in st.output_types]
+    dev_in, dev_out = [], []
+    try:
+      for arr in host_in:
+        ptr = ctypes.c_void_p()
+        check(lib.soda_hip_malloc(self.device, arr.nbytes, ctypes.byref(ptr)),
+              'run_batch: allocating an input')
+        dev_in.append(ptr)
+        check(lib.soda_hip_memcpy_h2d(ptr, arr.ctypes.data, arr.nbytes, None),
+              'run_batch: copy in')
+      for arr in dense:
+        ptr = ctypes.c_void_p()
+        check(lib.soda_hip_malloc(self.device, arr.nbytes, ctypes.byref(ptr)),
+              'run_batch: allocating an output')
+        dev_out.append(ptr)
+      self.run_device([p.value for p in dev_out], [p.value for p in dev_in],
+                      extent, iterate, batch=batch)
+      for arr, ptr in zip(dense, dev_out):
+        check(lib.soda_hip_memcpy_d2h(arr.ctypes.data, ptr, arr.nbytes, None),
+              'run_batch: copy out')
+    finally:
+      for ptr in dev_in + dev_out:
+        lib.soda_hip_free(self.device, ptr)
+    result = {}
+    for n, arr in zip(st.output_names, dense):
+      lo, hi = clipped_box(st.valid_box(extent, n, iterate), extent)
+      box = (slice(None),) + tuple(slice(l, h) for l, h in zip(lo, hi))[::-1]
+      result[n] = np.zeros_like(arr)
+      result[n][box] = arr[box]
     return result
 
 
