@@ -419,8 +419,9 @@ def _inputs(stencil, extent, seed=0, kind='random'):
       out[name] = rng.random(shape, dtype=np.float64).astype(dt)
     elif dt.kind == 'i':
       # signed cells stay small: i32 of SEAM_PROGRAMS grows at most 2.5 times
-      # an iteration, 13 iterations from 1000 stay below 2^31 (signed overflow
-      # is undefined in the C both sides are written in)
+      # an iteration, 13 iterations from 1000 stay below 2^31, so these cases
+      # never wrap.  (Overflow is defined, -fwrapv on both sides: cells of the
+      # whole int32 range run in tests/test_values.py.)
       out[name] = rng.integers(-1000, 1001, size=shape,
                                dtype=np.int64).astype(dt)
     else:
