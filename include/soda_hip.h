@@ -275,7 +275,30 @@ int soda_hip_program_destroy(soda_hip_program_t* program);
  * by the program and reused across calls.  `inputs` holds the num_inputs
  * tensors followed by the num_params param arrays (device pointers to
  * param_elems[k] elements each), the order of the reference's operator
- * signature (frt/host.py:72-78: inputs, outputs, then params). */
+ * signature (frt/host.py:72-78: inputs, outputs, then params).
+ *
+ * The device entry contract -- two preconditions on the caller's addresses,
+ * checked by every run entry below before anything is launched
+ * (SODA_HIP_ERR_INVALID, last_error ends in "nothing was launched"):
+ *   overlap    no output shares a byte with an input, a param array or
+ *              another output, each tensor taken as the dense array of
+ *              `extent` (of `batch` such arrays).  Inputs may share.
+ *   alignment  every input and output starts on a multiple of
+ *              min(16, vec x its cell size) bytes, `vec` being the largest
+ *              kernel_desc.vec of the plan (cells per lane; 0 counts as 1); a
+ *              param array on a multiple of its cell size.  Kernels move a
+ *              tensor in fragments of `vec` cells, one instruction of up to
+ *              16 bytes each; extent[0] is a multiple of `vec`
+ *              (soda_hip_plan_geometry refuses any other), so every row,
+ *              plane, kept row range and slab window starts on a fragment
+ *              boundary iff the array does.  A program built for a row length
+ *              that is not a multiple of 16 bytes has a smaller `vec` and
+ *              asks for less: 4 bytes for an odd number of float cells.
+ * What the hardware would make of a misaligned fragment is not measured
+ * anywhere; the library never launches on one.  Inside these rules a run
+ * writes no byte outside its output arrays and reads none outside its inputs
+ * and param arrays (tests/test_device_entry.py runs every kernel family
+ * between guard bands). */
 /* Same, for arrays that are a window of a larger grid (one GPU's slab):
  * `origin` = global position of cell 0 of the arrays, `global_extent` = size
  * of the whole grid (NULL, NULL = the arrays are the grid).  Only programs
@@ -296,8 +319,9 @@ int soda_hip_run_device_window(soda_hip_program_t* program,
  * are unspecified -- NOT "unchanged": the last pass still stores up to
  * fused_iters x reach rows on either side of [keep_lo, keep_hi), computed with
  * zeros where the launch ended, and leaves the rows beyond those as they
- * were, so a caller that reuses the output arrays sees a mix of stale and
- * wrong rows there.  A side with keep_lo = 0 (keep_hi = extent) is never
+ * were (no pass before the last one writes the outputs of such a run: they
+ * alternate between temporaries of the program), so a caller that reuses the
+ * output arrays sees a mix of stale and wrong rows there.  A side with keep_lo = 0 (keep_hi = extent) is never
  * trimmed.  The reference has no counterpart: its host tiles with a
  * replicated halo and recomputes all of it (frt/host.py:124-128). */
 int soda_hip_run_device_cone(soda_hip_program_t* program,

@@ -311,6 +311,7 @@ int soda_hip_program_create(const void* code, size_t code_size,
   p->auto_calibrate = !getenv("SODA_HIP_NO_CALIBRATE");
   p->locals.resize(plan->num_locals);
   p->temps.resize(plan->num_outputs);
+  p->temps2.resize(plan->num_outputs);
   p->host_in.resize(plan->num_inputs);
   p->host_prm.resize(plan->num_params);
   p->host_out.resize(plan->num_outputs);
@@ -321,8 +322,8 @@ int soda_hip_program_create(const void* code, size_t code_size,
 int soda_hip_program_destroy(soda_hip_program_t* p) {
   if (!p) return SODA_HIP_OK;
   (void)hipSetDevice(p->device);
-  for (auto* v : {&p->locals, &p->temps, &p->host_in, &p->host_out,
-                  &p->host_prm})
+  for (auto* v : {&p->locals, &p->temps, &p->temps2, &p->host_in,
+                  &p->host_out, &p->host_prm})
     for (auto& b : *v)
       if (b.ptr) (void)hipFree(b.ptr);
   for (int i = 0; i < 2; ++i) {
@@ -934,12 +935,44 @@ int run_core(soda_hip_program_t* p, void* const* outputs,
     if (!inputs[i]) return fail(SODA_HIP_ERR_INVALID, "run_device: NULL input");
   for (int i = 0; i < plan.num_outputs; ++i)
     if (!outputs[i]) return fail(SODA_HIP_ERR_INVALID, "run_device: NULL output");
-  for (int o = 0; o < plan.num_outputs; ++o)
-    for (int i = 0; i < plan.num_inputs; ++i)
-      if (outputs[o] == inputs[i])
-        return fail(SODA_HIP_ERR_INVALID,
-                    "run_device: an output aliases an input (in-place runs are "
-                    "not supported: inputs are read while outputs are written)");
+  // The caller's addresses: no output may share a byte with an input, a
+  // param array or another output (passes read their inputs while they write
+  // their outputs, and ping-pong through the outputs), each tensor taken as
+  // the dense array of `extent` -- `batch` of them -- that the kernels address.
+  if (!p->bank_tensors) {
+    const int out0 = plan.num_inputs;
+    const int prm0 = out0 + plan.num_outputs + plan.num_locals;
+    auto bytes_of = [&](int slot) {
+      return (uint64_t)cells * (uint64_t)batch * (uint64_t)plan.elem_size[slot];
+    };
+    auto overlap = [](const void* a, uint64_t na, const void* b, uint64_t nb) {
+      const uintptr_t a0 = reinterpret_cast<uintptr_t>(a);
+      const uintptr_t b0 = reinterpret_cast<uintptr_t>(b);
+      return a0 < b0 + nb && b0 < a0 + na;
+    };
+    for (int o = 0; o < plan.num_outputs; ++o) {
+      for (int i = 0; i < plan.num_inputs; ++i)
+        if (overlap(outputs[o], bytes_of(out0 + o), inputs[i], bytes_of(i)))
+          return fail(SODA_HIP_ERR_INVALID,
+                      std::string("run_device: an output ") +
+                          (outputs[o] == inputs[i] ? "aliases" : "overlaps") +
+                          " an input (in-place runs are not supported: inputs "
+                          "are read while outputs are written); nothing was "
+                          "launched");
+      for (int k = 0; k < plan.num_params; ++k)
+        if (overlap(outputs[o], bytes_of(out0 + o),
+                    inputs[plan.num_inputs + k],
+                    (uint64_t)plan.param_elems[k] * plan.elem_size[prm0 + k]))
+          return fail(SODA_HIP_ERR_INVALID,
+                      "run_device: an output overlaps a param array; nothing "
+                      "was launched");
+      for (int q = 0; q < o; ++q)
+        if (overlap(outputs[o], bytes_of(out0 + o), outputs[q],
+                    bytes_of(out0 + q)))
+          return fail(SODA_HIP_ERR_INVALID,
+                      "run_device: two outputs overlap; nothing was launched");
+    }
+  }
 
   // schedule: the multiset of passes that adds up to `iterate` at least total
   // cost (100 iterations with passes of 12 / 8 / 4 / 1: 7 x 12 + 2 x 8 beats
@@ -947,6 +980,44 @@ int run_core(soda_hip_program_t* p, void* const* outputs,
   // next...  Remembered per (extent, iterate).
   const ExtentPlan* ep = nullptr;
   if (int rc = extent_plan(plan, &extents, base.extent, &ep, batch)) return rc;
+  // ... and their alignment (behind the geometry, which has made sure that
+  // the row length is a multiple of every kernel's cells per lane: a row, a
+  // plane, a slab window or a band then starts on a fragment boundary iff the
+  // array does).  A kernel moves a tensor in fragments of `vec` cells, with
+  // one instruction of up to 16 bytes each -- marching and tile3d kernels
+  // through buffer resources (soda_rt.h soda_buf_load_frag /
+  // soda_buf_store_frag), direct and ldswin kernels through vector pointers
+  // (soda_load_frag / soda_store_frag; ldswin's quads are four 4-byte cells)
+  // -- so every tensor must be aligned to min(16, vec x its cell size) for
+  // the widest `vec` of the plan; param arrays are read cell by cell.
+  if (!p->bank_tensors) {
+    int32_t vec = 1;
+    for (int k = 0; k < plan.num_kernels; ++k)
+      if (plan.kernels[k].vec > vec) vec = plan.kernels[k].vec;
+    const int out0 = plan.num_inputs;
+    const int prm0 = out0 + plan.num_outputs + plan.num_locals;
+    char buf[256];
+    for (int t = 0; t < plan.num_inputs + plan.num_outputs + plan.num_params;
+         ++t) {
+      const bool prm = t >= plan.num_inputs + plan.num_outputs;
+      const int k = t - plan.num_inputs - plan.num_outputs;
+      const void* ptr = prm ? inputs[plan.num_inputs + k]
+                            : t < out0 ? inputs[t] : outputs[t - out0];
+      const int64_t elem = plan.elem_size[prm ? prm0 + k : t];
+      int64_t align = prm ? elem : (int64_t)vec * elem;
+      if (align > 16) align = 16;
+      if (align > 1 && reinterpret_cast<uintptr_t>(ptr) % (uintptr_t)align) {
+        snprintf(buf, sizeof buf,
+                 "run_device: %s %d at %p is not aligned to %d bytes (%d cells "
+                 "per lane x %d-byte cells, at most 16; params: one cell); "
+                 "nothing was launched",
+                 prm ? "param array" : t < out0 ? "input" : "output",
+                 prm ? k : t < out0 ? t : t - out0, ptr, (int)align,
+                 prm ? 1 : (int)vec, (int)elem);
+        return fail(SODA_HIP_ERR_INVALID, buf);
+      }
+    }
+  }
   int32_t count[SODA_HIP_MAX_PASSES];
   int32_t total = 0;
   if (force_pass >= 0) {
@@ -1030,11 +1101,20 @@ int run_core(soda_hip_program_t* p, void* const* outputs,
     if (rc) return rc;
     base.buf[loc0 + l] = p->locals[l].ptr;
   }
+  // A run that trims its passes to a cone promises to leave the rows of the
+  // caller's outputs beyond the LAST pass's reach as they were (soda_hip.h,
+  // soda_hip_run_device_cone).  The earlier passes cover more rows than the
+  // last one, so with three passes or more they may not ping-pong through
+  // the caller's outputs: they alternate between two temporaries instead.
+  const bool own_pingpong =
+      cone && total > 2 &&
+      (cone->keep_lo > 0 || cone->keep_hi < base.extent[plan.dim - 1]);
   if (total > 1)
     for (int o = 0; o < plan.num_outputs; ++o) {
-      int rc = ensure(p->temps[o],
-                      (size_t)cells * batch * plan.elem_size[out0 + o]);
-      if (rc) return rc;
+      const size_t bytes = (size_t)cells * batch * plan.elem_size[out0 + o];
+      if (int rc = ensure(p->temps[o], bytes)) return rc;
+      if (own_pingpong)
+        if (int rc = ensure(p->temps2[o], bytes)) return rc;
     }
 
   std::vector<PassLaunch> launches;
@@ -1056,8 +1136,13 @@ int run_core(soda_hip_program_t* p, void* const* outputs,
     bool to_out = ((total - 1 - (int)done) % 2) == 0;
     for (int j = 0; j < plan.num_inputs; ++j)
       base.buf[in0 + j] = const_cast<void*>(src[j]);
+    const bool last_pass = (int)done + 1 == total;
     for (int o = 0; o < plan.num_outputs; ++o)
-      base.buf[out0 + o] = to_out ? outputs[o] : p->temps[o].ptr;
+      base.buf[out0 + o] = !own_pingpong ? (to_out ? outputs[o]
+                                                   : p->temps[o].ptr)
+                           : last_pass   ? outputs[o]
+                           : to_out      ? p->temps2[o].ptr
+                                         : p->temps[o].ptr;
     soda_hip_kargs_t args = base;
     if (L.lo > 0 || L.hi < rows) {
       args.extent[ax] = L.hi - L.lo;
@@ -1576,6 +1661,8 @@ int soda_hip_stream_create(const soda_hip_stream_desc_t* desc,
   s->unwire.resize(desc->num_inputs, nullptr);
   for (int i = 0; unwire && i < desc->num_inputs; ++i) s->unwire[i] = unwire[i];
   s->wire.assign(wire, wire + desc->num_outputs);
+  for (soda_hip_program* c : s->unwire) if (c) c->bank_tensors = true;
+  for (soda_hip_program* c : s->wire) if (c) c->bank_tensors = true;
   s->dense_in.resize(desc->num_inputs);
   s->dense_out.resize(desc->num_outputs);
   *stream = s;
@@ -1642,6 +1729,7 @@ int soda_hip_stream_set_banked(soda_hip_stream_t* s, soda_hip_program_t* program
                 "stream_set_banked: not the one-launch banked form of this "
                 "stream's program");
   s->banked = program;
+  program->bank_tensors = true;
   s->banked_first = s->banked_last = nullptr;
   s->in_kernel.assign(in_kernel, in_kernel + d.num_inputs + d.num_outputs);
   // one source for both paths of this stream: which launches a run takes is
@@ -1683,6 +1771,7 @@ int soda_hip_stream_set_banked_pair(soda_hip_stream_t* s,
                   "stream_set_banked_pair: input and output cell sizes differ");
   s->banked_first = first;
   s->banked_last = last;
+  first->bank_tensors = last->bank_tensors = true;
   s->banked_tmp.resize(d.num_outputs);
   return SODA_HIP_OK;
 }

@@ -91,6 +91,9 @@ struct soda_hip_program {
   std::vector<hipFunction_t> functions;
   std::vector<soda_detail::DeviceBuffer> locals;   // one per local tensor
   std::vector<soda_detail::DeviceBuffer> temps;    // one per output: ping-pong
+  // ... and its partner in runs trimmed to a cone, which keep their
+  // intermediate passes out of the caller's outputs (run_core)
+  std::vector<soda_detail::DeviceBuffer> temps2;
   std::vector<soda_detail::DeviceBuffer> host_in;  // run_host staging
   std::vector<soda_detail::DeviceBuffer> host_prm; // ... of the param arrays
   std::vector<soda_detail::DeviceBuffer> host_out;
@@ -109,6 +112,13 @@ struct soda_hip_program {
   // kargs.reserved[0] of every launch: the length of the wire stream a banked
   // program runs on (soda_hip_stream_set_banked), 0 for every other program
   int32_t stream_elems = 0;
+  // a wire stream's copy kernel or banked program (soda_hip_stream_create,
+  // soda_hip_stream_set_banked[_pair]): its tensors are banks -- a fraction of
+  // `extent` cells long, at any address, the kernels pick their access width
+  // from it -- so run_core's overlap and alignment rules, which take every
+  // tensor as one dense array of `extent`, do not apply; the stream layer
+  // checks what it hands over itself
+  bool bank_tensors = false;
   // time every pass on an extent the first time it is run (a few ms, once):
   // on unless SODA_HIP_NO_CALIBRATE is set or the caller turns it off
   bool auto_calibrate = true;

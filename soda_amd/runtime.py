@@ -1050,7 +1050,16 @@ class Program:
                  batch: Optional[int] = None) -> None:
     """`outputs` / `inputs` are device addresses (e.g. tensor.data_ptr()) of
     dense dim-0-fastest arrays; asynchronous on `stream`.  `inputs` holds the
-    input tensors followed by the program's `param` arrays (C order).  For a
+    input tensors followed by the program's `param` arrays (C order).
+    The addresses must keep the device entry contract (include/soda_hip.h):
+    no output overlaps an input, a param array or another output, and every
+    input and output is aligned to min(16, vec x cell size) bytes -- `vec` the
+    widest cells-per-lane of the module's kernels (tune['vec'], follows
+    extent[0]: 4 float cells and 16 bytes where the row length allows, one cell
+    and 4 bytes for an odd one) -- a param array to its cell size.  A call that
+    breaks either is refused (BackendError, "nothing was launched"); a view or
+    slice of a torch tensor has to be checked against this, `.contiguous()` is
+    not enough for one that starts mid-row.  For a
     slab of a larger grid pass where its cell 0 sits (`origin`) and the size of
     the whole grid (`global_extent`): `border: preserve` means the GLOBAL border.
     `keep` = (lo, hi): only cells [lo, hi) along the last dimension of the
