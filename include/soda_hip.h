@@ -33,7 +33,8 @@
  * a launch plan.  Plain C types only; no C++ or torch types cross this ABI.
  * The library is synchronous per call unless a stream is given; it is not
  * re-entrant per program handle (the reference promises none either: single
- * host thread, frt/host.py:319-322).
+ * host thread, frt/host.py:319-322) -- on the GPU too: one handle is one queue
+ * of work, see "Streams, scratch, graphs" at soda_hip_run_device.
  *
  * Result contract (reference docs/data-layout.md:12-25, frt/host.py:357-375):
  * only cells inside the valid box of each output are defined; everything else
@@ -59,7 +60,8 @@ extern "C" {
  * soda_hip_stream_set_banked / _set_banked_pair (kargs.reserved[0] carries
  * the stream length to their programs); and
  * soda_hip_stream_create accepts wire[o] == NULL for an output on one bank
- * that the program stores at its wire position itself. */
+ * that the program stores at its wire position itself.  Added under 8:
+ * soda_hip_program_scratch. */
 #define SODA_HIP_ABI_VERSION 8
 #define SODA_HIP_MAX_DIM 4
 #define SODA_HIP_MAX_TENSORS 16
@@ -298,7 +300,45 @@ int soda_hip_program_destroy(soda_hip_program_t* program);
  * anywhere; the library never launches on one.  Inside these rules a run
  * writes no byte outside its output arrays and reads none outside its inputs
  * and param arrays (tests/test_device_entry.py runs every kernel family
- * between guard bands). */
+ * between guard bands).
+ *
+ * Streams, scratch, graphs -- what "asynchronous on `stream`" means for every
+ * soda_hip_run_device* entry and for soda_hip_stream_run_device
+ * (tests/test_async.py runs them on a live stream, ahead of their inputs):
+ *   ordering   every kernel, fill and copy pass of a call is enqueued on
+ *              `stream`, in order; nothing goes to the default stream.  The
+ *              one exception, the side stream of a split pass
+ *              (SODA_HIP_SPLIT=side), forks from `stream` and joins it again
+ *              by events inside the call: whatever follows the call on
+ *              `stream` sees all of its results.
+ *   blocking   two kinds of call wait for the GPU and are NOT asynchronous:
+ *              the first run of more than one iteration on an extent of a
+ *              program that calibrates by itself (below), and a call that
+ *              grows the program's scratch -- the ping-pong temporaries, the
+ *              locals, a stream object's staging arrays: a larger extent, a
+ *              larger batch, the first trimmed run of three passes or more.
+ *              Growing allocates, and where it replaces a buffer it first
+ *              waits for the whole device: earlier calls may still use it.
+ *              Scratch never shrinks (soda_hip_program_scratch tells).
+ *   one queue  a handle is one queue of work: its scratch is shared by all of
+ *              its calls.  Calls on ONE stream need nothing; a call on another
+ *              stream must be ordered behind the handle's earlier calls by
+ *              the caller (an event), and two streams may not run one handle
+ *              at the same time.  Handles are independent of each other.
+ *   graphs     a call on a stream that is being captured never calibrates and
+ *              never allocates: if its scratch would have to grow it returns
+ *              SODA_HIP_ERR_INVALID before anything is launched or allocated,
+ *              and the capture stays valid.  The recipe: run the call once
+ *              eagerly with the same extent, iterate, batch and keep range
+ *              (soda_hip_program_calibrate first, if the clock is to pick the
+ *              schedule), then capture.  The graph holds the addresses of
+ *              the program's scratch: it may be replayed until a later call
+ *              on the handle grows that scratch, or the handle is destroyed
+ *              -- replaying it after that uses freed memory.  Eager calls
+ *              that fit the scratch may run between replays, ordered against
+ *              them like any two calls.  Runs that are handed events
+ *              (soda_hip_run_device_slab) and group runs are not meant for
+ *              capture. */
 /* Same, for arrays that are a window of a larger grid (one GPU's slab):
  * `origin` = global position of cell 0 of the arrays, `global_extent` = size
  * of the whole grid (NULL, NULL = the arrays are the grid).  Only programs
@@ -560,6 +600,12 @@ int soda_hip_last_launches(soda_hip_program_t* program, int32_t* launches,
 /* Passes of the last run that were launched in two parts (boundary chunks /
  * interior) around a halo exchange. */
 int soda_hip_last_split(soda_hip_program_t* program, int32_t* passes);
+/* Device bytes of scratch the program holds now (locals, ping-pong
+ * temporaries) and how many times a call has replaced one of these buffers by
+ * a larger one so far -- each time a call that waited for the device.  Either
+ * may be NULL. */
+int soda_hip_program_scratch(soda_hip_program_t* program, int64_t* bytes,
+                             int32_t* regrown);
 
 /* -- one host thread, N GPUs: a grid cut into slabs -------------------------
  * The reference's host is one blocking C++ sequence on one device

@@ -15,6 +15,7 @@
 
 #include <hip/hiprtc.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -44,13 +45,39 @@ int hip_fail(hipError_t e, const char* what) {
 int ensure(DeviceBuffer& b, size_t bytes) {
   if (b.bytes >= bytes && b.ptr) return SODA_HIP_OK;
   if (b.ptr) {
+    // Earlier asynchronous calls on the handle may still be reading or writing
+    // the old buffer on any stream: wait for the device before it goes.  That
+    // hipFree waits too is nothing the HIP documentation promises; regrowth is
+    // rare and pays for a hipMalloc anyway.
+    HIP_TRY(hipDeviceSynchronize());
     HIP_TRY(hipFree(b.ptr));
     b.ptr = nullptr;
     b.bytes = 0;
+    ++b.regrown;
   }
   HIP_TRY(hipMalloc(&b.ptr, bytes));
   b.bytes = bytes;
   return SODA_HIP_OK;
+}
+
+bool too_small(const DeviceBuffer& b, size_t bytes) {
+  return !b.ptr || b.bytes < bytes;
+}
+
+int refuse_growth_while_capturing(void* stream, const char* who) {
+  hipStreamCaptureStatus capture = hipStreamCaptureStatusNone;
+  if (hipStreamIsCapturing(static_cast<hipStream_t>(stream), &capture) !=
+      hipSuccess) {
+    (void)hipGetLastError();
+    return SODA_HIP_OK;
+  }
+  if (capture == hipStreamCaptureStatusNone) return SODA_HIP_OK;
+  return fail(SODA_HIP_ERR_INVALID,
+              std::string(who) +
+                  ": scratch buffers must grow for this call and the stream is "
+                  "being captured into a graph, where allocating is illegal; "
+                  "run the same call once eagerly before the capture; nothing "
+                  "was launched");
 }
 
 }  // namespace soda_detail
@@ -875,12 +902,11 @@ int plan_launches(const soda_hip_plan_t& plan,
 // ms with the boundary part on a stream of its own (SODA_HIP_SPLIT=side: the
 // parts then share the GPU, but two hand-overs between hardware queues cost
 // more than that buys).
+// (read per split pass, not once per process: a host may switch between runs,
+// and tests/test_async.py runs both orders in one process)
 static bool split_in_order() {
-  static const int mode = [] {
-    const char* v = getenv("SODA_HIP_SPLIT");
-    return v && !strcmp(v, "side") ? 0 : 1;
-  }();
-  return mode == 1;
+  const char* v = getenv("SODA_HIP_SPLIT");
+  return !(v && !strcmp(v, "side"));
 }
 
 // the stream and events of split passes, made on first use
@@ -892,6 +918,35 @@ static int side_stream(soda_hip_program* p) {
     HIP_TRY(hipEventCreateWithFlags(&p->ev_bnd[i], hipEventDisableTiming));
   }
   return SODA_HIP_OK;
+}
+
+// scratch for the local tensors is needed only if a scheduled pass keeps them
+// in memory (marching kernels hold them in registers)
+static bool locals_in_memory(const soda_hip_plan_t& plan, const int32_t* count) {
+  for (int i = 0; i < plan.num_passes; ++i)
+    for (int k = 0; count[i] && k < plan.passes[i].num_kernels; ++k)
+      if (plan.kernels[plan.passes[i].kernel[k]].march_dim == 0) return true;
+  return false;
+}
+
+// Would a run of `total` launches on `cells` x `batch` cells allocate: the
+// locals, the ping-pong temporaries, their partners of a trimmed run?
+static bool scratch_grows(const soda_hip_program* p, bool need_locals,
+                          int32_t total, bool own_pingpong, int64_t cells,
+                          int32_t batch) {
+  const soda_hip_plan_t& plan = p->plan;
+  const int out0 = plan.num_inputs, loc0 = out0 + plan.num_outputs;
+  for (int l = 0; need_locals && l < plan.num_locals; ++l)
+    if (too_small(p->locals[l],
+                  (size_t)cells * batch * plan.elem_size[loc0 + l]))
+      return true;
+  for (int o = 0; total > 1 && o < plan.num_outputs; ++o) {
+    const size_t bytes = (size_t)cells * batch * plan.elem_size[out0 + o];
+    if (too_small(p->temps[o], bytes) ||
+        (own_pingpong && too_small(p->temps2[o], bytes)))
+      return true;
+  }
+  return false;
 }
 
 int run_core(soda_hip_program_t* p, void* const* outputs,
@@ -1088,19 +1143,7 @@ int run_core(soda_hip_program_t* p, void* const* outputs,
     base.buf[prm0 + k] = const_cast<void*>(inputs[plan.num_inputs + k]);
   // scratch for the local tensors -- only if a scheduled pass keeps them in
   // memory (marching kernels hold them in registers)
-  bool need_locals = false;
-  for (int i = 0; i < plan.num_passes; ++i)
-    for (int k = 0; count[i] && k < plan.passes[i].num_kernels; ++k)
-      need_locals = need_locals ||
-                    plan.kernels[plan.passes[i].kernel[k]].march_dim == 0;
-  // (all of it for the whole batch: item i of a local or a temporary lies i
-  // grids behind its start, like the caller's tensors; a larger batch regrows)
-  for (int l = 0; need_locals && l < plan.num_locals; ++l) {
-    int rc = ensure(p->locals[l],
-                    (size_t)cells * batch * plan.elem_size[loc0 + l]);
-    if (rc) return rc;
-    base.buf[loc0 + l] = p->locals[l].ptr;
-  }
+  const bool need_locals = locals_in_memory(plan, count);
   // A run that trims its passes to a cone promises to leave the rows of the
   // caller's outputs beyond the LAST pass's reach as they were (soda_hip.h,
   // soda_hip_run_device_cone).  The earlier passes cover more rows than the
@@ -1109,6 +1152,20 @@ int run_core(soda_hip_program_t* p, void* const* outputs,
   const bool own_pingpong =
       cone && total > 2 &&
       (cone->keep_lo > 0 || cone->keep_hi < base.extent[plan.dim - 1]);
+  // Growing scratch allocates and synchronises (ensure): illegal on a stream
+  // that is being captured.  Known here, before the first launch; the stream
+  // is asked only when something must grow.
+  if (scratch_grows(p, need_locals, total, own_pingpong, cells, batch))
+    if (int rc = refuse_growth_while_capturing(stream_, "run_device"))
+      return rc;
+  // (all of it for the whole batch: item i of a local or a temporary lies i
+  // grids behind its start, like the caller's tensors; a larger batch regrows)
+  for (int l = 0; need_locals && l < plan.num_locals; ++l) {
+    int rc = ensure(p->locals[l],
+                    (size_t)cells * batch * plan.elem_size[loc0 + l]);
+    if (rc) return rc;
+    base.buf[loc0 + l] = p->locals[l].ptr;
+  }
   if (total > 1)
     for (int o = 0; o < plan.num_outputs; ++o) {
       const size_t bytes = (size_t)cells * batch * plan.elem_size[out0 + o];
@@ -1579,6 +1636,24 @@ int soda_hip_last_rows(soda_hip_program_t* p, int64_t* rows) {
   return SODA_HIP_OK;
 }
 
+static void add_scratch(const std::vector<DeviceBuffer>& bufs, int64_t* bytes,
+                        int32_t* regrown) {
+  for (const DeviceBuffer& b : bufs) {
+    if (bytes && b.ptr) *bytes += (int64_t)b.bytes;
+    if (regrown) *regrown += b.regrown;
+  }
+}
+
+int soda_hip_program_scratch(soda_hip_program_t* p, int64_t* bytes,
+                             int32_t* regrown) {
+  if (!p) return fail(SODA_HIP_ERR_INVALID, "NULL program");
+  if (bytes) *bytes = 0;
+  if (regrown) *regrown = 0;
+  for (const auto* v : {&p->locals, &p->temps, &p->temps2})
+    add_scratch(*v, bytes, regrown);
+  return SODA_HIP_OK;
+}
+
 // -- wire format: <app>_kernel on banked streams -------------------------------
 
 struct soda_hip_stream {
@@ -1614,6 +1689,11 @@ struct soda_hip_stream {
   soda_hip_program* banked_first = nullptr;
   soda_hip_program* banked_last = nullptr;
   std::vector<DeviceBuffer> banked_tmp;
+  // (stream length, banked launches) of the device runs that went through:
+  // the staging arrays and the scratch of every program such a call runs are
+  // in place, a repeat allocates nothing and skips the look-ahead
+  // (stream_grows).  Emptied by whatever changes the path a length takes.
+  std::vector<std::pair<int32_t, int>> warm;
 };
 
 int soda_hip_stream_create(const soda_hip_stream_desc_t* desc,
@@ -1685,12 +1765,14 @@ int soda_hip_stream_set_device_dense_min_tile(soda_hip_stream_t* s,
   if (!s || min_tile0 < 0)
     return fail(SODA_HIP_ERR_INVALID, "stream_set_device_dense_min_tile");
   s->device_dense_min_tile0 = min_tile0;
+  s->warm.clear();
   return SODA_HIP_OK;
 }
 
 int soda_hip_stream_set_banked(soda_hip_stream_t* s, soda_hip_program_t* program,
                                const int32_t* in_kernel) {
   if (!s) return fail(SODA_HIP_ERR_INVALID, "stream_set_banked: NULL stream");
+  s->warm.clear();
   if (!program) {
     s->banked = s->banked_first = s->banked_last = nullptr;
     s->in_kernel.clear();
@@ -1745,6 +1827,7 @@ int soda_hip_stream_set_banked_pair(soda_hip_stream_t* s,
   if (!s || !s->banked)
     return fail(SODA_HIP_ERR_INVALID,
                 "stream_set_banked_pair: no banked program is set");
+  s->warm.clear();
   if (!first && !last) {
     s->banked_first = s->banked_last = nullptr;
     return SODA_HIP_OK;
@@ -1859,6 +1942,63 @@ static int banked_launches(soda_hip_stream* s, void* const* out_banks,
   return SODA_HIP_OK;
 }
 
+// Would a plain run of `iterate` iterations on `ext` grow the scratch of `p`?
+// By the schedule run_core itself would take on a capturing stream (measured
+// times where there are any, never a calibration).
+static int program_grows(soda_hip_program* p, const int32_t* ext,
+                         int32_t iterate, bool* grows) {
+  int32_t count[SODA_HIP_MAX_PASSES];
+  if (int rc = soda_hip_program_schedule(p, ext, iterate, count)) return rc;
+  int32_t total = 0;
+  int64_t cells = 1;
+  for (int i = 0; i < p->plan.num_passes; ++i) total += count[i];
+  for (int d = 0; d < p->plan.dim; ++d) cells *= ext[d];
+  if (scratch_grows(p, locals_in_memory(p->plan, count), total, false, cells, 1))
+    *grows = true;
+  return SODA_HIP_OK;
+}
+
+// The look-ahead of soda_hip_stream_run_device: its ensure() calls lie between
+// its launches, so whether this call allocates anything -- a staging array, the
+// temporary of the two-launch banked form, scratch of a program it runs -- is
+// worked out here, before the first of them, following the same decisions.
+static int stream_grows(soda_hip_stream* s, int32_t n, int banked,
+                        const int32_t* bext, bool* grows) {
+  const soda_hip_stream_desc_t& d = s->desc;
+  const int32_t* kern = banked ? s->in_kernel.data() : nullptr;
+  const int32_t ext1[1] = {n};
+  *grows = false;
+  for (int i = 0; i < d.num_inputs; ++i) {
+    if ((kern && kern[i]) || (d.banks[i] == 1 && d.shift[i] == 0)) continue;
+    if (too_small(s->dense_in[i], (size_t)n * d.elem_size[i])) *grows = true;
+    if (int rc = program_grows(s->unwire[i], ext1, 1, grows)) return rc;
+  }
+  for (int o = 0; o < d.num_outputs; ++o) {
+    if ((kern && kern[d.num_inputs + o]) || !s->wire[o]) continue;
+    if (too_small(s->dense_out[o], (size_t)n * d.elem_size[d.num_inputs + o]))
+      *grows = true;
+    if (int rc = program_grows(s->wire[o], ext1, 1, grows)) return rc;
+  }
+  if (banked == 2) {
+    for (int o = 0; o < d.num_outputs; ++o)
+      if (too_small(s->banked_tmp[o], (size_t)n * d.elem_size[d.num_inputs + o]))
+        *grows = true;
+    if (int rc = program_grows(s->banked_first, bext, 1, grows)) return rc;
+    return program_grows(s->banked_last, bext, 1, grows);
+  }
+  if (banked == 1) return program_grows(s->banked, bext, 1, grows);
+  int32_t ext[SODA_HIP_MAX_DIM];
+  if (d.tile[0] >= s->device_dense_min_tile0 && dense_view(s, n, ext)) {
+    const int rc = program_grows(s->dense, ext, d.iterate, grows);
+    if (rc != SODA_HIP_ERR_INVALID) return rc;
+    // INVALID: this extent does not suit the dense kernels; the call goes linear
+  }
+  int pick = d.num_linear - 1;
+  for (int k = 0; k < d.num_linear; ++k)
+    if (n % d.linear_vec[k] == 0) { pick = k; break; }
+  return program_grows(s->linear[pick], ext1, d.iterate, grows);
+}
+
 int soda_hip_stream_run_device(soda_hip_stream_t* s, void* const* out_banks,
                                const void* const* in_banks,
                                uint64_t coalesced_data_num, void* hip_stream) {
@@ -1880,6 +2020,18 @@ int soda_hip_stream_run_device(soda_hip_stream_t* s, void* const* out_banks,
     if (int rc = banked_launches(s, out_banks, in_banks, n, bext, &banked))
       return rc;
   const int32_t* kern = banked ? s->in_kernel.data() : nullptr;
+  // A length that has not run this way before may allocate.  On a stream that
+  // is being captured that is refused here, before the first launch (whatever
+  // else is wrong with the call is found and said below, as ever).
+  const std::pair<int32_t, int> key(n, banked);
+  const bool warm =
+      std::find(s->warm.begin(), s->warm.end(), key) != s->warm.end();
+  if (!warm) {
+    bool grows = false;
+    if (stream_grows(s, n, banked, bext, &grows) == SODA_HIP_OK && grows)
+      if (int rc = refuse_growth_while_capturing(hip_stream, "stream_run"))
+        return rc;
+  }
   // 1. un-interleave (and un-delay) the inputs
   std::vector<const void*> din;     // one entry per tensor, NB per in_kernel one
   int bank0 = 0;
@@ -1996,6 +2148,10 @@ int soda_hip_stream_run_device(soda_hip_stream_t* s, void* const* out_banks,
     if (int rc = soda_hip_run_device(s->wire[o], out_banks + bank0, ins, ext1, 1,
                                      hip_stream))
       return rc;
+  }
+  if (!warm) {
+    if (s->warm.size() >= 64) s->warm.clear();
+    s->warm.push_back(key);
   }
   return SODA_HIP_OK;
 }

@@ -29,8 +29,16 @@ int hip_fail(hipError_t e, const char* what);
 struct DeviceBuffer {
   void* ptr = nullptr;
   size_t bytes = 0;
+  int32_t regrown = 0;   // times ensure() replaced it by a larger one
 };
+// At least `bytes` behind b.ptr.  Replacing a buffer synchronises the device
+// first: work in flight may still use the old one.
 int ensure(DeviceBuffer& b, size_t bytes);
+bool too_small(const DeviceBuffer& b, size_t bytes);   // would ensure() allocate?
+// SODA_HIP_ERR_INVALID ("... nothing was launched") if `stream` is being
+// captured into a graph: asked only by a call that found a buffer too_small,
+// before its first launch
+int refuse_growth_while_capturing(void* stream, const char* who);
 
 typedef std::array<int32_t, SODA_HIP_MAX_DIM> ExtentKey;
 

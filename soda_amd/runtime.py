@@ -221,6 +221,9 @@ API = {
     ]),
     'soda_hip_last_rows': (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_int64)]),
     'soda_hip_last_split': (ctypes.c_int, [_vp, _pi32]),
+    'soda_hip_program_scratch': (ctypes.c_int, [
+        _vp, ctypes.POINTER(ctypes.c_int64), _pi32
+    ]),
     'soda_hip_group_create': (ctypes.c_int, [
         _vp, ctypes.c_size_t, ctypes.POINTER(Plan), ctypes.POINTER(GroupDesc),
         _pvp
@@ -1080,7 +1083,25 @@ class Program:
     are shared), and one launch per kernel runs them all
     (soda_hip_run_device_batch).  Needs a program built with
     LowerOptions.batch; not together with `keep` / `ghosts` / `sends` /
-    `origin`."""
+    `origin`.
+    Streams, scratch, graphs (include/soda_hip.h has the full text): every
+    kernel, fill and copy of a call is enqueued on `stream`, in order, and the
+    side stream of a split pass joins it again inside the call.  Two kinds of
+    call wait for the GPU: the first run of more than one iteration on an
+    extent of a program that calibrates by itself (`calibrate=None`), and a
+    call that grows the program's scratch -- a larger extent or batch, the
+    first `keep` run of three passes or more (`scratch()` tells).  A Program
+    is one queue of work: calls on one stream need nothing, a call on another
+    stream has to be ordered behind the earlier ones by the caller (an event),
+    and two streams may not run one Program at once.  Under
+    `torch.cuda.graph` a call never calibrates and never allocates; if scratch
+    would have to grow it is refused (BackendError, "nothing was launched")
+    and the capture stays valid.  So: run the call once eagerly with the same
+    extent, iterate, batch and keep range -- `calibrate()` first if the clock
+    is to pick the schedule -- then capture.  The graph holds the addresses of
+    the scratch: replay it only until a later call grows that scratch or the
+    Program is closed.  Runs with `ghosts_ready` / `sendable` are not meant
+    for capture."""
     st = self.stencil
     iterate = st.iterate if iterate is None else iterate
     self._check_extent(extent)
@@ -1138,6 +1159,14 @@ class Program:
     check(self._lib.soda_hip_last_split(self._handle, ctypes.byref(n)),
           'last_split')
     return n.value
+
+  def scratch(self):
+    """(device bytes of scratch the program holds, times a call replaced one of
+    its buffers by a larger one -- each a call that waited for the device)."""
+    n, grown = ctypes.c_int64(), ctypes.c_int32()
+    check(self._lib.soda_hip_program_scratch(self._handle, ctypes.byref(n),
+                                             ctypes.byref(grown)), 'scratch')
+    return n.value, grown.value
 
   def last_rows(self) -> int:
     """Cells along the last dimension the passes of the last run covered,
