@@ -61,8 +61,11 @@ extern "C" {
  * the stream length to their programs); and
  * soda_hip_stream_create accepts wire[o] == NULL for an output on one bank
  * that the program stores at its wire position itself.  Added under 8:
- * soda_hip_program_scratch. */
-#define SODA_HIP_ABI_VERSION 8
+ * soda_hip_program_scratch.  9: the residual of a run's last iteration -- the
+ * kernel descriptor names its twin, the plan carries `residual`, with
+ * soda_hip_run_device_residual / _until, soda_hip_plan_residual_box and
+ * soda_hip_last_residual. */
+#define SODA_HIP_ABI_VERSION 9
 #define SODA_HIP_MAX_DIM 4
 #define SODA_HIP_MAX_TENSORS 16
 #define SODA_HIP_MAX_KERNELS 32
@@ -70,6 +73,8 @@ extern "C" {
 #define SODA_HIP_MAX_PASS_KERNELS 16
 #define SODA_HIP_MAX_PARAMS 8
 #define SODA_HIP_NAME_LEN 96
+#define SODA_HIP_MAX_RES_PAIRS 8       /* input / output pairs of a residual */
+#define SODA_HIP_RES_NONE (-(1 << 30)) /* residual plan: no dependence */
 
 enum soda_hip_status {
   SODA_HIP_OK = 0,
@@ -156,7 +161,71 @@ typedef struct soda_hip_kernel_desc {
                                           whole row (its waves hand x-halos
                                           over through LDS): extent[0] must not
                                           exceed this, else ERR_INVALID */
+  int32_t twin;                        /* ABI 9, plans with a residual only:
+                                          index of this kernel's twin -- the
+                                          same kernel, same stores, which also
+                                          takes the residual of its last fused
+                                          iteration: `k(soda_hip_kargs_t a,
+                                          soda_hip_residual_t* r,
+                                          soda_hip_resbox_t box)` -- or -1 */
 } soda_hip_kernel_desc_t;
+
+/* The residual of the last iteration of a run of N iterations: how much that
+ * iteration changed the grid.  32 device bytes.
+ *   pairs   every output o pairs with the input i it replaces, by position
+ *           (under `border: preserve`: the input it keeps its border from).
+ *           `cur` is o after N iterations; `prev` is that input as the last
+ *           iteration saw it: o after N - 1 iterations, or the caller's input
+ *           when N = 1.
+ *   cells   o's valid box after N iterations (the whole array under `border:
+ *           preserve`).
+ *   delta   per cell, in the cell type's own arithmetic.  float and double:
+ *           fabs(cur - prev), one IEEE operation in the cell's precision.
+ *           Integers up to 32 bits: |cur - prev| exactly, in 64 bits.  int64
+ *           and uint64: the unsigned 64-bit absolute difference.
+ * All four fields are sums or maxima of exact per-cell values, taken over all
+ * pairs: no reduction order can change them. */
+typedef struct soda_hip_residual {
+  uint64_t changed;          /* cells whose delta is non-zero or NaN; +0
+                                against -0 is unchanged */
+  uint64_t unordered;        /* cells whose delta is NaN (a NaN cell, or
+                                inf - inf): counted in `changed`, left out of
+                                the maxima */
+  uint64_t max_float_bits;   /* bit pattern of the largest float delta as a
+                                double (an fp32 delta widens exactly; for
+                                non-negative non-NaN values the pattern orders
+                                like the value; +inf is an ordinary value) */
+  uint64_t max_int;          /* largest integer delta */
+} soda_hip_residual_t;
+
+/* Third argument of a residual kernel: the cells counted, [lo, hi) per pair
+ * and dimension of the arrays the launch addresses. */
+typedef struct soda_hip_resbox {
+  int32_t lo[SODA_HIP_MAX_RES_PAIRS][SODA_HIP_MAX_DIM];
+  int32_t hi[SODA_HIP_MAX_RES_PAIRS][SODA_HIP_MAX_DIM];
+} soda_hip_resbox_t;
+
+/* What a plan says about residuals (plan.residual.present != 0: the program
+ * was built with LowerOptions.residual / sodac --hip-residual).  `kernel` is
+ * `<app>_residual(kargs, r, box)`: dense cur (output slots) against dense prev
+ * (input slots), launched on a whole number of rows' worth of blocks.  The rest lets the library
+ * find every output's valid box after N iterations without the program text:
+ * one iteration maps the bounds of its inputs' windows to its outputs',
+ *   lo(o) = min(base_lo[o], min over i of dep_lo[o][i] + min(lo(i), 0))
+ * per dimension, `hi` alike with max (SODA_HIP_RES_NONE: o does not read i);
+ * N rounds from zero windows give the window of N iterations, the box is the
+ * array less that window.  whole != 0 (`border: preserve`): the whole array. */
+typedef struct soda_hip_residual_plan {
+  int32_t present;
+  int32_t kernel;
+  int32_t zero_kernel;   /* `<app>_residual_zero(soda_hip_residual_t* r)`: one
+                            block of 64 threads zeroes the struct */
+  int32_t whole;
+  int32_t base_lo[SODA_HIP_MAX_RES_PAIRS][SODA_HIP_MAX_DIM];
+  int32_t base_hi[SODA_HIP_MAX_RES_PAIRS][SODA_HIP_MAX_DIM];
+  int32_t dep_lo[SODA_HIP_MAX_RES_PAIRS][SODA_HIP_MAX_RES_PAIRS][SODA_HIP_MAX_DIM];
+  int32_t dep_hi[SODA_HIP_MAX_RES_PAIRS][SODA_HIP_MAX_RES_PAIRS][SODA_HIP_MAX_DIM];
+} soda_hip_residual_plan_t;
 
 /* One way of advancing the program by `fused_iters` iterations: the listed
  * kernels launched in order (one fused kernel, or one kernel per stage). */
@@ -208,6 +277,9 @@ typedef struct soda_hip_plan {
    * launched on (blocks, batch, 1).  Only such a plan runs through
    * soda_hip_run_device_batch; every other entry runs it as a batch of 1. */
   int32_t batched;
+  /* ABI 9: the residual kernels of the plan.  Kernels named here or as a
+   * `twin` belong to no pass. */
+  soda_hip_residual_plan_t residual;
 } soda_hip_plan_t;
 
 typedef struct soda_hip_program soda_hip_program_t;   /* opaque */
@@ -223,7 +295,8 @@ int soda_hip_device_count(int* count);
 /* sizeof() of the ABI structs as this library was compiled, for bindings to
  * check their mirrors: 0 kargs, 1 kernel_desc, 2 pass_desc, 3 plan,
  * 4 host_tensor, 5 stream_desc, 6 slab_run, 7 group_desc, 8 slab_info,
- * 9 group_stats, 10 launch_info; 0 for anything else. */
+ * 9 group_stats, 10 launch_info, 11 residual, 12 resbox; 0 for anything
+ * else. */
 size_t soda_hip_sizeof(int which);
 
 /* -- JIT: HIP source text -> gfx950 code object (hiprtc; needs no GPU) ---- */
@@ -461,6 +534,61 @@ int soda_hip_run_device_batch(soda_hip_program_t* program,
                               void* const* outputs, const void* const* inputs,
                               const int32_t* extent, int32_t batch,
                               int32_t iterate, void* stream);
+
+/* soda_hip_run_device that also tells how much the LAST of the `iterate`
+ * iterations changed the grid: the soda_hip_residual_t defined above is left
+ * in the caller's 32 device bytes `residual_dev` (8-byte aligned, no byte
+ * shared with an output).  Same contract checks, same guard behaviour, inputs
+ * are never written.  Asynchronous on `stream` under "Streams, scratch,
+ * graphs": the struct is zeroed by a small kernel of the program enqueued on
+ * `stream` inside the call, nothing waits on the host, and the call can be captured once an eager
+ * call has sized the scratch -- every replay zeroes and refills the struct.
+ * The passes are the multiset soda_hip_run_device would launch; only their
+ * order may differ: a scheduled pass whose kernel has a twin goes last and is
+ * launched as its twin (the deepest such pass).  If no scheduled pass has
+ * one -- `direct`, `ldswin`, `tile3d` passes, a marching depth whose twin did
+ * not fit -- or SODA_HIP_RESIDUAL_GENERIC=1 is set (A/B runs), the run ends in
+ * the one-iteration pass, taken out of a deeper pass's count if the schedule
+ * had none (iterate - 1 iterations are scheduled, one is added), followed by
+ * `<app>_residual` over the outputs and that pass's inputs.
+ * SODA_HIP_ERR_UNSUPPORTED, nothing launched: a program built without
+ * `residual`.  Windows, cones, slabs, groups and batches are not served. */
+int soda_hip_run_device_residual(soda_hip_program_t* program,
+                                 void* const* outputs,
+                                 const void* const* inputs,
+                                 const int32_t* extent, int32_t iterate,
+                                 void* residual_dev, void* stream);
+/* Iterates until converged.  SYNCHRONOUS: advances `check_every` iterations at
+ * a time through the entry above (the last chunk may be shorter), after each
+ * chunk fetches the 32 bytes and waits for them, and stops when
+ *   unordered == 0 && max_float <= tol && max_int <= int_tol
+ * or when `max_iterate` iterations are done.  SODA_HIP_OK either way;
+ * *iterations_done and *result_host (either may be NULL) tell which.  The
+ * struct is that of the last iteration done, its cells the valid box after
+ * ALL iterations done so far.  Chunks ping-pong between the caller's outputs
+ * and scratch of the program (soda_hip_program_scratch counts it); the
+ * caller's inputs are read by the first chunk only and never written; the
+ * final iterate ends up in `outputs`, by one device copy per output if it
+ * landed in scratch. */
+int soda_hip_run_device_until(soda_hip_program_t* program,
+                              void* const* outputs, const void* const* inputs,
+                              const int32_t* extent, int32_t max_iterate,
+                              int32_t check_every, double tol,
+                              uint64_t int_tol,
+                              soda_hip_residual_t* result_host,
+                              int32_t* iterations_done, void* stream);
+/* The cells a residual over `iterate` iterations on `extent` counts: [lo, hi)
+ * per output and dimension (num_outputs x dim values each), clipped to the
+ * array.  Pure function of the plan (no GPU). */
+int soda_hip_plan_residual_box(const soda_hip_plan_t* plan,
+                               const int32_t* extent, int32_t iterate,
+                               int32_t* lo, int32_t* hi);
+/* How the last soda_hip_run_device_residual call of the program took its
+ * residual: 0 not at all, 1 in the twin of its last pass, 2 by
+ * `<app>_residual`; *fused_iters (may be NULL): the fusion depth of that last
+ * pass. */
+int soda_hip_last_residual(soda_hip_program_t* program, int32_t* mode,
+                           int32_t* fused_iters);
 
 /* Replaces soda::app::<app>(): host arrays described by (ptr, extent, stride,
  * min) per tensor, inputs then outputs; copies in, runs, copies the outputs

@@ -83,6 +83,22 @@ def add_arguments(parser) -> None:
                       help='batched kernels (names end in _bt): a launch runs '
                       'many independent grids of one extent, blockIdx.y is '
                       'the item (soda_hip_run_device_batch)')
+  parser.add_argument('--hip-residual', action='store_true',
+                      dest='hip_residual',
+                      help='residual kernels: twins of the marching kernels '
+                      '(names end in _rs) and <app>_residual, which report how '
+                      'much the last iteration of a run changed the grid '
+                      '(soda_hip_run_device_residual / _until)')
+  parser.add_argument('--hip-until', type=float, dest='hip_until',
+                      default=None, metavar='TOL',
+                      help='--hip-backend: iterate until the largest change of '
+                      'a cell in one iteration is <= TOL (at most `iterate` '
+                      'iterations); implies --hip-residual; prints the '
+                      'iterations and the residual')
+  parser.add_argument('--hip-check-every', type=int, dest='hip_check_every',
+                      default=8, metavar='K',
+                      help='with --hip-until: iterations between two looks at '
+                      'the residual (default 8)')
   parser.add_argument('--hip-nt-store', action='store_true',
                       dest='hip_nt_store',
                       help='non-temporal instead of plain output stores')
@@ -126,7 +142,10 @@ def options_from_args(args: argparse.Namespace) -> lower.LowerOptions:
                             xcd_swizzle=not args.hip_no_xcd_swizzle,
                             pipe=args.hip_pipe,
                             xshare_block=args.hip_xshare_block,
-                            batch=bool(getattr(args, 'hip_batch', False)))
+                            batch=bool(getattr(args, 'hip_batch', False)),
+                            residual=bool(
+                                getattr(args, 'hip_residual', False) or
+                                getattr(args, 'hip_until', None) is not None))
 
 
 def print_code(stencil: core.Stencil, args: argparse.Namespace) -> None:
@@ -220,7 +239,16 @@ def run(stencil: core.Stencil, args: argparse.Namespace) -> None:
     prog = runtime.Program(stencil, options_from_args(args),
                            device=args.hip_device, extent=extent)
     t0 = time.time()
-    outputs = prog.run(inputs)
+    if getattr(args, 'hip_until', None) is not None:
+      outputs, done, res = prog.run_until(
+          inputs, args.hip_until, stencil.iterate,
+          check_every=max(1, int(args.hip_check_every)))
+      extra = {'until': args.hip_until, 'iterations': done,
+               'residual': {'changed': res.changed, 'unordered': res.unordered,
+                            'max_float': res.max_float,
+                            'max_int': res.max_int}}
+    else:
+      outputs = prog.run(inputs)
     seconds = time.time() - t0
   cells = float(np.prod(extent)) * stencil.iterate
   print(json.dumps({

@@ -64,6 +64,8 @@ def emit_plan(w, func: str, plan) -> None:
     for field in ('step_ns', 'warm_saved', 'bytes_per_cell',
                   'lane_redundancy'):
       w('  plan.kernels[%d].%s = %rf;' % (i, field, float(getattr(d, field))))
+    if plan.residual.present:
+      w('  plan.kernels[%d].twin = %d;' % (i, d.twin))
   w('  plan.num_passes = %d;' % plan.num_passes)
   for i in range(plan.num_passes):
     p = plan.passes[i]
@@ -74,6 +76,19 @@ def emit_plan(w, func: str, plan) -> None:
       w('  plan.passes[%d].kernel[%d] = %d;' % (i, j, p.kernel[j]))
   for field in ('has_reach', 'reach_lo', 'reach_hi', 'batched'):
     w('  plan.%s = %d;' % (field, getattr(plan, field)))
+  if plan.residual.present:     # (twins are read only where this is set)
+    r = plan.residual
+    for field in ('present', 'kernel', 'zero_kernel', 'whole'):
+      w('  plan.residual.%s = %d;' % (field, getattr(r, field)))
+    for o in range(plan.num_outputs):
+      for d in range(4):
+        w('  plan.residual.base_lo[%d][%d] = %d;' % (o, d, r.base_lo[o][d]))
+        w('  plan.residual.base_hi[%d][%d] = %d;' % (o, d, r.base_hi[o][d]))
+        for i in range(plan.num_inputs):
+          w('  plan.residual.dep_lo[%d][%d][%d] = %d;' %
+            (o, i, d, r.dep_lo[o][i][d]))
+          w('  plan.residual.dep_hi[%d][%d][%d] = %d;' %
+            (o, i, d, r.dep_hi[o][i][d]))
   w('  return plan;')
   w('}')
 

@@ -54,6 +54,7 @@ from soda_amd import core, util
 
 from soda_amd.codegen.hip.module import (KernelDesc, Module, PassDesc,  # noqa: F401
                                          _check_native, runtime_text)
+from soda_amd.codegen.hip import residual
 from soda_amd.codegen.hip.direct import DIRECT_BLOCK, add_direct_pass  # noqa: F401
 from soda_amd.codegen.hip.ldswin import (add_ldswin_pass,  # noqa: F401
                                          ldswin_candidate, ldswin_pays,
@@ -61,7 +62,8 @@ from soda_amd.codegen.hip.ldswin import (add_ldswin_pass,  # noqa: F401
 from soda_amd.codegen.hip.march import (LANE_SHIFTS, MAX_FUSE_3D,  # noqa: F401
                                         MAX_FUSE_PRESERVE, MAX_SHIFT_TEMPS,
                                         MAX_UNROLL, REG_BUDGET, MarchConfig,
-                                        add_march_pass, default_vec,
+                                        add_march_pass, add_march_twin,
+                                        default_vec,
                                         march_supported)
 from soda_amd.codegen.hip.tile3d import (add_tile3d_pass,  # noqa: F401
                                          tile3d_supported)
@@ -180,6 +182,14 @@ class LowerOptions:
   # 1).  For callers and A/B runs: `auto` never sets it, no environment
   # override.  Not with `banks`
   batch: bool = False
+  # residual of a run's last iteration (residual.py): every
+  # default kernel is emitted unchanged; beside the marching kernels come
+  # twins (`_rs`) that take |cur - prev| of the last fused iteration where they
+  # store, and every module gets `<app>_residual` for the families and depths
+  # without one (soda_hip_run_device_residual / _until).  For callers: `auto`
+  # never sets it, no environment override.  Iterable programs only; not with
+  # `batch`, not with `banks`
+  residual: bool = False
 
   def __post_init__(self):
     self.fuse = tuple(self.fuse)
@@ -305,6 +315,8 @@ def lower(stencil: core.Stencil, opts: Optional[LowerOptions] = None) -> Module:
     raise util.SemanticError(
         'batch: the wire format has no batch, `banks` cannot be combined with '
         'it')
+  if opts.residual:
+    residual.check_options(stencil, opts.batch, opts.banks)
   _check_native(stencil)
   stencil.check_preserve()
   if opts.banks and opts.strategy not in ('auto', 'march'):
@@ -352,10 +364,12 @@ def lower(stencil: core.Stencil, opts: Optional[LowerOptions] = None) -> Module:
       if opts.banks:
         raise util.SemanticError(
             'banks: `ldswin` kernels read and write dense arrays')
-      mod = Module(whole, batch=opts.batch)
+      mod = Module(whole, batch=opts.batch, residual=opts.residual)
       try:
         add_ldswin_pass(mod, chunk=opts.chunk_rows or 64,
                         step=opts.waves_y if opts.waves_y > 1 else None)
+        if opts.residual:
+          residual.add_residual_kernel(mod)
         return mod
       except util.SemanticError:
         # the ring does not fit LDS (window too tall / too wide): only an
@@ -390,7 +404,7 @@ def lower(stencil: core.Stencil, opts: Optional[LowerOptions] = None) -> Module:
   # the same bits (exact.py; the program as written unless one is enabled)
   from soda_amd.codegen.hip import exact
   stencil = exact.specialize(stencil)
-  mod = Module(stencil, opts.banks, opts.batch)
+  mod = Module(stencil, opts.banks, opts.batch, opts.residual)
   use_march = opts.strategy in ('auto', 'march', 'tile3d') and \
       march_supported(stencil) is None
   if opts.strategy == 'march' and not use_march:
@@ -540,8 +554,13 @@ def lower(stencil: core.Stencil, opts: Optional[LowerOptions] = None) -> Module:
           forms = [(0, 0)]
         for xs, xb in forms:
           try:
-            add_march_pass(mod, config(t, vec, opts.prefetch or None,
-                                       xshare=xs, xshare_block=xb))
+            cfg = config(t, vec, opts.prefetch or None, xshare=xs,
+                         xshare_block=xb)
+            add_march_pass(mod, cfg)
+            if opts.residual:
+              # (a form or depth whose twin does not fit has none: the
+              # library then ends such a run in `<app>_residual`)
+              add_march_twin(mod, cfg)
             break
           except util.SemanticError:
             # this shape does not fit: try without sharing; if the depth does
@@ -553,13 +572,18 @@ def lower(stencil: core.Stencil, opts: Optional[LowerOptions] = None) -> Module:
       if (share or seg) and opts.xshare:
         keep = (len(mod.kernels), len(mod.passes), len(mod.chunks))
         try:
-          add_march_pass(mod, config(1, vec, pf1, rows1, xshare=share,
-                                     xshare_block=seg))
+          cfg = config(1, vec, pf1, rows1, xshare=share, xshare_block=seg)
+          add_march_pass(mod, cfg)
+          if opts.residual:
+            add_march_twin(mod, cfg)
           done1 = True
         except util.SemanticError:
           del mod.kernels[keep[0]:], mod.passes[keep[1]:], mod.chunks[keep[2]:]
       if not done1:
-        add_march_pass(mod, config(1, vec, pf1, rows1))
+        cfg = config(1, vec, pf1, rows1)
+        add_march_pass(mod, cfg)
+        if opts.residual:
+          add_march_twin(mod, cfg)
   if not use_march:
     if opts.banks:
       raise util.SemanticError(
@@ -588,5 +612,7 @@ def lower(stencil: core.Stencil, opts: Optional[LowerOptions] = None) -> Module:
       raise refusal or util.SemanticError(
           'tile3d: no fusion depth of 2 or more to build (iterate %d, fuse %s)'
           % (stencil.iterate, list(opts.fuse)))
+  if opts.residual:
+    residual.add_residual_kernel(mod)
   return mod
 

@@ -42,6 +42,10 @@ class _Node:
     # on cells one iteration cannot compute (it is then also a parent, tapped
     # at offset 0)
     self.keep: Optional[str] = None
+    # residual twins: DSL name of the input this output of the LAST fused
+    # iteration replaces -- a parent tapped at offset 0, like `keep` (and the
+    # same tensor where both are set), for |cur - prev| where it is stored
+    self.prev: Optional[str] = None
     # x-halo sharing: the strip's neighbours hand this tensor's end cells over
     # through LDS (one register per row slot holds them, like edge loads)
     self.xs = False
@@ -58,7 +62,7 @@ class _Node:
       lo, hi = self.stage.tap_bounds(pname)
     else:
       lo, hi = (0,) * dim, (0,) * dim
-    if pname == self.keep:
+    if pname == self.keep or pname == self.prev:
       lo = tuple(min(0, v) for v in lo)
       hi = tuple(max(0, v) for v in hi)
     return lo, hi
@@ -107,7 +111,14 @@ class MarchConfig:
                xwindow: bool = True, slide: bool = True,
                xshare_block: int = 0,
                banks: Optional[Dict[str, int]] = None,
-               bank_lead: Optional[Dict[str, int]] = None):
+               bank_lead: Optional[Dict[str, int]] = None,
+               residual: bool = False):
+    # the kernel's twin (LowerOptions.residual): same chain, same stores, and
+    # on the last fused level every output is also a consumer of the input it
+    # replaces, at offset 0; the delta is taken where the plane is stored,
+    # under the store's own predicate (_emit_store).  Name: the plain
+    # kernel's + `_rs`
+    self.residual = bool(residual)
     # the banked form of a wire stream's dense program: {input or output: NB}.
     # Such a tensor is not one dense array but NB banks, stream element k in
     # bank k % NB at index k / NB; the kernel addresses every bank through a
@@ -267,7 +278,8 @@ def march_supported(stencil: core.Stencil) -> Optional[str]:
 
 
 def _build_chain(st: core.Stencil, T: int, pf: int, edge: Tuple[int, int],
-                 pipe: int = 1, pipe_rows: int = 1, xshare: bool = False):
+                 pipe: int = 1, pipe_rows: int = 1, xshare: bool = False,
+                 residual: bool = False):
   """The tensors of T chained iterations with their schedule (delay in ticks
   behind the load of the input plane, window of planes kept, invalid margins).
   `pipe` > 1 splits the iterations evenly over that many waves of a block:
@@ -307,6 +319,10 @@ def _build_chain(st: core.Stencil, T: int, pf: int, edge: Tuple[int, int],
       if st.preserve_border and stage.is_output:
         n.keep = st.preserved_from(stage.name)
         n.parents.setdefault(n.keep, env[n.keep])
+      if residual and it == T - 1 and stage.is_output:
+        # (under `border: preserve` the window is there already: `keep`)
+        n.prev = st.input_names[st.output_names.index(stage.name)]
+        n.parents.setdefault(n.prev, env[n.prev])
       env[stage.name] = n
       nodes.append(n)
     last_outputs = {o: env[o] for o in st.output_names}
@@ -493,8 +509,14 @@ class _MarchKernel:
         raise util.SemanticError('march: 1 to 16 waves can share a row')
       if self.dim == 3 and self.cfg.tile_rows > 24:
         raise util.SemanticError('march: x-halo sharing holds a row per lane')
+    if self.cfg.residual and (self.W > 1 or self.seg or self.banks or
+                              self.cfg.waves_x * self.cfg.waves_y != 1):
+      raise util.SemanticError(
+          'march: no residual twin of stage-pipelined blocks, segmented '
+          'x-halo sharing, several waves per block or banked tensors')
     self.nodes, self.inputs, self.outputs = _build_chain(
-        self.st, self.T, self.PF, self.edge, self.W, self.R, bool(self.xs))
+        self.st, self.T, self.PF, self.edge, self.W, self.R, bool(self.xs),
+        self.cfg.residual)
     self.out_nodes = list(self.outputs.values())
     self.margin_lo = max(0, max(n.margin[0] for n in self.out_nodes))
     self.margin_hi = max(0, max(n.margin[1] for n in self.out_nodes))
@@ -511,7 +533,8 @@ class _MarchKernel:
       if (p_lo, p_hi) == (self.lanes_lo, self.lanes_hi):
         self.edge = (0, 0)
         self.nodes, self.inputs, self.outputs = _build_chain(
-            self.st, self.T, self.PF, self.edge, self.W, self.R, bool(self.xs))
+            self.st, self.T, self.PF, self.edge, self.W, self.R, bool(self.xs),
+            self.cfg.residual)
         self.out_nodes = list(self.outputs.values())
     if self.cfg.align_lanes > 1 and self.group == 64:
       spare = (64 - self.lanes_lo - self.lanes_hi) % self.cfg.align_lanes
@@ -641,6 +664,8 @@ class _MarchKernel:
 
     self.kind = 'march%dd' % self.dim
     self.name = '%s_%s_%s' % (self.st.app_name, self.kind, self.cfg.key())
+    if self.cfg.residual:
+      self.name += '_rs'
     self.waves = self.cfg.waves_x * self.cfg.waves_y if self.dim == 2 else 1
     self.wx = self.cfg.waves_x if self.dim == 2 else 1
     if self.W > 1:
@@ -686,6 +711,9 @@ class _MarchKernel:
       self.w('    d[2] = __builtin_amdgcn_s_getreg(63492);   // HW_REG_HW_ID')
       self.w('    d[3] = __builtin_amdgcn_s_getreg(63508);   // HW_REG_XCC_ID')
       self.w('  }')
+    if self.cfg.residual:
+      # one wave reduction and lane 0's atomics, at the end of the kernel
+      self.w('  soda_res_flush(soda_acc, soda_res);')
     self.w('}')
     return self._finish()
 
@@ -715,10 +743,16 @@ class _MarchKernel:
       self.w('//   %-24s delay %2d  window %2d (slots %2d)  margin %d/%d  rows %d/%d' %
         (n.var, n.delay, n.window, n.slots, n.margin[0], n.margin[1],
          n.rmargin[0], n.rmargin[1]))
-    self.w('extern "C" __global__ void __launch_bounds__(%d) %s%s(soda_hip_kargs_t a) {'
+    self.w('extern "C" __global__ void __launch_bounds__(%d) %s%s%s'
       % (self.block, '__attribute__((amdgpu_waves_per_eu(%d, %d))) ' %
          (self.cfg.min_waves, max(self.cfg.min_waves, 8))
-         if self.cfg.min_waves else '', self.name))
+         if self.cfg.min_waves else '', self.name,
+         '(soda_hip_kargs_t a, soda_hip_residual_t* soda_res, '
+         'soda_hip_resbox_t soda_box) {' if self.cfg.residual else
+         '(soda_hip_kargs_t a) {'))
+    if self.cfg.residual:
+      self.w('  soda_res_lane_t soda_acc;  // this lane\'s share of the residual')
+      self.w('  soda_res_init(soda_acc);')
     if self.cfg.stamps:
       self.w('  const unsigned long long soda_t0 = __builtin_amdgcn_s_memtime();')
     self.w('  const int lane = (int)(threadIdx.x & 63u);')
@@ -857,6 +891,13 @@ class _MarchKernel:
       self.w('  const soda_rsrc_t w_%s = soda_make_rsrc((%s*)a.buf[%d] + '
         '(int64_t)m_begin * pitch, (int64_t)(m_end - m_begin) * pitch * %d);' %
         (o, n.ctype, self.mod.slot[o], self.esz[o]))
+    if self.cfg.residual:
+      # the cells of a lane that count: those its stores land (store_ok; a
+      # lane is wholly inside the row or wholly outside) inside the pair's box
+      for p, o in enumerate(self.st.output_names):
+        for e in range(self.V):
+          self.w('  const bool rsx%d_%d = store_ok && x0 + %d >= soda_box.lo[%d][0] '
+                 '&& x0 + %d < soda_box.hi[%d][0];' % (p, e, e, p, e, p))
     if self.xs or self.n_edge:
       self.w('  const bool edge_lane = lane == 0 || lane == 63;')
     self.xs_nodes = [n for n in self.nodes if n.xs]
@@ -1317,7 +1358,7 @@ class _MarchKernel:
                (n.ctype, self.V, n.var, 2 * self.R - 1, j, self.V, n.var,
                 dst_slot, j))
     if n.store_slot is not None:
-      self._emit_store(n, stage.name, dst_slot)
+      self._emit_store(n, stage.name, dst_slot, k)
 
   # -- integer window reductions along dimension 0, all cells of a lane jointly --
   def _xwindow(self, stage):
@@ -1417,13 +1458,39 @@ class _MarchKernel:
             body.append('        %s = (%s)(%s);' % (dst[e], n.ctype, expr))
       body.append('      }')
 
-  def _emit_store(self, n: _Node, oname: str, dst_slot: int) -> None:
+  def _emit_store(self, n: _Node, oname: str, dst_slot: int, k: int) -> None:
     """Stores the new plane of a last-iteration output (rows and lanes that
-    are not this wave's to write are dropped by the addressing)."""
+    are not this wave's to write are dropped by the addressing).  A twin also
+    takes the plane's share of the residual: per cell, the decision the
+    addressing makes implicitly -- the plane is one of the chunk's (m_ok), the
+    row one of the tile's and of the grid's, the lane one that stores
+    (store_ok, in rsx) -- as a boolean, and inside the pair's box.  Chunks,
+    tiles and the storing lanes of strips partition the grid, so a cell
+    counts once whatever overlaps the wave computes."""
     es = self.esz[oname]
     self.w('      {')
     self.w('        const int m = t - %d;' % n.delay)
     self.w('        const bool m_ok = m >= m_begin && m < m_end;')
+    if n.prev is not None:
+      pair = self.st.output_names.index(oname)
+      prev = n.parents[n.prev]
+      pslot = self.slot_of(prev, k, n.delay - prev.fill_delay)
+      self.w('        const bool rs_m = m_ok && m >= soda_box.lo[%d][%d] && m < '
+             'soda_box.hi[%d][%d];' % (pair, self.ax, pair, self.ax))
+      for j in self.store_rows(n):
+        if j < prev.rmargin[0] or j >= self.rows_in - prev.rmargin[1]:
+          raise util.InternalError('march: row %d of %s is not held' %
+                                   (j, prev.var))
+        row = 'rs_m'
+        if self.dim == 3:
+          # (the box lies inside the grid: a row in it is a row that exists)
+          self.w('        const bool rs_r%d = rs_m && y0 + %d >= soda_box.lo[%d][1] '
+                 '&& y0 + %d < soda_box.hi[%d][1];' % (j, j, pair, j, pair))
+          row = 'rs_r%d' % j
+        for e in range(self.V):
+          self.w('        soda_res_add(soda_acc, %s_s%d_r%d[%d], %s_s%d_r%d[%d], '
+                 '%s && rsx%d_%d);' % (n.var, dst_slot, j, e, prev.var, pslot,
+                                      j, e, row, pair, e))
     for j in self.store_rows(n):
       reg = '%s_s%d_r%d' % (n.var, dst_slot, j)
       if oname in self.banks:
@@ -1518,6 +1585,32 @@ class _MarchKernel:
              est_window_regs=self.est_regs))
     self.mod.passes.append(p)
     return p
+
+
+def add_march_twin(mod: Module, cfg: MarchConfig) -> Optional[int]:
+  """Adds the residual twin of the marching kernel `cfg` built last (a kernel,
+  not a pass: the library launches it in place of its plain kernel) and names
+  it in that kernel's descriptor; None, and nothing added, where the form has
+  no twin or the extra window does not fit."""
+  import copy
+  plain = '%s_march%dd_%s' % (mod.stencil.app_name, mod.stencil.dim, cfg.key())
+  owner = [k for k in mod.kernels if k.name == plain]
+  if len(owner) != 1:
+    raise util.InternalError('march: no kernel %s to build a twin of' % plain)
+  twin_cfg = copy.copy(cfg)
+  twin_cfg.residual = True
+  keep = (len(mod.kernels), len(mod.passes), len(mod.chunks))
+  try:
+    p = _MarchKernel(mod, twin_cfg).emit()
+  except util.SemanticError:
+    del mod.kernels[keep[0]:], mod.passes[keep[1]:], mod.chunks[keep[2]:]
+    return None
+  mod.passes.remove(p)
+  owner[0].twin = p.kernels[0]
+  mod.kernels[p.kernels[0]].tune['twin_of'] = plain
+  mod.kernels[p.kernels[0]].tune['est_window_regs'] = \
+      p.traffic_model['est_window_regs']
+  return p.kernels[0]
 
 
 def add_march_pass(mod: Module, cfg: MarchConfig) -> PassDesc:

@@ -55,6 +55,9 @@ class KernelDesc:
     # marching kernels: what the host needs to size the chunk length at load
     # time (axis, waves of a block along it, pipeline warm-up, fixed or not)
     self.tune = tune
+    # LowerOptions.residual: index of the kernel's twin (the same kernel, with
+    # the residual of the last fused iteration taken where it stores), or -1
+    self.twin = -1
 
 
 class PassDesc:
@@ -72,8 +75,14 @@ class Module:
   """HIP source text + plan for one program at one vector width."""
 
   def __init__(self, stencil: core.Stencil,
-               banks: Optional[Dict[str, int]] = None, batch: bool = False):
+               banks: Optional[Dict[str, int]] = None, batch: bool = False,
+               residual: bool = False):
     self.stencil = stencil
+    # LowerOptions.residual: the module also holds `<app>_residual` (its index
+    # in `kernels`; residual.py) and the twins of its marching kernels
+    self.residual = bool(residual)
+    self.residual_kernel = -1
+    self.residual_zero_kernel = -1
     # LowerOptions.batch: every kernel is emitted in its batched form
     # (add_kernel)
     self.batch = bool(batch)
@@ -177,10 +186,11 @@ class Module:
       # no 64-bit arithmetic anywhere: fp32 lane shifts may fold into their
       # consumers (soda_rt.h, soda_lane_shift)
       head += '#define SODA_FOLD_F32_DPP 1\n'
-    from soda_amd.codegen.hip import exact
+    from soda_amd.codegen.hip import exact, residual
     return (head + runtime_text() +
             (banked_runtime_text() if self.banks else '') +
             (batch_runtime_text() if self.batch else '') +
+            (residual.residual_runtime_text() if self.residual else '') +
             exact.helper_text(self.stencil) + '\n' + '\n'.join(self.chunks))
 
   def sorted_passes(self) -> List[PassDesc]:

@@ -139,6 +139,8 @@ size_t soda_hip_sizeof(int which) {
     case 8: return sizeof(soda_hip_slab_info_t);
     case 9: return sizeof(soda_hip_group_stats_t);
     case 10: return sizeof(soda_hip_launch_info_t);
+    case 11: return sizeof(soda_hip_residual_t);
+    case 12: return sizeof(soda_hip_resbox_t);
     default: return 0;
   }
 }
@@ -297,6 +299,34 @@ static int check_plan(const soda_hip_plan_t* p) {
     return fail(SODA_HIP_ERR_INVALID, "plan: last pass must advance 1 iteration");
   if (p->has_reach && (p->reach_lo < 0 || p->reach_hi < 0))
     return fail(SODA_HIP_ERR_INVALID, "plan: negative reach");
+  if (p->residual.present) {
+    // residual kernels belong to no pass; twins are read only here
+    if (p->num_inputs != p->num_outputs ||
+        p->num_outputs > SODA_HIP_MAX_RES_PAIRS || p->batched)
+      return fail(SODA_HIP_ERR_INVALID,
+                  "plan: a residual needs as many outputs as inputs, at most "
+                  "SODA_HIP_MAX_RES_PAIRS, and no batch");
+    if (p->residual.kernel < 0 || p->residual.kernel >= p->num_kernels ||
+        p->residual.zero_kernel < 0 ||
+        p->residual.zero_kernel >= p->num_kernels ||
+        p->residual.zero_kernel == p->residual.kernel)
+      return fail(SODA_HIP_ERR_INVALID, "plan: bad residual kernel index");
+    for (int k = 0; k < p->num_kernels; ++k)
+      if (p->kernels[k].twin < -1 || p->kernels[k].twin >= p->num_kernels ||
+          p->kernels[k].twin == k)
+        return fail(SODA_HIP_ERR_INVALID, "plan: bad twin index");
+    for (int i = 0; i < p->num_passes; ++i)
+      for (int k = 0; k < p->passes[i].num_kernels; ++k) {
+        const int kk = p->passes[i].kernel[k];
+        if (kk == p->residual.kernel || kk == p->residual.zero_kernel)
+          return fail(SODA_HIP_ERR_INVALID,
+                      "plan: the residual kernel belongs to no pass");
+        for (int q = 0; q < p->num_kernels; ++q)
+          if (p->kernels[q].twin == kk)
+            return fail(SODA_HIP_ERR_INVALID,
+                        "plan: a twin belongs to no pass");
+      }
+  }
   return SODA_HIP_OK;
 }
 
@@ -339,6 +369,7 @@ int soda_hip_program_create(const void* code, size_t code_size,
   p->locals.resize(plan->num_locals);
   p->temps.resize(plan->num_outputs);
   p->temps2.resize(plan->num_outputs);
+  p->until_tmp.resize(plan->num_outputs);
   p->host_in.resize(plan->num_inputs);
   p->host_prm.resize(plan->num_params);
   p->host_out.resize(plan->num_outputs);
@@ -349,10 +380,11 @@ int soda_hip_program_create(const void* code, size_t code_size,
 int soda_hip_program_destroy(soda_hip_program_t* p) {
   if (!p) return SODA_HIP_OK;
   (void)hipSetDevice(p->device);
-  for (auto* v : {&p->locals, &p->temps, &p->temps2, &p->host_in,
-                  &p->host_out, &p->host_prm})
+  for (auto* v : {&p->locals, &p->temps, &p->temps2, &p->until_tmp,
+                  &p->host_in, &p->host_out, &p->host_prm})
     for (auto& b : *v)
       if (b.ptr) (void)hipFree(b.ptr);
+  if (p->until_res.ptr) (void)hipFree(p->until_res.ptr);
   for (int i = 0; i < 2; ++i) {
     if (p->ev_pre[i]) (void)hipEventDestroy(p->ev_pre[i]);
     if (p->ev_bnd[i]) (void)hipEventDestroy(p->ev_bnd[i]);
@@ -640,11 +672,24 @@ struct TileRange {
   int32_t skip_from, skip_count, count;
 };
 
+// a residual kernel's arguments: `k(soda_hip_kargs_t a, soda_hip_residual_t* r,
+// soda_hip_resbox_t box)`, laid out as the kernel-argument segment lays them
+// out (each at its natural alignment: 8, 8, 4)
+struct ResidualArgs {
+  soda_hip_kargs_t a;
+  void* r;
+  soda_hip_resbox_t box;
+};
+
+// res_dev != nullptr: kernel k is a twin and takes the residual arguments
 int launch(soda_hip_program* p, int k, const soda_hip_kargs_t& base,
            const int32_t* tile, hipStream_t stream,
-           const TileRange* range = nullptr, int32_t batch = 1) {
+           const TileRange* range = nullptr, int32_t batch = 1,
+           void* res_dev = nullptr, const soda_hip_resbox_t* box = nullptr) {
   const soda_hip_kernel_desc_t& d = p->plan.kernels[k];
-  soda_hip_kargs_t args = base;
+  ResidualArgs all;
+  soda_hip_kargs_t& args = all.a;
+  args = base;
   int64_t blocks = 1;
   for (int i = 0; i < SODA_HIP_MAX_DIM; ++i) {
     int32_t t = i < p->plan.dim ? tile[i] : 1;
@@ -658,7 +703,12 @@ int launch(soda_hip_program* p, int k, const soda_hip_kargs_t& base,
   if (blocks < 1 || blocks > 0x7fffffffLL)
     return fail(SODA_HIP_ERR_INVALID, "grid does not fit a 1-D launch");
   size_t size = sizeof args;
-  void* extra[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &args,
+  if (res_dev) {
+    all.r = res_dev;
+    all.box = *box;
+    size = sizeof all;
+  }
+  void* extra[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &all,
                    HIP_LAUNCH_PARAM_BUFFER_SIZE, &size, HIP_LAUNCH_PARAM_END};
   // (a batched kernel takes blockIdx.y as the item; every other kernel is
   // launched with batch = 1 and never looks)
@@ -667,6 +717,90 @@ int launch(soda_hip_program* p, int k, const soda_hip_kargs_t& base,
                                 d.block[0], d.block[1], d.block[2],
                                 d.lds_bytes, stream, nullptr, extra));
   return SODA_HIP_OK;
+}
+
+// `<app>_residual` over the dense arrays of `base` (outputs: cur, inputs:
+// prev)
+int launch_residual(soda_hip_program* p, const soda_hip_kargs_t& base,
+                    hipStream_t stream, void* res_dev,
+                    const soda_hip_resbox_t& box) {
+  const int k = p->plan.residual.kernel;
+  const soda_hip_kernel_desc_t& d = p->plan.kernels[k];
+  ResidualArgs all;
+  all.a = base;
+  all.r = res_dev;
+  all.box = box;
+  // grid: the segments of block x vec cells a row has, times as many rows in
+  // flight as fill the GPU a few times over (the kernel strides over the
+  // rest): a whole number of rows' worth of blocks, which is what lets the
+  // kernel find its segment without a division per fragment
+  const int64_t seg = (int64_t)d.block[0] * (d.vec > 0 ? d.vec : 1);
+  const int64_t nx = (base.extent[0] + seg - 1) / seg;
+  int64_t rows = 1;
+  for (int i = 1; i < p->plan.dim; ++i) rows *= base.extent[i];
+  if (rows > 0x7fffffffLL || nx > 0x7fffffLL)
+    return fail(SODA_HIP_ERR_INVALID, "residual: grid does not fit a launch");
+  // (about a thousand blocks: every wave ends in up to four atomics on the
+  // one struct, and tens of thousands of those cost more than the arrays'
+  // bytes -- jacobi2d 8192^2: 918 us over a plain run on 8192 blocks, 306 on
+  // 1024)
+  int64_t in_flight = 1024 / nx;
+  if (in_flight < 1) in_flight = 1;
+  if (in_flight > rows) in_flight = rows;
+  const int64_t blocks = nx * in_flight;
+  size_t size = sizeof all;
+  void* extra[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &all,
+                   HIP_LAUNCH_PARAM_BUFFER_SIZE, &size, HIP_LAUNCH_PARAM_END};
+  HIP_TRY(hipModuleLaunchKernel(p->functions[k], (unsigned)blocks, 1, 1,
+                                d.block[0], d.block[1], d.block[2],
+                                d.lds_bytes, stream, nullptr, extra));
+  return SODA_HIP_OK;
+}
+
+// The cells a residual over `iterate` iterations counts (soda_hip.h,
+// soda_hip_residual_plan_t): the plan's recurrence run `iterate` times from
+// zero windows, the box the array less the window, clipped like every valid
+// box (lo inside the array, hi >= lo).  A round costs pairs^2 x dim steps.
+void residual_box(const soda_hip_plan_t& plan, const int32_t* ext,
+                  int32_t iterate, soda_hip_resbox_t* box) {
+  const soda_hip_residual_plan_t& r = plan.residual;
+  const int n = plan.num_outputs, dim = plan.dim;
+  int64_t lo[SODA_HIP_MAX_RES_PAIRS][SODA_HIP_MAX_DIM] = {};
+  int64_t hi[SODA_HIP_MAX_RES_PAIRS][SODA_HIP_MAX_DIM] = {};
+  const int64_t cap = (int64_t)1 << 40;    // far beyond any extent
+  for (int32_t it = 0; it < iterate && !r.whole; ++it) {
+    int64_t nlo[SODA_HIP_MAX_RES_PAIRS][SODA_HIP_MAX_DIM];
+    int64_t nhi[SODA_HIP_MAX_RES_PAIRS][SODA_HIP_MAX_DIM];
+    for (int o = 0; o < n; ++o)
+      for (int d = 0; d < dim; ++d) {
+        int64_t l = r.base_lo[o][d], h = r.base_hi[o][d];
+        for (int i = 0; i < n; ++i) {
+          if (r.dep_lo[o][i][d] != SODA_HIP_RES_NONE) {
+            const int64_t v = r.dep_lo[o][i][d] + (lo[i][d] < 0 ? lo[i][d] : 0);
+            if (v < l) l = v;
+          }
+          if (r.dep_hi[o][i][d] != SODA_HIP_RES_NONE) {
+            const int64_t v = r.dep_hi[o][i][d] + (hi[i][d] > 0 ? hi[i][d] : 0);
+            if (v > h) h = v;
+          }
+        }
+        nlo[o][d] = l < -cap ? -cap : l;
+        nhi[o][d] = h > cap ? cap : h;
+      }
+    memcpy(lo, nlo, sizeof lo);
+    memcpy(hi, nhi, sizeof hi);
+  }
+  memset(box, 0, sizeof *box);
+  for (int o = 0; o < n; ++o)
+    for (int d = 0; d < SODA_HIP_MAX_DIM; ++d) {
+      const int64_t e = d < dim ? ext[d] : 1;
+      int64_t l = d < dim && !r.whole && lo[o][d] < 0 ? -lo[o][d] : 0;
+      int64_t h = e - (d < dim && !r.whole && hi[o][d] > 0 ? hi[o][d] : 0);
+      if (l > e) l = e;
+      if (h < l) h = l;
+      box->lo[o][d] = (int32_t)l;
+      box->hi[o][d] = (int32_t)h;
+    }
 }
 
 int64_t ceil_div(int64_t a, int64_t b) { return a <= 0 ? 0 : (a + b - 1) / b; }
@@ -953,10 +1087,13 @@ int run_core(soda_hip_program_t* p, void* const* outputs,
              const void* const* inputs, const int32_t* extent,
              const int32_t* origin, const int32_t* global_extent,
              int32_t iterate, void* stream_, int force_pass,
-             const SlabRun* slab, int32_t batch) {
+             const SlabRun* slab, int32_t batch, const ResidualRun* res) {
   if (!p || !outputs || !inputs || !extent)
     return fail(SODA_HIP_ERR_INVALID, "run_device: NULL argument");
   const soda_hip_plan_t& plan = p->plan;
+  if (res && (slab || batch != 1 || force_pass >= 0 || origin ||
+              global_extent || !plan.residual.present || !res->dev))
+    return fail(SODA_HIP_ERR_INVALID, "run_core: bad residual run");
   if (batch < 1 || (batch > 1 && (!plan.batched || slab)))
     return fail(SODA_HIP_ERR_INVALID, "run_core: bad batch");
   // plans, schedules and measured times of this batch size
@@ -1128,6 +1265,45 @@ int run_core(soda_hip_program_t* p, void* const* outputs,
     total = hit->second[plan.num_passes];
   }
 
+  // A residual run keeps the multiset of passes and changes their order: the
+  // pass that takes the residual goes last.  That is the deepest scheduled
+  // pass whose kernel has a twin (the residual costs a launch the same work
+  // whatever its depth); if none has one, the one-iteration pass,
+  // behind which `<app>_residual` compares the outputs with that pass's
+  // inputs -- taken out of a deeper pass's count where the schedule had none
+  // (iterate - 1 iterations scheduled, one added).
+  int res_last = -1;
+  bool res_twin = false;
+  if (res) {
+    const char* g = getenv("SODA_HIP_RESIDUAL_GENERIC");
+    const bool generic = g && !strcmp(g, "1");
+    for (int i = 0; i < plan.num_passes && !generic && res_last < 0; ++i)
+      if (count[i] > 0 && plan.passes[i].num_kernels == 1 &&
+          plan.kernels[plan.passes[i].kernel[0]].twin >= 0) {
+        res_last = i;
+        res_twin = true;
+      }
+    if (res_last < 0) {
+      const int one = plan.num_passes - 1;   // fused_iters 1 (check_plan)
+      if (!count[one]) {
+        for (int i = 0; i < plan.num_passes; ++i) count[i] = 0;
+        total = 0;
+        if (iterate > 1) {
+          ExtentKey key;
+          for (int d = 0; d < SODA_HIP_MAX_DIM; ++d) key[d] = base.extent[d];
+          auto it = measured.find(key);
+          const std::vector<double>& pass_ns =
+              it != measured.end() ? it->second : ep->model_ns;
+          if (int rc = schedule(plan, pass_ns, iterate - 1, count, &total))
+            return rc;
+        }
+        ++count[one];
+        ++total;
+      }
+      res_last = one;
+    }
+  }
+
   if (p->debug) base.buf[SODA_HIP_MAX_TENSORS - 1] = p->debug;
   // the banked form of a wire stream's program: the stream's length, beyond
   // which a delayed input reads as zero (0 for every other program).  Such a
@@ -1178,6 +1354,32 @@ int run_core(soda_hip_program_t* p, void* const* outputs,
   if (int rc = plan_launches(plan, &extents, base.extent, count, total,
                              iterate, slab, &launches))
     return rc;
+  soda_hip_resbox_t res_box;
+  if (res) {
+    // the pass that takes the residual goes last
+    for (size_t q = launches.size(); q-- > 0;)
+      if (launches[q].pass == res_last) {
+        std::rotate(launches.begin() + q, launches.begin() + q + 1,
+                    launches.end());
+        break;
+      }
+    residual_box(plan, base.extent, res->box_iterate, &res_box);
+    // zeroed inside the call, on the caller's stream, by a kernel of the
+    // program: a captured call zeroes and refills the struct at every replay
+    // (as a 32-byte memset node the zeroing did not survive a replay)
+    {
+      const int zk = plan.residual.zero_kernel;
+      void* dev = res->dev;
+      size_t size = sizeof dev;
+      void* extra[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &dev,
+                       HIP_LAUNCH_PARAM_BUFFER_SIZE, &size,
+                       HIP_LAUNCH_PARAM_END};
+      HIP_TRY(hipModuleLaunchKernel(p->functions[zk], 1, 1, 1, 64, 1, 1, 0,
+                                    stream, nullptr, extra));
+    }
+    p->last_res_mode = res_twin ? 1 : 2;
+    p->last_res_fused = plan.passes[res_last].fused_iters;
+  }
   p->last_launches = 0;
   p->last_fused = 0;
   p->last_split = 0;
@@ -1262,11 +1464,20 @@ int run_core(soda_hip_program_t* p, void* const* outputs,
     } else {
       if (L.wait) HIP_TRY(hipStreamWaitEvent(stream, slab->ghosts_ready, 0));
       for (int k = 0; k < plan.passes[i].num_kernels; ++k) {
-        const int kk = plan.passes[i].kernel[k];
-        int rc = launch(p, kk, args, use->geo[kk].tile, stream, nullptr, batch);
+        int kk = plan.passes[i].kernel[k];
+        const bool twin = res && res_twin && last_pass;
+        if (twin) kk = plan.kernels[kk].twin;
+        int rc = launch(p, kk, args, use->geo[kk].tile, stream, nullptr, batch,
+                        twin ? res->dev : nullptr, &res_box);
         if (rc) return rc;
         ++p->last_launches;
         if (i == 0) ++p->last_fused;
+      }
+      if (res && !res_twin && last_pass) {
+        // cur: what the pass just wrote; prev: what it read
+        if (int rc = launch_residual(p, args, stream, res->dev, res_box))
+          return rc;
+        ++p->last_launches;
       }
       if (L.record) HIP_TRY(hipEventRecord(slab->sendable, stream));
     }
@@ -1285,6 +1496,167 @@ int soda_hip_run_device(soda_hip_program_t* p, void* const* outputs,
                         int32_t iterate, void* stream_) {
   return run_core(p, outputs, inputs, extent, nullptr, nullptr, iterate,
                   stream_, -1, nullptr);
+}
+
+int soda_hip_plan_residual_box(const soda_hip_plan_t* plan,
+                               const int32_t* extent, int32_t iterate,
+                               int32_t* lo, int32_t* hi) {
+  if (!plan || !extent || !lo || !hi)
+    return fail(SODA_HIP_ERR_INVALID, "plan_residual_box: NULL argument");
+  if (int rc = check_plan(plan)) return rc;
+  if (!plan->residual.present)
+    return fail(SODA_HIP_ERR_UNSUPPORTED,
+                "plan_residual_box: the plan has no residual");
+  if (iterate < 1)
+    return fail(SODA_HIP_ERR_INVALID, "plan_residual_box: iterate < 1");
+  for (int d = 0; d < plan->dim; ++d)
+    if (extent[d] < 1)
+      return fail(SODA_HIP_ERR_INVALID, "plan_residual_box: extent < 1");
+  soda_hip_resbox_t box;
+  residual_box(*plan, extent, iterate, &box);
+  for (int o = 0; o < plan->num_outputs; ++o)
+    for (int d = 0; d < plan->dim; ++d) {
+      lo[o * plan->dim + d] = box.lo[o][d];
+      hi[o * plan->dim + d] = box.hi[o][d];
+    }
+  return SODA_HIP_OK;
+}
+
+// what both residual entries ask of a program and of the 32 bytes
+static int check_residual(const soda_hip_program* p, void* const* outputs,
+                          const int32_t* extent, const void* residual_dev,
+                          const char* who) {
+  const soda_hip_plan_t& plan = p->plan;
+  if (!plan.residual.present)
+    return fail(SODA_HIP_ERR_UNSUPPORTED,
+                std::string(who) +
+                    ": the program has no residual kernels (build it with "
+                    "LowerOptions.residual / sodac --hip-residual); nothing "
+                    "was launched");
+  if (!residual_dev) return SODA_HIP_OK;
+  if (reinterpret_cast<uintptr_t>(residual_dev) % 8)
+    return fail(SODA_HIP_ERR_INVALID,
+                std::string(who) + ": the residual struct is not 8-byte "
+                                   "aligned; nothing was launched");
+  uint64_t cells = 1;
+  for (int d = 0; d < plan.dim; ++d) cells *= (uint64_t)(extent[d] > 0 ? extent[d] : 0);
+  const uintptr_t r0 = reinterpret_cast<uintptr_t>(residual_dev);
+  for (int o = 0; o < plan.num_outputs; ++o) {
+    const uintptr_t o0 = reinterpret_cast<uintptr_t>(outputs[o]);
+    if (outputs[o] && r0 < o0 + cells * plan.elem_size[plan.num_inputs + o] &&
+        o0 < r0 + sizeof(soda_hip_residual_t))
+      return fail(SODA_HIP_ERR_INVALID,
+                  std::string(who) + ": the residual struct overlaps an "
+                                     "output; nothing was launched");
+  }
+  return SODA_HIP_OK;
+}
+
+int soda_hip_run_device_residual(soda_hip_program_t* p, void* const* outputs,
+                                 const void* const* inputs,
+                                 const int32_t* extent, int32_t iterate,
+                                 void* residual_dev, void* stream_) {
+  if (!p || !outputs || !inputs || !extent || !residual_dev)
+    return fail(SODA_HIP_ERR_INVALID, "run_device_residual: NULL argument");
+  p->last_res_mode = 0;
+  p->last_res_fused = 0;
+  p->last_launches = 0;
+  p->last_fused = 0;
+  if (int rc = check_residual(p, outputs, extent, residual_dev,
+                              "run_device_residual"))
+    return rc;
+  const ResidualRun run = {residual_dev, iterate};
+  return run_core(p, outputs, inputs, extent, nullptr, nullptr, iterate,
+                  stream_, -1, nullptr, 1, &run);
+}
+
+int soda_hip_run_device_until(soda_hip_program_t* p, void* const* outputs,
+                              const void* const* inputs, const int32_t* extent,
+                              int32_t max_iterate, int32_t check_every,
+                              double tol, uint64_t int_tol,
+                              soda_hip_residual_t* result_host,
+                              int32_t* iterations_done, void* stream_) {
+  if (!p || !outputs || !inputs || !extent)
+    return fail(SODA_HIP_ERR_INVALID, "run_device_until: NULL argument");
+  if (max_iterate < 1 || check_every < 1)
+    return fail(SODA_HIP_ERR_INVALID,
+                "run_device_until: max_iterate and check_every must be >= 1");
+  if (int rc = check_residual(p, outputs, extent, nullptr, "run_device_until"))
+    return rc;
+  const soda_hip_plan_t& plan = p->plan;
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  HIP_TRY(hipSetDevice(p->device));
+  hipStreamCaptureStatus capture = hipStreamCaptureStatusNone;
+  if (hipStreamIsCapturing(stream, &capture) != hipSuccess) {
+    (void)hipGetLastError();
+    capture = hipStreamCaptureStatusNone;
+  }
+  if (capture != hipStreamCaptureStatusNone)
+    return fail(SODA_HIP_ERR_INVALID,
+                "run_device_until: synchronous, not for a stream that is "
+                "being captured; nothing was launched");
+  int64_t cells = 1;
+  for (int d = 0; d < plan.dim; ++d) {
+    if (extent[d] < 1)
+      return fail(SODA_HIP_ERR_INVALID, "run_device_until: extent < 1");
+    cells *= extent[d];
+  }
+  if (int rc = ensure(p->until_res, sizeof(soda_hip_residual_t))) return rc;
+  const int out0 = plan.num_inputs;
+  std::vector<const void*> in(inputs,
+                              inputs + plan.num_inputs + plan.num_params);
+  std::vector<void*> tmp(plan.num_outputs, nullptr);
+  std::vector<void*> own(outputs, outputs + plan.num_outputs);
+  soda_hip_residual_t host;
+  memset(&host, 0, sizeof host);
+  int32_t done = 0;
+  bool in_tmp = false;
+  for (int32_t chunk = 0; done < max_iterate; ++chunk) {
+    const int32_t n =
+        max_iterate - done < check_every ? max_iterate - done : check_every;
+    in_tmp = chunk % 2 == 1;
+    if (in_tmp && !tmp[0])
+      for (int o = 0; o < plan.num_outputs; ++o) {
+        if (int rc = ensure(p->until_tmp[o],
+                            (size_t)cells * plan.elem_size[out0 + o]))
+          return rc;
+        tmp[o] = p->until_tmp[o].ptr;
+      }
+    void* const* dst = in_tmp ? tmp.data() : own.data();
+    const ResidualRun run = {p->until_res.ptr, done + n};
+    if (int rc = run_core(p, dst, in.data(), extent, nullptr, nullptr, n,
+                          stream_, -1, nullptr, 1, &run))
+      return rc;
+    HIP_TRY(hipMemcpyAsync(&host, p->until_res.ptr, sizeof host,
+                           hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    done += n;
+    // the next chunk continues from this one's result; the caller's inputs
+    // were read by the first chunk only
+    for (int j = 0; j < plan.num_inputs; ++j) in[j] = dst[j];
+    double max_float;
+    memcpy(&max_float, &host.max_float_bits, sizeof max_float);
+    if (host.unordered == 0 && max_float <= tol && host.max_int <= int_tol)
+      break;
+  }
+  if (in_tmp) {
+    for (int o = 0; o < plan.num_outputs; ++o)
+      HIP_TRY(hipMemcpyAsync(outputs[o], tmp[o],
+                             (size_t)cells * plan.elem_size[out0 + o],
+                             hipMemcpyDeviceToDevice, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+  }
+  if (result_host) *result_host = host;
+  if (iterations_done) *iterations_done = done;
+  return SODA_HIP_OK;
+}
+
+int soda_hip_last_residual(soda_hip_program_t* p, int32_t* mode,
+                           int32_t* fused_iters) {
+  if (!p || !mode) return fail(SODA_HIP_ERR_INVALID, "last_residual: NULL");
+  *mode = p->last_res_mode;
+  if (fused_iters) *fused_iters = p->last_res_fused;
+  return SODA_HIP_OK;
 }
 
 int soda_hip_run_device_batch(soda_hip_program_t* p, void* const* outputs,
@@ -1649,7 +2021,7 @@ int soda_hip_program_scratch(soda_hip_program_t* p, int64_t* bytes,
   if (!p) return fail(SODA_HIP_ERR_INVALID, "NULL program");
   if (bytes) *bytes = 0;
   if (regrown) *regrown = 0;
-  for (const auto* v : {&p->locals, &p->temps, &p->temps2})
+  for (const auto* v : {&p->locals, &p->temps, &p->temps2, &p->until_tmp})
     add_scratch(*v, bytes, regrown);
   return SODA_HIP_OK;
 }

@@ -102,6 +102,14 @@ struct soda_hip_program {
   // ... and its partner in runs trimmed to a cone, which keep their
   // intermediate passes out of the caller's outputs (run_core)
   std::vector<soda_detail::DeviceBuffer> temps2;
+  // soda_hip_run_device_until: the arrays its chunks ping-pong through beside
+  // the caller's outputs (one per output), and the 32 bytes it fetches
+  std::vector<soda_detail::DeviceBuffer> until_tmp;
+  soda_detail::DeviceBuffer until_res;
+  // how the last soda_hip_run_device_residual took its residual (0 none,
+  // 1 twin, 2 `<app>_residual`) and the fusion depth of its last pass
+  int32_t last_res_mode = 0;
+  int32_t last_res_fused = 0;
   std::vector<soda_detail::DeviceBuffer> host_in;  // run_host staging
   std::vector<soda_detail::DeviceBuffer> host_prm; // ... of the param arrays
   std::vector<soda_detail::DeviceBuffer> host_out;
@@ -153,6 +161,15 @@ struct soda_hip_program {
 
 namespace soda_detail {
 
+// A run that also takes the residual of its last iteration
+// (soda_hip_run_device_residual): where the struct goes, and the iterations
+// the counted box is that of (soda_hip_run_device_until runs chunk after
+// chunk: the box is the one after all iterations done so far)
+struct ResidualRun {
+  void* dev;
+  int32_t box_iterate;
+};
+
 // force_pass >= 0: use only that pass (calibration).  batch > 1: every
 // tensor holds that many grids of `extent`, one launch runs them all (a
 // batched plan, no slab: soda_hip_run_device_batch checks)
@@ -160,7 +177,8 @@ int run_core(soda_hip_program* p, void* const* outputs,
              const void* const* inputs, const int32_t* extent,
              const int32_t* origin, const int32_t* global_extent,
              int32_t iterate, void* stream, int force_pass,
-             const SlabRun* slab, int32_t batch = 1);
+             const SlabRun* slab, int32_t batch = 1,
+             const ResidualRun* res = nullptr);
 
 inline std::map<ExtentKey, std::vector<double>>& measured_of(
     soda_hip_program* p, int32_t batch) {

@@ -11,6 +11,7 @@ There is no CPU fallback: a missing library, a failed JIT or a missing GPU
 raises `util.BackendError`.
 """
 import ctypes
+import dataclasses
 import hashlib
 import os
 from typing import Dict, Optional, Sequence
@@ -51,10 +52,11 @@ MAX_PASS_KERNELS = 16
 MAX_PARAMS = 8
 MAX_SLABS = 64
 NAME_LEN = 96
+MAX_RES_PAIRS = 8     # SODA_HIP_MAX_RES_PAIRS
 GROUP_NO_OVERLAP = 1
 GROUP_CALIBRATE = 2
 GROUP_THREADS = 4
-ABI_VERSION = 8
+ABI_VERSION = 9
 MAX_BATCH = 65535      # SODA_HIP_MAX_BATCH: gridDim.y
 
 
@@ -76,7 +78,8 @@ class KernelDesc(ctypes.Structure):
               ('warm_saved', ctypes.c_float),
               ('bytes_per_cell', ctypes.c_float),
               ('lane_redundancy', ctypes.c_float),
-              ('max_extent0', ctypes.c_int32)]
+              ('max_extent0', ctypes.c_int32),
+              ('twin', ctypes.c_int32)]
 
 
 class PassDesc(ctypes.Structure):
@@ -84,6 +87,47 @@ class PassDesc(ctypes.Structure):
               ('num_kernels', ctypes.c_int32),
               ('kernel', ctypes.c_int32 * MAX_PASS_KERNELS),
               ('cost', ctypes.c_float)]
+
+
+class ResidualStruct(ctypes.Structure):
+  """Mirror of soda_hip_residual_t: the 32 device bytes a residual run fills."""
+  _fields_ = [('changed', ctypes.c_uint64), ('unordered', ctypes.c_uint64),
+              ('max_float_bits', ctypes.c_uint64), ('max_int', ctypes.c_uint64)]
+
+
+class ResBox(ctypes.Structure):
+  """Mirror of soda_hip_resbox_t."""
+  _fields_ = [('lo', (ctypes.c_int32 * MAX_DIM) * MAX_RES_PAIRS),
+              ('hi', (ctypes.c_int32 * MAX_DIM) * MAX_RES_PAIRS)]
+
+
+class ResidualPlan(ctypes.Structure):
+  """Mirror of soda_hip_residual_plan_t."""
+  _fields_ = [('present', ctypes.c_int32), ('kernel', ctypes.c_int32),
+              ('zero_kernel', ctypes.c_int32), ('whole', ctypes.c_int32),
+              ('base_lo', (ctypes.c_int32 * MAX_DIM) * MAX_RES_PAIRS),
+              ('base_hi', (ctypes.c_int32 * MAX_DIM) * MAX_RES_PAIRS),
+              ('dep_lo', ((ctypes.c_int32 * MAX_DIM) * MAX_RES_PAIRS) *
+               MAX_RES_PAIRS),
+              ('dep_hi', ((ctypes.c_int32 * MAX_DIM) * MAX_RES_PAIRS) *
+               MAX_RES_PAIRS)]
+
+
+@dataclasses.dataclass(frozen=True)
+class Residual:
+  """soda_hip_residual_t decoded: how much the last iteration of a run changed
+  the grid (include/soda_hip.h has the definition)."""
+  changed: int
+  unordered: int
+  max_float: float
+  max_int: int
+
+  @classmethod
+  def from_struct(cls, raw: 'ResidualStruct') -> 'Residual':
+    import struct
+    return cls(int(raw.changed), int(raw.unordered),
+               struct.unpack('<d', struct.pack('<Q', raw.max_float_bits))[0],
+               int(raw.max_int))
 
 
 class Plan(ctypes.Structure):
@@ -98,7 +142,8 @@ class Plan(ctypes.Structure):
               ('num_passes', ctypes.c_int32),
               ('passes', PassDesc * MAX_PASSES),
               ('has_reach', ctypes.c_int32), ('reach_lo', ctypes.c_int32),
-              ('reach_hi', ctypes.c_int32), ('batched', ctypes.c_int32)]
+              ('reach_hi', ctypes.c_int32), ('batched', ctypes.c_int32),
+              ('residual', ResidualPlan)]
 
 
 class StreamDesc(ctypes.Structure):
@@ -207,6 +252,16 @@ API = {
     'soda_hip_run_device': (ctypes.c_int, [_vp, _pvp, _pvp, _pi32, _i32, _vp]),
     'soda_hip_run_device_batch': (ctypes.c_int, [_vp, _pvp, _pvp, _pi32, _i32,
                                                  _i32, _vp]),
+    'soda_hip_run_device_residual': (ctypes.c_int, [_vp, _pvp, _pvp, _pi32,
+                                                    _i32, _vp, _vp]),
+    'soda_hip_run_device_until': (ctypes.c_int, [
+        _vp, _pvp, _pvp, _pi32, _i32, _i32, ctypes.c_double, ctypes.c_uint64,
+        ctypes.POINTER(ResidualStruct), _pi32, _vp
+    ]),
+    'soda_hip_plan_residual_box': (ctypes.c_int, [
+        ctypes.POINTER(Plan), _pi32, _i32, _pi32, _pi32
+    ]),
+    'soda_hip_last_residual': (ctypes.c_int, [_vp, _pi32, _pi32]),
     'soda_hip_run_device_window': (ctypes.c_int, [_vp, _pvp, _pvp, _pi32, _pi32,
                                                   _pi32, _i32, _vp]),
     'soda_hip_run_device_cone': (ctypes.c_int, [_vp, _pvp, _pvp, _pi32, _pi32,
@@ -342,7 +397,8 @@ def library() -> ctypes.CDLL:
     for which, mirror in ((1, KernelDesc), (2, PassDesc), (3, Plan),
                           (4, HostTensor), (5, StreamDesc), (6, SlabRun),
                           (7, GroupDesc), (8, SlabInfo), (9, GroupStats),
-                          (10, LaunchInfo)):
+                          (10, LaunchInfo), (11, ResidualStruct),
+                          (12, ResBox)):
       if lib.soda_hip_sizeof(which) != ctypes.sizeof(mirror):
         raise util.BackendError(
             'struct layout mismatch between libsoda_hip.so and runtime.py '
@@ -512,6 +568,15 @@ def make_plan(mod: lower.Module,
       d.bytes_per_cell = 0.0 if tune.get('unmodelled') else io_bytes
       d.lane_redundancy = float(tune.get('lane_redundancy') or 1.0)
       d.max_extent0 = int(tune.get('max_extent0') or 0)
+    d.twin = int(getattr(k, 'twin', -1))
+    if d.twin >= 0 and resources:
+      # a twin whose extra window made the compiler spill where the plain
+      # kernel does not is dropped: the library then ends such a run in the
+      # one-iteration pass and `<app>_residual`
+      mine = resources.get(k.name, {}).get('scratch') or 0
+      its = resources.get(mod.kernels[d.twin].name, {}).get('scratch') or 0
+      if its > mine:
+        d.twin = -1
   passes = mod.sorted_passes()
   if len(passes) > MAX_PASSES:
     raise util.SemanticError('more than %d passes' % MAX_PASSES)
@@ -529,6 +594,19 @@ def make_plan(mod: lower.Module,
   plan.has_reach = 1
   plan.reach_lo, plan.reach_hi = st.reach_along(st.dim - 1)
   plan.batched = 1 if getattr(mod, 'batch', False) else 0
+  if getattr(mod, 'residual', False):
+    from soda_amd.codegen.hip import residual as _residual
+    rec = _residual.box_recurrence(st)
+    r = plan.residual
+    r.present, r.kernel, r.whole = 1, mod.residual_kernel, int(rec['whole'])
+    r.zero_kernel = mod.residual_zero_kernel
+    for o in range(len(st.output_names)):
+      for d in range(MAX_DIM):
+        r.base_lo[o][d] = rec['base_lo'][o][d]
+        r.base_hi[o][d] = rec['base_hi'][o][d]
+        for i in range(len(st.input_names)):
+          r.dep_lo[o][i][d] = rec['dep_lo'][o][i][d]
+          r.dep_hi[o][i][d] = rec['dep_hi'][o][i][d]
   return plan
 
 
@@ -1050,7 +1128,8 @@ class Program:
                  ghosts: Optional[Sequence[int]] = None,
                  sends: Optional[Sequence[int]] = None,
                  ghosts_ready: int = 0, sendable: int = 0,
-                 batch: Optional[int] = None) -> None:
+                 batch: Optional[int] = None,
+                 residual: Optional[int] = None) -> None:
     """`outputs` / `inputs` are device addresses (e.g. tensor.data_ptr()) of
     dense dim-0-fastest arrays; asynchronous on `stream`.  `inputs` holds the
     input tensors followed by the program's `param` arrays (C order).
@@ -1101,7 +1180,13 @@ class Program:
     is to pick the schedule -- then capture.  The graph holds the addresses of
     the scratch: replay it only until a later call grows that scratch or the
     Program is closed.  Runs with `ghosts_ready` / `sendable` are not meant
-    for capture."""
+    for capture.
+    `residual` = the device address of 32 bytes (8-byte aligned): the run also
+    leaves there how much its LAST iteration changed the grid
+    (soda_hip_run_device_residual; `residual()` reads and decodes them).  The
+    struct is zeroed on `stream` inside the call; the run stays asynchronous
+    and can be captured like any other.  Needs a program built with
+    LowerOptions.residual; runs on whole grids only."""
     st = self.stencil
     iterate = st.iterate if iterate is None else iterate
     self._check_extent(extent)
@@ -1111,6 +1196,19 @@ class Program:
     outs = (ctypes.c_void_p * len(outputs))(*outputs)
     ins = (ctypes.c_void_p * len(inputs))(*inputs)
     ext = (ctypes.c_int32 * len(extent))(*extent)
+    if residual is not None:
+      if batch is not None or keep is not None or ghosts is not None or \
+          sends is not None or origin is not None or \
+          global_extent is not None or ghosts_ready or sendable:
+        raise util.InputError(
+            'run_device: a residual is that of a run on one whole grid: no '
+            'batch / keep / ghosts / sends / origin')
+      check(
+          self._lib.soda_hip_run_device_residual(
+              self._handle, outs, ins, ext, iterate, ctypes.c_void_p(residual),
+              ctypes.c_void_p(stream)),
+          'running `%s` with a residual' % st.app_name)
+      return
     if batch is not None:
       if keep is not None or ghosts is not None or sends is not None or \
           origin is not None or global_extent is not None or ghosts_ready or \
@@ -1152,6 +1250,115 @@ class Program:
                                              gext, iterate,
                                              ctypes.c_void_p(stream)),
         'running `%s`' % st.app_name)
+
+  def residual(self, ptr: int, stream: int = 0) -> Residual:
+    """The struct a `run_device(..., residual=ptr)` left at device address
+    `ptr`, decoded.  Copies the 32 bytes on `stream` and waits for them."""
+    raw = ResidualStruct()
+    check(self._lib.soda_hip_memcpy_d2h(ctypes.byref(raw), ctypes.c_void_p(ptr),
+                                        ctypes.sizeof(raw),
+                                        ctypes.c_void_p(stream)),
+          'residual: copy out')
+    check(self._lib.soda_hip_stream_synchronize(ctypes.c_void_p(stream)),
+          'residual: synchronize')
+    return Residual.from_struct(raw)
+
+  def last_residual(self):
+    """How the last `run_device(..., residual=)` took its residual: ('twin' |
+    'generic' | None, fusion depth of the pass launched last)."""
+    mode, fused = ctypes.c_int32(), ctypes.c_int32()
+    check(self._lib.soda_hip_last_residual(self._handle, ctypes.byref(mode),
+                                           ctypes.byref(fused)),
+          'last_residual')
+    return {0: None, 1: 'twin', 2: 'generic'}[mode.value], fused.value
+
+  def residual_box(self, extent: Sequence[int], iterate: int):
+    """[(lo, hi)] per output: the cells a residual over `iterate` iterations
+    on `extent` counts, as the library derives them from the plan."""
+    dim = self.stencil.dim
+    n = len(self.stencil.output_names)
+    ext = (ctypes.c_int32 * MAX_DIM)(*(list(extent) + [1] * (MAX_DIM - dim)))
+    lo, hi = (ctypes.c_int32 * (n * dim))(), (ctypes.c_int32 * (n * dim))()
+    check(library().soda_hip_plan_residual_box(ctypes.byref(self.plan), ext,
+                                               iterate, lo, hi),
+          'residual_box')
+    return [(tuple(lo[o * dim:(o + 1) * dim]), tuple(hi[o * dim:(o + 1) * dim]))
+            for o in range(n)]
+
+  def run_until(self, inputs: Dict[str, 'numpy.ndarray'], tol: float,
+                max_iterate: int, check_every: int = 8, int_tol: int = 0):
+    """Iterates on numpy arrays until converged: `check_every` iterations at a
+    time, stopping when the last iteration's residual has `unordered == 0`,
+    `max_float <= tol` and `max_int <= int_tol`, or after `max_iterate`
+    iterations (soda_hip_run_device_until; synchronous).  Returns (outputs,
+    iterations done, Residual).  Like `run`, the outputs start as zeros and
+    only each output's valid box after the iterations done is written; the
+    input arrays are not touched.  Needs a program built with
+    LowerOptions.residual."""
+    import numpy as np
+    st = self.stencil
+    lib = self._lib
+    first = np.asarray(inputs[st.input_names[0]])
+    extent = tuple(first.shape[::-1])
+    self._check_extent(extent)
+    host_in = []
+    for n, t in zip(st.input_names, st.input_types):
+      arr = np.ascontiguousarray(inputs[n])
+      if arr.dtype != np.dtype(t.np_name):
+        raise util.InputError('expected dtype %s, got %s' % (t.np_name,
+                                                             arr.dtype))
+      if arr.shape != first.shape:
+        raise util.InputError('all tensors must share one shape')
+      host_in.append(arr)
+    for pstmt in st.param_stmts:        # param arrays follow, C order
+      arr = np.ascontiguousarray(inputs[pstmt.name]).reshape(-1)
+      if arr.dtype != np.dtype(pstmt.haoda_type.np_name) or \
+          arr.size != st.param_elems(pstmt):
+        raise util.InputError('param %s must be %d x %s' % (
+            pstmt.name, st.param_elems(pstmt), pstmt.haoda_type.np_name))
+      host_in.append(arr)
+    dense = [np.empty(first.shape, dtype=np.dtype(t.np_name))
+             for t in st.output_types]
+    dev_in, dev_out = [], []
+    raw = ResidualStruct()
+    done = ctypes.c_int32(0)
+    try:
+      for arr in host_in:
+        ptr = ctypes.c_void_p()
+        check(lib.soda_hip_malloc(self.device, arr.nbytes, ctypes.byref(ptr)),
+              'run_until: allocating an input')
+        dev_in.append(ptr)
+        check(lib.soda_hip_memcpy_h2d(ptr, arr.ctypes.data, arr.nbytes, None),
+              'run_until: copy in')
+      for arr in dense:
+        ptr = ctypes.c_void_p()
+        check(lib.soda_hip_malloc(self.device, arr.nbytes, ctypes.byref(ptr)),
+              'run_until: allocating an output')
+        dev_out.append(ptr)
+      outs = (ctypes.c_void_p * len(dev_out))(*[p.value for p in dev_out])
+      ins = (ctypes.c_void_p * len(dev_in))(*[p.value for p in dev_in])
+      ext = (ctypes.c_int32 * len(extent))(*extent)
+      check(
+          lib.soda_hip_run_device_until(self._handle, outs, ins, ext,
+                                        int(max_iterate), int(check_every),
+                                        float(tol), int(int_tol),
+                                        ctypes.byref(raw), ctypes.byref(done),
+                                        None),
+          'running `%s` until converged' % st.app_name)
+      for arr, ptr in zip(dense, dev_out):
+        check(lib.soda_hip_memcpy_d2h(arr.ctypes.data, ptr, arr.nbytes, None),
+              'run_until: copy out')
+      check(lib.soda_hip_stream_synchronize(None), 'run_until: synchronize')
+    finally:
+      for ptr in dev_in + dev_out:
+        lib.soda_hip_free(self.device, ptr)
+    result = {}
+    for n, arr in zip(st.output_names, dense):
+      lo, hi = clipped_box(st.valid_box(extent, n, done.value), extent)
+      box = tuple(slice(l, h) for l, h in zip(lo, hi))[::-1]
+      result[n] = np.zeros_like(arr)
+      result[n][box] = arr[box]
+    return result, done.value, Residual.from_struct(raw)
 
   def last_split(self) -> int:
     """Passes of the last run launched in two parts around a halo exchange."""
