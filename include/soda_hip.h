@@ -64,7 +64,11 @@ extern "C" {
  * soda_hip_program_scratch.  9: the residual of a run's last iteration -- the
  * kernel descriptor names its twin, the plan carries `residual`, with
  * soda_hip_run_device_residual / _until, soda_hip_plan_residual_box and
- * soda_hip_last_residual. */
+ * soda_hip_last_residual.  Added under 9 (no struct changed): the residual
+ * on slabs and groups -- soda_hip_plan_residual_slab_box,
+ * soda_hip_run_device_slab_residual, soda_hip_plan_launches_residual,
+ * soda_hip_group_run_residual, soda_hip_group_residual,
+ * soda_hip_group_last_residual, soda_hip_group_run_until. */
 #define SODA_HIP_ABI_VERSION 9
 #define SODA_HIP_MAX_DIM 4
 #define SODA_HIP_MAX_TENSORS 16
@@ -552,7 +556,8 @@ int soda_hip_run_device_batch(soda_hip_program_t* program,
  * had none (iterate - 1 iterations are scheduled, one is added), followed by
  * `<app>_residual` over the outputs and that pass's inputs.
  * SODA_HIP_ERR_UNSUPPORTED, nothing launched: a program built without
- * `residual`.  Windows, cones, slabs, groups and batches are not served. */
+ * `residual`.  Slabs are served by soda_hip_run_device_slab_residual, groups
+ * by soda_hip_group_run_residual; batches are not served. */
 int soda_hip_run_device_residual(soda_hip_program_t* program,
                                  void* const* outputs,
                                  const void* const* inputs,
@@ -583,12 +588,65 @@ int soda_hip_run_device_until(soda_hip_program_t* program,
 int soda_hip_plan_residual_box(const soda_hip_plan_t* plan,
                                const int32_t* extent, int32_t iterate,
                                int32_t* lo, int32_t* hi);
-/* How the last soda_hip_run_device_residual call of the program took its
- * residual: 0 not at all, 1 in the twin of its last pass, 2 by
- * `<app>_residual`; *fused_iters (may be NULL): the fusion depth of that last
- * pass. */
+/* How the last soda_hip_run_device_residual / _slab_residual call of the
+ * program took its residual: 0 not at all, 1 in the twin of its last pass, 2
+ * by `<app>_residual`; *fused_iters (may be NULL): the fusion depth of that
+ * last pass. */
 int soda_hip_last_residual(soda_hip_program_t* program, int32_t* mode,
                            int32_t* fused_iters);
+
+/* The cells ONE SLAB of a larger grid counts: [lo, hi) per output and
+ * dimension, in the coordinates of the slab's arrays (cell 0 of which sits at
+ * `origin` of the grid of `global_extent`).  That is the box
+ * soda_hip_plan_residual_box gives for `global_extent` and `iterate`, cut to
+ * the rows [keep_lo, keep_hi) of the slab's last dimension -- the rows the slab
+ * keeps; its ghost rows are some other slab's to count -- moved by `origin`
+ * and clipped to `extent`.  Slabs whose kept rows partition the global rows
+ * partition the global box: every cell counts once.  Under `border: preserve`
+ * the global box is the whole grid, a slab counts its kept rows.  A slab whose
+ * kept rows miss the global box gets lo == hi and counts nothing.  Pure
+ * function of the plan (no GPU). */
+int soda_hip_plan_residual_slab_box(const soda_hip_plan_t* plan,
+                                    const int32_t* global_extent,
+                                    const int32_t* origin,
+                                    const int32_t* extent, int32_t keep_lo,
+                                    int32_t keep_hi, int32_t iterate,
+                                    int32_t* lo, int32_t* hi);
+/* soda_hip_run_device_slab that also leaves, in the 32 device bytes
+ * `residual_dev`, the slab's share of the residual of the last of `iterate`
+ * iterations: the cells of soda_hip_plan_residual_slab_box taken at
+ * `box_iterate`, the number of iterations the STATE has seen since its inputs
+ * were the caller's -- in a run of several exchange intervals more than this
+ * call's `iterate`; box_iterate < iterate: SODA_HIP_ERR_INVALID.  The shares
+ * of all slabs combine exactly: counts add, maxima take the larger.
+ * The pass that takes the residual goes last, as in
+ * soda_hip_run_device_residual, and the rows every earlier pass covers are
+ * the cone of the order really launched (soda_hip_plan_launches_residual
+ * shows them).  A last pass that is split around the exchange runs its twin
+ * twice on one struct and one box -- first the boundary chunks, `sendable`
+ * recorded exactly once behind them, then the interior -- so when `sendable`
+ * fires the send rows are complete but THE RESIDUAL IS NOT: it is complete
+ * when the interior has finished, i.e. for whatever follows the call on
+ * `stream`.  Where `<app>_residual` takes it, that kernel runs behind both
+ * parts.  The ghost rows of the result, which the last pass writes too, lie
+ * outside the box.  The struct is zeroed by `<app>_residual_zero` on `stream`
+ * inside the call.  "Streams, scratch, graphs" applies as to
+ * soda_hip_run_device_slab: with events not meant for capture. */
+int soda_hip_run_device_slab_residual(
+    soda_hip_program_t* program, void* const* outputs,
+    const void* const* inputs, const int32_t* extent, const int32_t* origin,
+    const int32_t* global_extent, int32_t iterate, int32_t box_iterate,
+    const soda_hip_slab_run_t* run, void* residual_dev, void* stream);
+/* soda_hip_plan_launches for a run that takes a residual (by the model; no
+ * GPU): the last entry is the pass that takes it, *mode how -- 1: launched as
+ * its twin (both parts, if split), 2: followed by `<app>_residual`.
+ * SODA_HIP_ERR_UNSUPPORTED: a plan without residual. */
+int soda_hip_plan_launches_residual(const soda_hip_plan_t* plan,
+                                    const int32_t* extent, int32_t iterate,
+                                    const soda_hip_slab_run_t* run,
+                                    int32_t capacity,
+                                    soda_hip_launch_info_t* launches,
+                                    int32_t* count, int32_t* mode);
 
 /* Replaces soda::app::<app>(): host arrays described by (ptr, extent, stride,
  * min) per tensor, inputs then outputs; copies in, runs, copies the outputs
@@ -848,6 +906,39 @@ int soda_hip_group_run_host(soda_hip_group_t* group,
                             const int32_t* valid_hi);
 int soda_hip_group_last_stats(soda_hip_group_t* group,
                               soda_hip_group_stats_t* stats);
+/* soda_hip_group_run that also takes the residual of the last of `iterate`
+ * iterations: every slab's LAST interval goes through
+ * soda_hip_run_device_slab_residual into 32 bytes the group owns on that
+ * slab's device (allocated at create when plan.residual.present, never inside
+ * a run); earlier intervals are those of soda_hip_group_run.  The box is that
+ * of all iterations since soda_hip_group_load / _loaded: both reset the
+ * count, every run -- plain ones too -- adds to it.  Asynchronous like
+ * soda_hip_group_run; threaded or not, overlapped or not.
+ * SODA_HIP_ERR_UNSUPPORTED, nothing launched: the plan has no residual;
+ * SODA_HIP_ERR_INVALID: no state loaded. */
+int soda_hip_group_run_residual(soda_hip_group_t* group, int32_t iterate);
+/* Synchronises the group, fetches the slabs' structs and folds them on the
+ * host -- counts add, maxima take the larger: the residual of the whole grid,
+ * exactly.  per_slab_host: num_slabs structs, or NULL.  SODA_HIP_ERR_INVALID
+ * if the group's last run was not a residual run. */
+int soda_hip_group_residual(soda_hip_group_t* group,
+                            soda_hip_residual_t* result_host,
+                            soda_hip_residual_t* per_slab_host);
+/* soda_hip_last_residual of one slab's last interval. */
+int soda_hip_group_last_residual(soda_hip_group_t* group, int32_t slab,
+                                 int32_t* mode, int32_t* fused_iters);
+/* Iterates the group's state until converged.  SYNCHRONOUS: `check_every`
+ * iterations at a time through soda_hip_group_run_residual (the last chunk may
+ * be shorter), after each soda_hip_group_residual, and stops when
+ *   unordered == 0 && max_float <= tol && max_int <= int_tol
+ * or when `max_iterate` iterations are done -- the rule of
+ * soda_hip_run_device_until.  SODA_HIP_OK either way; *iterations_done and
+ * *result_host (either may be NULL) tell which.  The state lives in the
+ * slabs: nothing is copied, soda_hip_group_store delivers the result. */
+int soda_hip_group_run_until(soda_hip_group_t* group, int32_t max_iterate,
+                             int32_t check_every, double tol, uint64_t int_tol,
+                             soda_hip_residual_t* result_host,
+                             int32_t* iterations_done);
 
 /* -- the reference kernel's WIRE format: <app>_kernel on banked streams -----
  * The reference's generated host hands its kernel one linear stream per

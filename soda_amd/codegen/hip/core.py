@@ -94,7 +94,8 @@ def add_arguments(parser) -> None:
                       help='--hip-backend: iterate until the largest change of '
                       'a cell in one iteration is <= TOL (at most `iterate` '
                       'iterations); implies --hip-residual; prints the '
-                      'iterations and the residual')
+                      'iterations and the residual; with --hip-gpus N on the '
+                      'slabs (soda_hip_group_run_until)')
   parser.add_argument('--hip-check-every', type=int, dest='hip_check_every',
                       default=8, metavar='K',
                       help='with --hip-until: iterations between two looks at '
@@ -229,12 +230,31 @@ def run(stencil: core.Stencil, args: argparse.Namespace) -> None:
                          exchange_every=int(getattr(args, 'hip_exchange_every',
                                                     0) or 0))
     t0 = time.time()
-    outputs = prog.run_host(inputs)
+    res = None
+    if getattr(args, 'hip_until', None) is not None:
+      # the one-GPU form's loop on the slabs (soda_hip_group_run_until)
+      prog.load(inputs)
+      done, res = prog.run_until(
+          args.hip_until, stencil.iterate,
+          check_every=max(1, int(args.hip_check_every)))
+      outputs = prog.store(done)
+      extra = {'until': args.hip_until, 'iterations': done}
+    elif getattr(args, 'hip_residual', False):
+      prog.load(inputs)
+      prog.run(residual=True)
+      res = prog.residual()
+      outputs = prog.store()
+    else:
+      outputs = prog.run_host(inputs)
     seconds = time.time() - t0
     st = prog.stats()
-    extra = {'gpus': gpus, 'devices': devices,
-             'exchange_every': st['exchange_every'],
-             'exchanges': st['exchanges'], 'split_passes': st['split_passes']}
+    if res is not None:
+      extra['residual'] = {'changed': res.changed, 'unordered': res.unordered,
+                           'max_float': res.max_float, 'max_int': res.max_int}
+    extra.update({'gpus': gpus, 'devices': devices,
+                  'exchange_every': st['exchange_every'],
+                  'exchanges': st['exchanges'],
+                  'split_passes': st['split_passes']})
   else:
     prog = runtime.Program(stencil, options_from_args(args),
                            device=args.hip_device, extent=extent)

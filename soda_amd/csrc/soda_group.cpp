@@ -66,6 +66,10 @@ struct Slab {
   int64_t copy_bytes = 0;
   int rc = 0;
   std::string error;
+  // the slab's share of a residual run (32 bytes, made at create when the
+  // plan has a residual), and how its last interval took it
+  DeviceBuffer res;
+  int32_t res_mode = 0, res_fused = 0;
 };
 
 // Transfer model behind the choice of the exchange interval.  A peer copy
@@ -98,6 +102,11 @@ struct soda_hip_group {
   std::condition_variable cv_job, cv_done;
   int64_t job = 0;             // number of the run the workers should enqueue
   int32_t job_iterate = 0;
+  bool job_residual = false;
+  // iterations the state has seen since soda_hip_group_load / _loaded: the
+  // box of a residual run is that of all of them
+  int64_t iters_since_load = 0;
+  bool last_run_residual = false;
   int finished = 0;
   bool stop = false;
   std::atomic<bool> failed{false};
@@ -353,8 +362,10 @@ int enqueue_exchange(soda_hip_group* g, int s, int64_t j) {
   return SODA_HIP_OK;
 }
 
+// box_iterate > 0: the run's last interval, which takes the slab's share of
+// the residual over the box of that many iterations
 int enqueue_interval(soda_hip_group* g, int s, int64_t j, int32_t iters,
-                     bool exchanged) {
+                     bool exchanged, int32_t box_iterate) {
   Slab& me = *g->slabs[s];
   const int n = (int)g->slabs.size();
   const bool overlap = !(g->desc.flags & SODA_HIP_GROUP_NO_OVERLAP);
@@ -395,9 +406,15 @@ int enqueue_interval(soda_hip_group* g, int s, int64_t j, int32_t iters,
   std::vector<const void*> ins(cur.begin(), cur.end());
   for (auto& prm : me.params) ins.push_back(prm.ptr);
   std::vector<void*> outs = g->outputs_of(me, j);
+  const ResidualRun res = {me.res.ptr, box_iterate};
   if (int rc = run_core(me.prog, outs.data(), ins.data(), me.extent, me.origin,
-                        g->desc.extent, iters, me.main, -1, &run))
+                        g->desc.extent, iters, me.main, -1, &run, 1,
+                        box_iterate > 0 ? &res : nullptr))
     return rc;
+  if (box_iterate > 0) {
+    me.res_mode = me.prog->last_res_mode;
+    me.res_fused = me.prog->last_res_fused;
+  }
   if (after) HIP_TRY(hipEventRecord(after, me.main));
   me.launches += me.prog->last_launches;
   me.split_passes += me.prog->last_split;
@@ -408,7 +425,7 @@ int enqueue_interval(soda_hip_group* g, int s, int64_t j, int32_t iters,
 // starts at interval j0.  Threaded: before a copy is ordered behind a
 // neighbour's `sendable`, that neighbour's thread must have RECORDED it.
 int enqueue_slab_run(soda_hip_group* g, int s, int64_t j0, int32_t iterate,
-                     bool fresh) {
+                     bool fresh, int32_t box_iterate) {
   const int n = (int)g->slabs.size();
   Slab& me = *g->slabs[s];
   int32_t done = 0;
@@ -425,7 +442,9 @@ int enqueue_slab_run(soda_hip_group* g, int s, int64_t j0, int32_t iterate,
           }
       if (int rc = enqueue_exchange(g, s, j)) return rc;
     }
-    if (int rc = enqueue_interval(g, s, j, k, exchange)) return rc;
+    if (int rc = enqueue_interval(g, s, j, k, exchange,
+                                  done + k == iterate ? box_iterate : 0))
+      return rc;
     me.enqueued.store(j + 1, std::memory_order_release);
     fresh = !g->iterable;
     done += k;
@@ -436,16 +455,18 @@ int enqueue_slab_run(soda_hip_group* g, int s, int64_t j0, int32_t iterate,
 void worker_main(soda_hip_group* g, int s) {
   int64_t seen = 0;
   for (;;) {
-    int32_t iterate;
+    int32_t iterate, box_iterate;
     {
       std::unique_lock<std::mutex> lock(g->mu);
       g->cv_job.wait(lock, [&] { return g->stop || g->job > seen; });
       if (g->stop) return;
       seen = g->job;
       iterate = g->job_iterate;
+      box_iterate =
+          g->job_residual ? (int32_t)(g->iters_since_load + iterate) : 0;
     }
     Slab& me = *g->slabs[s];
-    me.rc = enqueue_slab_run(g, s, g->interval, iterate, g->fresh);
+    me.rc = enqueue_slab_run(g, s, g->interval, iterate, g->fresh, box_iterate);
     if (me.rc) {
       me.error = last_error_text();
       g->failed.store(true);
@@ -467,6 +488,7 @@ void destroy_slab(Slab& s) {
     if (s.ghosts_ready[i]) (void)hipEventDestroy(s.ghosts_ready[i]);
     if (s.sendable[i]) (void)hipEventDestroy(s.sendable[i]);
   }
+  if (s.res.ptr) (void)hipFree(s.res.ptr);
   if (s.main) (void)hipStreamDestroy(s.main);
   if (s.comm) (void)hipStreamDestroy(s.comm);
   if (s.prog) (void)soda_hip_program_destroy(s.prog);
@@ -502,8 +524,12 @@ int create_slab(soda_hip_group* g, int s, const void* code, size_t code_size) {
     if (int rc = ensure(me.params[k],
                         (size_t)plan.param_elems[k] * plan.elem_size[prm0 + k]))
       return rc;
+  if (plan.residual.present)
+    if (int rc = ensure(me.res, sizeof(soda_hip_residual_t))) return rc;
   return SODA_HIP_OK;
 }
+
+int group_run(soda_hip_group* g, int32_t iterate, bool residual);
 
 }  // namespace
 
@@ -695,6 +721,8 @@ int soda_hip_group_load(soda_hip_group_t* g,
   }
   g->loaded = true;
   g->fresh = true;
+  g->iters_since_load = 0;
+  g->last_run_residual = false;
   return SODA_HIP_OK;
 }
 
@@ -703,11 +731,30 @@ int soda_hip_group_loaded(soda_hip_group_t* g) {
   if (int rc = soda_hip_group_synchronize(g)) return rc;
   g->loaded = true;
   g->fresh = true;
+  g->iters_since_load = 0;
+  g->last_run_residual = false;
   return SODA_HIP_OK;
 }
 
 int soda_hip_group_run(soda_hip_group_t* g, int32_t iterate) {
+  return group_run(g, iterate, false);
+}
+
+int soda_hip_group_run_residual(soda_hip_group_t* g, int32_t iterate) {
+  return group_run(g, iterate, true);
+}
+
+}  // extern "C"
+
+namespace {
+
+int group_run(soda_hip_group* g, int32_t iterate, bool residual) {
   if (!g) return fail(SODA_HIP_ERR_INVALID, "group_run: NULL group");
+  if (residual && !g->plan.residual.present)
+    return fail(SODA_HIP_ERR_UNSUPPORTED,
+                "group_run_residual: the program has no residual kernels "
+                "(build it with LowerOptions.residual / sodac --hip-residual); "
+                "nothing was launched");
   if (!g->loaded)
     return fail(SODA_HIP_ERR_INVALID,
                 "group_run: no state (soda_hip_group_load first)");
@@ -719,10 +766,16 @@ int soda_hip_group_run(soda_hip_group_t* g, int32_t iterate) {
   const auto t0 = std::chrono::steady_clock::now();
   const int n = (int)g->slabs.size();
   const int32_t intervals = (iterate + g->every - 1) / g->every;
+  if (residual && g->iters_since_load + iterate > 0x7fffffffLL)
+    return fail(SODA_HIP_ERR_INVALID,
+                "group_run_residual: too many iterations since the load");
+  const int32_t box_iterate =
+      residual ? (int32_t)(g->iters_since_load + iterate) : 0;
   for (auto& s : g->slabs) {
     s->copies = s->launches = s->split_passes = 0;
     s->copy_bytes = 0;
     s->rc = 0;
+    s->res_mode = s->res_fused = 0;
   }
   int rc = SODA_HIP_OK;
   std::string why;
@@ -731,6 +784,7 @@ int soda_hip_group_run(soda_hip_group_t* g, int32_t iterate) {
     {
       std::lock_guard<std::mutex> lock(g->mu);
       g->job_iterate = iterate;
+      g->job_residual = residual;
       g->finished = 0;
       ++g->job;
     }
@@ -754,7 +808,8 @@ int soda_hip_group_run(soda_hip_group_t* g, int32_t iterate) {
       const bool exchange = !fresh && n > 1;
       for (int s = 0; exchange && s < n && !rc; ++s) rc = enqueue_exchange(g, s, j);
       for (int s = 0; s < n && !rc; ++s) {
-        rc = enqueue_interval(g, s, j, k, exchange);
+        rc = enqueue_interval(g, s, j, k, exchange,
+                              done + k == iterate ? box_iterate : 0);
         g->slabs[s]->enqueued.store(j + 1, std::memory_order_release);
       }
       fresh = !g->iterable;
@@ -777,6 +832,8 @@ int soda_hip_group_run(soda_hip_group_t* g, int32_t iterate) {
   g->interval += intervals;
   for (auto& s : g->slabs) s->enqueued.store(g->interval);
   g->fresh = !g->iterable;      // a result's ghost rows are stale
+  g->iters_since_load += iterate;
+  g->last_run_residual = residual && !rc;
   st.enqueue_ms = std::chrono::duration<float, std::milli>(
                       std::chrono::steady_clock::now() - t0).count();
   if (rc) {
@@ -785,6 +842,10 @@ int soda_hip_group_run(soda_hip_group_t* g, int32_t iterate) {
   }
   return SODA_HIP_OK;
 }
+
+}  // namespace
+
+extern "C" {
 
 int soda_hip_group_synchronize(soda_hip_group_t* g) {
   if (!g) return fail(SODA_HIP_ERR_INVALID, "group_synchronize: NULL group");
@@ -853,6 +914,74 @@ int soda_hip_group_last_stats(soda_hip_group_t* g,
                               soda_hip_group_stats_t* stats) {
   if (!g || !stats) return fail(SODA_HIP_ERR_INVALID, "group_stats: NULL argument");
   *stats = g->stats;
+  return SODA_HIP_OK;
+}
+
+int soda_hip_group_residual(soda_hip_group_t* g,
+                            soda_hip_residual_t* result_host,
+                            soda_hip_residual_t* per_slab_host) {
+  if (!g || !result_host)
+    return fail(SODA_HIP_ERR_INVALID, "group_residual: NULL argument");
+  if (!g->last_run_residual)
+    return fail(SODA_HIP_ERR_INVALID,
+                "group_residual: the group's last run took no residual "
+                "(soda_hip_group_run_residual first)");
+  if (int rc = soda_hip_group_synchronize(g)) return rc;
+  soda_hip_residual_t sum;
+  memset(&sum, 0, sizeof sum);
+  for (size_t s = 0; s < g->slabs.size(); ++s) {
+    Slab& me = *g->slabs[s];
+    soda_hip_residual_t one;
+    HIP_TRY(hipSetDevice(me.device));
+    HIP_TRY(hipMemcpy(&one, me.res.ptr, sizeof one, hipMemcpyDeviceToHost));
+    if (per_slab_host) per_slab_host[s] = one;
+    // sums and maxima of exact per-cell values: no tolerance, any order
+    sum.changed += one.changed;
+    sum.unordered += one.unordered;
+    if (one.max_float_bits > sum.max_float_bits)
+      sum.max_float_bits = one.max_float_bits;
+    if (one.max_int > sum.max_int) sum.max_int = one.max_int;
+  }
+  *result_host = sum;
+  return SODA_HIP_OK;
+}
+
+int soda_hip_group_last_residual(soda_hip_group_t* g, int32_t slab,
+                                 int32_t* mode, int32_t* fused_iters) {
+  if (!g || !mode)
+    return fail(SODA_HIP_ERR_INVALID, "group_last_residual: NULL argument");
+  if (slab < 0 || slab >= (int32_t)g->slabs.size())
+    return fail(SODA_HIP_ERR_INVALID, "group_last_residual: no such slab");
+  *mode = g->last_run_residual ? g->slabs[slab]->res_mode : 0;
+  if (fused_iters)
+    *fused_iters = g->last_run_residual ? g->slabs[slab]->res_fused : 0;
+  return SODA_HIP_OK;
+}
+
+int soda_hip_group_run_until(soda_hip_group_t* g, int32_t max_iterate,
+                             int32_t check_every, double tol, uint64_t int_tol,
+                             soda_hip_residual_t* result_host,
+                             int32_t* iterations_done) {
+  if (!g) return fail(SODA_HIP_ERR_INVALID, "group_run_until: NULL group");
+  if (max_iterate < 1 || check_every < 1)
+    return fail(SODA_HIP_ERR_INVALID,
+                "group_run_until: max_iterate and check_every must be >= 1");
+  soda_hip_residual_t host;
+  memset(&host, 0, sizeof host);
+  int32_t done = 0;
+  while (done < max_iterate) {
+    const int32_t n =
+        max_iterate - done < check_every ? max_iterate - done : check_every;
+    if (int rc = group_run(g, n, true)) return rc;
+    if (int rc = soda_hip_group_residual(g, &host, nullptr)) return rc;
+    done += n;
+    double max_float;
+    memcpy(&max_float, &host.max_float_bits, sizeof max_float);
+    if (host.unordered == 0 && max_float <= tol && host.max_int <= int_tol)
+      break;
+  }
+  if (result_host) *result_host = host;
+  if (iterations_done) *iterations_done = done;
   return SODA_HIP_OK;
 }
 

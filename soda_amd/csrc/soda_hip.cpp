@@ -803,6 +803,55 @@ void residual_box(const soda_hip_plan_t& plan, const int32_t* ext,
     }
 }
 
+// The same for a slab of a larger grid (soda_hip.h,
+// soda_hip_plan_residual_slab_box): the box of the GLOBAL grid, of which the
+// slab counts the rows [keep_lo, keep_hi) of its last dimension, in the
+// coordinates of the slab's arrays (cell 0 at `origin`) and clipped to them.
+// Slabs whose kept rows partition the global rows partition the global box.
+void residual_slab_box(const soda_hip_plan_t& plan, const int32_t* gext,
+                       const int32_t* origin, const int32_t* ext,
+                       int32_t keep_lo, int32_t keep_hi, int32_t iterate,
+                       soda_hip_resbox_t* box) {
+  residual_box(plan, gext, iterate, box);
+  const int dim = plan.dim;
+  for (int o = 0; o < plan.num_outputs; ++o)
+    for (int d = 0; d < dim; ++d) {
+      int64_t l = (int64_t)box->lo[o][d] - origin[d];
+      int64_t h = (int64_t)box->hi[o][d] - origin[d];
+      int64_t a = 0, b = ext[d];
+      if (d == dim - 1) {
+        if (keep_lo > a) a = keep_lo;
+        if (keep_hi < b) b = keep_hi;
+        if (b < a) b = a;
+      }
+      if (l < a) l = a;
+      if (l > b) l = b;
+      if (h > b) h = b;
+      if (h < l) h = l;
+      box->lo[o][d] = (int32_t)l;
+      box->hi[o][d] = (int32_t)h;
+    }
+}
+
+// The box for a launch on rows [row0, row0 + rows) of the last dimension:
+// kernels count in the coordinates of the arrays their launch addresses.
+soda_hip_resbox_t shifted_box(const soda_hip_plan_t& plan,
+                              const soda_hip_resbox_t& box, int32_t row0,
+                              int32_t rows) {
+  soda_hip_resbox_t out = box;
+  const int ax = plan.dim - 1;
+  for (int o = 0; o < plan.num_outputs; ++o) {
+    int64_t l = (int64_t)box.lo[o][ax] - row0, h = (int64_t)box.hi[o][ax] - row0;
+    if (l < 0) l = 0;
+    if (l > rows) l = rows;
+    if (h > rows) h = rows;
+    if (h < l) h = l;
+    out.lo[o][ax] = (int32_t)l;
+    out.hi[o][ax] = (int32_t)h;
+  }
+  return out;
+}
+
 int64_t ceil_div(int64_t a, int64_t b) { return a <= 0 ? 0 : (a + b - 1) / b; }
 int64_t floor_div(int64_t a, int64_t b) { return a <= 0 ? 0 : a / b; }
 
@@ -855,6 +904,34 @@ int schedule(const soda_hip_plan_t& plan, const std::vector<double>& pass_ns,
     ++count[pick[n]];
     ++*total;
   }
+  return SODA_HIP_OK;
+}
+
+int residual_order(const soda_hip_plan_t& plan,
+                   const std::vector<double>& pass_ns, int32_t iterate,
+                   int32_t* count, int32_t* total, int* res_pass,
+                   bool* res_twin) {
+  const char* g = getenv("SODA_HIP_RESIDUAL_GENERIC");
+  const bool generic = g && !strcmp(g, "1");
+  *res_pass = -1;
+  *res_twin = false;
+  for (int i = 0; i < plan.num_passes && !generic && *res_pass < 0; ++i)
+    if (count[i] > 0 && plan.passes[i].num_kernels == 1 &&
+        plan.kernels[plan.passes[i].kernel[0]].twin >= 0) {
+      *res_pass = i;
+      *res_twin = true;
+    }
+  if (*res_pass >= 0) return SODA_HIP_OK;
+  const int one = plan.num_passes - 1;   // fused_iters 1 (check_plan)
+  if (!count[one]) {
+    for (int i = 0; i < plan.num_passes; ++i) count[i] = 0;
+    *total = 0;
+    if (iterate > 1)
+      if (int rc = schedule(plan, pass_ns, iterate - 1, count, total)) return rc;
+    ++count[one];
+    ++*total;
+  }
+  *res_pass = one;
   return SODA_HIP_OK;
 }
 
@@ -930,15 +1007,28 @@ namespace soda_detail {
 int plan_launches(const soda_hip_plan_t& plan,
                   std::map<ExtentKey, ExtentPlan>* cache, const int32_t* ext,
                   const int32_t* count, int32_t total, int32_t iterate,
-                  const SlabRun* slab, std::vector<PassLaunch>* out) {
+                  const SlabRun* slab, std::vector<PassLaunch>* out,
+                  int res_pass, bool res_twin) {
   const int ax = plan.dim - 1;
   const int32_t rows = ext[ax];
   const Cone* cone = slab ? &slab->cone : nullptr;
   out->clear();
   out->reserve(total);
+  // the order launched: deepest first -- and, in a run that takes a residual,
+  // one launch of the pass that takes it moved to the end.  The cone below is
+  // that of THIS order: a deep pass that goes last reads further than the
+  // shallow one it displaced, so the passes before it must cover more rows.
+  std::vector<int> order;
+  order.reserve(total);
+  for (int i = 0; i < plan.num_passes; ++i)
+    for (int c = 0; c < count[i] - (i == res_pass ? 1 : 0); ++c)
+      order.push_back(i);
+  if (res_pass >= 0 && res_pass < plan.num_passes && count[res_pass] > 0)
+    order.push_back(res_pass);
   int done = 0, done_iters = 0;
-  for (int i = 0; i < plan.num_passes; ++i) {
-    for (int c = 0; c < count[i]; ++c, ++done) {
+  {
+    for (; done < (int)order.size(); ++done) {
+      const int i = order[done];
       PassLaunch L;
       memset(&L, 0, sizeof L);
       L.pass = i;
@@ -962,7 +1052,11 @@ int plan_launches(const soda_hip_plan_t& plan,
       const bool first = done == 0, last = done + 1 == total;
       L.wait = first && slab && slab->ghosts_ready;
       L.record = last && slab && slab->sendable;
-      const int k0 = plan.passes[i].kernel[0];
+      // (a last pass that runs as its twin is cut by the twin's chunks)
+      int k0 = plan.passes[i].kernel[0];
+      if (last && res_twin && i == res_pass && plan.passes[i].num_kernels == 1 &&
+          plan.kernels[k0].twin >= 0)
+        k0 = plan.kernels[k0].twin;
       if ((L.wait || L.record) && plan.passes[i].num_kernels == 1 &&
           plan.kernels[k0].march_dim == plan.dim) {
         int32_t sub[SODA_HIP_MAX_DIM];
@@ -1091,8 +1185,8 @@ int run_core(soda_hip_program_t* p, void* const* outputs,
   if (!p || !outputs || !inputs || !extent)
     return fail(SODA_HIP_ERR_INVALID, "run_device: NULL argument");
   const soda_hip_plan_t& plan = p->plan;
-  if (res && (slab || batch != 1 || force_pass >= 0 || origin ||
-              global_extent || !plan.residual.present || !res->dev))
+  if (res && (batch != 1 || force_pass >= 0 || !plan.residual.present ||
+              !res->dev || res->box_iterate < iterate))
     return fail(SODA_HIP_ERR_INVALID, "run_core: bad residual run");
   if (batch < 1 || (batch > 1 && (!plan.batched || slab)))
     return fail(SODA_HIP_ERR_INVALID, "run_core: bad batch");
@@ -1275,33 +1369,14 @@ int run_core(soda_hip_program_t* p, void* const* outputs,
   int res_last = -1;
   bool res_twin = false;
   if (res) {
-    const char* g = getenv("SODA_HIP_RESIDUAL_GENERIC");
-    const bool generic = g && !strcmp(g, "1");
-    for (int i = 0; i < plan.num_passes && !generic && res_last < 0; ++i)
-      if (count[i] > 0 && plan.passes[i].num_kernels == 1 &&
-          plan.kernels[plan.passes[i].kernel[0]].twin >= 0) {
-        res_last = i;
-        res_twin = true;
-      }
-    if (res_last < 0) {
-      const int one = plan.num_passes - 1;   // fused_iters 1 (check_plan)
-      if (!count[one]) {
-        for (int i = 0; i < plan.num_passes; ++i) count[i] = 0;
-        total = 0;
-        if (iterate > 1) {
-          ExtentKey key;
-          for (int d = 0; d < SODA_HIP_MAX_DIM; ++d) key[d] = base.extent[d];
-          auto it = measured.find(key);
-          const std::vector<double>& pass_ns =
-              it != measured.end() ? it->second : ep->model_ns;
-          if (int rc = schedule(plan, pass_ns, iterate - 1, count, &total))
-            return rc;
-        }
-        ++count[one];
-        ++total;
-      }
-      res_last = one;
-    }
+    ExtentKey key;
+    for (int d = 0; d < SODA_HIP_MAX_DIM; ++d) key[d] = base.extent[d];
+    auto it = measured.find(key);
+    const std::vector<double>& pass_ns =
+        it != measured.end() ? it->second : ep->model_ns;
+    if (int rc = residual_order(plan, pass_ns, iterate, count, &total,
+                                &res_last, &res_twin))
+      return rc;
   }
 
   if (p->debug) base.buf[SODA_HIP_MAX_TENSORS - 1] = p->debug;
@@ -1352,18 +1427,19 @@ int run_core(soda_hip_program_t* p, void* const* outputs,
 
   std::vector<PassLaunch> launches;
   if (int rc = plan_launches(plan, &extents, base.extent, count, total,
-                             iterate, slab, &launches))
+                             iterate, slab, &launches, res_last, res_twin))
     return rc;
   soda_hip_resbox_t res_box;
   if (res) {
-    // the pass that takes the residual goes last
-    for (size_t q = launches.size(); q-- > 0;)
-      if (launches[q].pass == res_last) {
-        std::rotate(launches.begin() + q, launches.begin() + q + 1,
-                    launches.end());
-        break;
-      }
-    residual_box(plan, base.extent, res->box_iterate, &res_box);
+    // (the pass that takes the residual is the last of `launches`, and the
+    // cone of every pass before it is that of this order: plan_launches.)
+    // The cells counted: the global grid's box, of which a slab takes its
+    // kept rows -- the ghost rows of the result, which the last pass writes
+    // too, lie outside and are not counted.
+    residual_slab_box(plan, base.gextent, base.origin, base.extent,
+                      cone ? cone->keep_lo : 0,
+                      cone ? cone->keep_hi : base.extent[plan.dim - 1],
+                      res->box_iterate, &res_box);
     // zeroed inside the call, on the caller's stream, by a kernel of the
     // program: a captured call zeroes and refills the struct at every replay
     // (as a 32-byte memset node the zeroing did not survive a replay)
@@ -1414,7 +1490,18 @@ int run_core(soda_hip_program_t* p, void* const* outputs,
     if (int rc = extent_plan(plan, &extents, args.extent, &use, batch))
       return rc;
     p->last_rows += L.hi - L.lo;
-    const int k0 = plan.passes[i].kernel[0];
+    int k0 = plan.passes[i].kernel[0];
+    // The last pass of a residual run: as its twin (both parts of a split
+    // pass -- one struct, one box, every chunk in exactly one part), or
+    // followed by `<app>_residual`.  The box in the coordinates of the rows
+    // this launch addresses.
+    const bool take_twin = res && res_twin && last_pass;
+    const bool take_generic = res && !res_twin && last_pass;
+    void* const rdev = take_twin ? res->dev : nullptr;
+    soda_hip_resbox_t lbox;
+    if (take_twin || take_generic)
+      lbox = shifted_box(plan, res_box, L.lo, L.hi - L.lo);
+    if (take_twin) k0 = plan.kernels[k0].twin;
     if (L.split && split_in_order()) {
       // both parts on the caller's stream, the part that does not depend on
       // the exchange first: no hand-over between streams, but the two launches
@@ -1423,22 +1510,32 @@ int run_core(soda_hip_program_t* p, void* const* outputs,
       const TileRange boundary = {ax, L.bnd_lo, hole, L.chunks - hole};
       const TileRange interior = {ax, 0, L.bnd_lo, hole};
       if (!L.record) {       // first pass: interior, wait, boundary
-        if (int rc = launch(p, k0, args, use->geo[k0].tile, stream, &interior))
+        if (int rc = launch(p, k0, args, use->geo[k0].tile, stream, &interior, 1,
+                            rdev, &lbox))
           return rc;
         HIP_TRY(hipStreamWaitEvent(stream, slab->ghosts_ready, 0));
-        if (int rc = launch(p, k0, args, use->geo[k0].tile, stream, &boundary))
+        if (int rc = launch(p, k0, args, use->geo[k0].tile, stream, &boundary, 1,
+                            rdev, &lbox))
           return rc;
       } else {               // last pass: (wait,) boundary, signal, interior
         if (L.wait) HIP_TRY(hipStreamWaitEvent(stream, slab->ghosts_ready, 0));
-        if (int rc = launch(p, k0, args, use->geo[k0].tile, stream, &boundary))
+        if (int rc = launch(p, k0, args, use->geo[k0].tile, stream, &boundary, 1,
+                            rdev, &lbox))
           return rc;
         HIP_TRY(hipEventRecord(slab->sendable, stream));
-        if (int rc = launch(p, k0, args, use->geo[k0].tile, stream, &interior))
+        if (int rc = launch(p, k0, args, use->geo[k0].tile, stream, &interior, 1,
+                            rdev, &lbox))
           return rc;
       }
       p->last_launches += 2;
       if (i == 0) ++p->last_fused;
       ++p->last_split;
+      if (take_generic) {
+        // behind both parts: it reads all of what the pass wrote and writes
+        // the struct only, so `sendable` need not wait for it
+        if (int rc = launch_residual(p, args, stream, res->dev, lbox)) return rc;
+        ++p->last_launches;
+      }
     } else if (L.split) {
       // the boundary chunks on the program's side stream, the interior on the
       // caller's: the two share the GPU, the copies run underneath
@@ -1450,32 +1547,37 @@ int run_core(soda_hip_program_t* p, void* const* outputs,
       if (L.wait) HIP_TRY(hipStreamWaitEvent(p->side, slab->ghosts_ready, 0));
       const int32_t hole = L.bnd_hi - L.bnd_lo;
       const TileRange boundary = {ax, L.bnd_lo, hole, L.chunks - hole};
-      if (int rc = launch(p, k0, args, use->geo[k0].tile, p->side, &boundary))
+      if (int rc = launch(p, k0, args, use->geo[k0].tile, p->side, &boundary, 1,
+                            rdev, &lbox))
         return rc;
       if (L.record) HIP_TRY(hipEventRecord(slab->sendable, p->side));
       HIP_TRY(hipEventRecord(p->ev_bnd[turn], p->side));
       const TileRange interior = {ax, 0, L.bnd_lo, hole};
-      if (int rc = launch(p, k0, args, use->geo[k0].tile, stream, &interior))
+      if (int rc = launch(p, k0, args, use->geo[k0].tile, stream, &interior, 1,
+                            rdev, &lbox))
         return rc;
       HIP_TRY(hipStreamWaitEvent(stream, p->ev_bnd[turn], 0));
       p->last_launches += 2;
       if (i == 0) ++p->last_fused;
       ++p->last_split;
+      if (take_generic) {
+        if (int rc = launch_residual(p, args, stream, res->dev, lbox)) return rc;
+        ++p->last_launches;
+      }
     } else {
       if (L.wait) HIP_TRY(hipStreamWaitEvent(stream, slab->ghosts_ready, 0));
       for (int k = 0; k < plan.passes[i].num_kernels; ++k) {
         int kk = plan.passes[i].kernel[k];
-        const bool twin = res && res_twin && last_pass;
-        if (twin) kk = plan.kernels[kk].twin;
+        if (take_twin) kk = plan.kernels[kk].twin;
         int rc = launch(p, kk, args, use->geo[kk].tile, stream, nullptr, batch,
-                        twin ? res->dev : nullptr, &res_box);
+                        rdev, &lbox);
         if (rc) return rc;
         ++p->last_launches;
         if (i == 0) ++p->last_fused;
       }
-      if (res && !res_twin && last_pass) {
+      if (take_generic) {
         // cur: what the pass just wrote; prev: what it read
-        if (int rc = launch_residual(p, args, stream, res->dev, res_box))
+        if (int rc = launch_residual(p, args, stream, res->dev, lbox))
           return rc;
         ++p->last_launches;
       }
@@ -1747,10 +1849,99 @@ int soda_hip_run_device_slab(soda_hip_program_t* p, void* const* outputs,
                   stream_, -1, &s);
 }
 
+int soda_hip_run_device_slab_residual(
+    soda_hip_program_t* p, void* const* outputs, const void* const* inputs,
+    const int32_t* extent, const int32_t* origin, const int32_t* global_extent,
+    int32_t iterate, int32_t box_iterate, const soda_hip_slab_run_t* run,
+    void* residual_dev, void* stream_) {
+  if (!p || !outputs || !inputs || !extent || !run || !residual_dev)
+    return fail(SODA_HIP_ERR_INVALID, "run_device_slab_residual: NULL argument");
+  p->last_res_mode = 0;
+  p->last_res_fused = 0;
+  p->last_launches = 0;
+  p->last_fused = 0;
+  if (int rc = check_residual(p, outputs, extent, residual_dev,
+                              "run_device_slab_residual"))
+    return rc;
+  if (box_iterate < iterate)
+    return fail(SODA_HIP_ERR_INVALID,
+                "run_device_slab_residual: box_iterate counts the iterations "
+                "the state has seen, this call's included: it cannot be less "
+                "than iterate; nothing was launched");
+  SlabRun s;
+  if (int rc = slab_run(run, extent, p->plan.dim - 1, &s)) return rc;
+  const ResidualRun res = {residual_dev, box_iterate};
+  return run_core(p, outputs, inputs, extent, origin, global_extent, iterate,
+                  stream_, -1, &s, 1, &res);
+}
+
+int soda_hip_plan_residual_slab_box(const soda_hip_plan_t* plan,
+                                    const int32_t* global_extent,
+                                    const int32_t* origin,
+                                    const int32_t* extent, int32_t keep_lo,
+                                    int32_t keep_hi, int32_t iterate,
+                                    int32_t* lo, int32_t* hi) {
+  if (!plan || !global_extent || !origin || !extent || !lo || !hi)
+    return fail(SODA_HIP_ERR_INVALID, "plan_residual_slab_box: NULL argument");
+  if (int rc = check_plan(plan)) return rc;
+  if (!plan->residual.present)
+    return fail(SODA_HIP_ERR_UNSUPPORTED,
+                "plan_residual_slab_box: the plan has no residual");
+  if (iterate < 1)
+    return fail(SODA_HIP_ERR_INVALID, "plan_residual_slab_box: iterate < 1");
+  for (int d = 0; d < plan->dim; ++d)
+    if (extent[d] < 1 || origin[d] < 0 ||
+        (int64_t)origin[d] + extent[d] > global_extent[d])
+      return fail(SODA_HIP_ERR_INVALID,
+                  "plan_residual_slab_box: the slab does not lie in the "
+                  "global grid");
+  if (keep_lo < 0 || keep_hi > extent[plan->dim - 1] || keep_lo > keep_hi)
+    return fail(SODA_HIP_ERR_INVALID,
+                "plan_residual_slab_box: [keep_lo, keep_hi) must be a range of "
+                "the slab's last dimension");
+  soda_hip_resbox_t box;
+  residual_slab_box(*plan, global_extent, origin, extent, keep_lo, keep_hi,
+                    iterate, &box);
+  for (int o = 0; o < plan->num_outputs; ++o)
+    for (int d = 0; d < plan->dim; ++d) {
+      lo[o * plan->dim + d] = box.lo[o][d];
+      hi[o * plan->dim + d] = box.hi[o][d];
+    }
+  return SODA_HIP_OK;
+}
+
+static int plan_launches_c(const soda_hip_plan_t* plan, const int32_t* extent,
+                           int32_t iterate, const soda_hip_slab_run_t* run,
+                           int32_t capacity, soda_hip_launch_info_t* launches,
+                           int32_t* count, int32_t* residual_mode);
+
 int soda_hip_plan_launches(const soda_hip_plan_t* plan, const int32_t* extent,
                            int32_t iterate, const soda_hip_slab_run_t* run,
                            int32_t capacity, soda_hip_launch_info_t* launches,
                            int32_t* count) {
+  return plan_launches_c(plan, extent, iterate, run, capacity, launches, count,
+                         nullptr);
+}
+
+int soda_hip_plan_launches_residual(const soda_hip_plan_t* plan,
+                                    const int32_t* extent, int32_t iterate,
+                                    const soda_hip_slab_run_t* run,
+                                    int32_t capacity,
+                                    soda_hip_launch_info_t* launches,
+                                    int32_t* count, int32_t* mode) {
+  if (!mode) return fail(SODA_HIP_ERR_INVALID, "plan_launches: bad argument");
+  if (plan && !plan->residual.present)
+    return fail(SODA_HIP_ERR_UNSUPPORTED,
+                "plan_launches_residual: the plan has no residual");
+  return plan_launches_c(plan, extent, iterate, run, capacity, launches, count,
+                         mode);
+}
+
+// residual_mode != NULL: the launches of a run that takes a residual
+static int plan_launches_c(const soda_hip_plan_t* plan, const int32_t* extent,
+                           int32_t iterate, const soda_hip_slab_run_t* run,
+                           int32_t capacity, soda_hip_launch_info_t* launches,
+                           int32_t* count, int32_t* residual_mode) {
   if (!plan || !extent || !count || capacity < 0 || (capacity && !launches))
     return fail(SODA_HIP_ERR_INVALID, "plan_launches: bad argument");
   if (iterate < 1) return fail(SODA_HIP_ERR_INVALID, "cannot iterate < 1 times");
@@ -1768,9 +1959,17 @@ int soda_hip_plan_launches(const soda_hip_plan_t* plan, const int32_t* extent,
   if (int rc = extent_plan(*plan, &cache, ext, &ep)) return rc;
   int32_t per_pass[SODA_HIP_MAX_PASSES], total = 0;
   if (int rc = schedule(*plan, ep->model_ns, iterate, per_pass, &total)) return rc;
+  int res_pass = -1;
+  bool res_twin = false;
+  if (residual_mode) {
+    if (int rc = residual_order(*plan, ep->model_ns, iterate, per_pass, &total,
+                                &res_pass, &res_twin))
+      return rc;
+    *residual_mode = res_twin ? 1 : 2;
+  }
   std::vector<PassLaunch> list;
   if (int rc = plan_launches(*plan, &cache, ext, per_pass, total, iterate,
-                             run ? &s : nullptr, &list))
+                             run ? &s : nullptr, &list, res_pass, res_twin))
     return rc;
   *count = (int32_t)list.size();
   for (int32_t i = 0; i < *count && i < capacity; ++i) {

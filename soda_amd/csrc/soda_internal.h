@@ -164,7 +164,10 @@ namespace soda_detail {
 // A run that also takes the residual of its last iteration
 // (soda_hip_run_device_residual): where the struct goes, and the iterations
 // the counted box is that of (soda_hip_run_device_until runs chunk after
-// chunk: the box is the one after all iterations done so far)
+// chunk: the box is the one after all iterations done so far; a slab run
+// between two exchanges: the iterations since the state was the caller's).
+// On a slab (run_core's `slab`, `origin`, `global_extent`) the box is the
+// global grid's, cut to the slab's kept rows (soda_hip_plan_residual_slab_box)
 struct ResidualRun {
   void* dev;
   int32_t box_iterate;
@@ -206,7 +209,19 @@ struct PassLaunch {
 int plan_launches(const soda_hip_plan_t& plan,
                   std::map<ExtentKey, ExtentPlan>* cache, const int32_t* ext,
                   const int32_t* count, int32_t total, int32_t iterate,
-                  const SlabRun* slab, std::vector<PassLaunch>* out);
+                  const SlabRun* slab, std::vector<PassLaunch>* out,
+                  int res_pass = -1, bool res_twin = false);
+
+// A residual run keeps the multiset of passes `count` / `total` scheduled for
+// `iterate` iterations and names the pass that goes last (*res_pass) and
+// whether it runs as its twin: the deepest scheduled pass whose kernel has
+// one; else the one-iteration pass, behind which `<app>_residual` runs --
+// taken out of a deeper pass's count where the schedule had none (iterate - 1
+// iterations rescheduled by `pass_ns`, one added).
+int residual_order(const soda_hip_plan_t& plan,
+                   const std::vector<double>& pass_ns, int32_t iterate,
+                   int32_t* count, int32_t* total, int* res_pass,
+                   bool* res_twin);
 
 // tiles, modelled pass times and schedules of `plan` on `ext` (all
 // SODA_HIP_MAX_DIM entries filled) for launches over `batch` grids,

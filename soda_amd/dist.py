@@ -243,7 +243,8 @@ class StreamOverlap:
 def run(slab: Slab, src: Sequence, work_a: Sequence, work_b: Sequence,
         step: Callable[..., None],
         iterate: int, dist_module, group=None, ghosts_fresh: bool = True,
-        overlap: Optional[StreamOverlap] = None):
+        overlap: Optional[StreamOverlap] = None,
+        residual: Optional[int] = None, iterations_before: int = 0):
   """Advances the program `iterate` iterations.  `src` holds the inputs (own
   rows + ghosts); `work_a` / `work_b` are same-shaped work arrays the state
   ping-pongs through (`work_b` is only touched when more than one exchange
@@ -254,16 +255,30 @@ def run(slab: Slab, src: Sequence, work_a: Sequence, work_b: Sequence,
   ghost rows of `src` with the neighbours' rows (bench.py's chained steps rely
   on exactly that): do not pass a view of data you need unchanged.
   `overlap`: hide the exchanges under the compute; `step` is then called as
-  step(dst, src, extent, iters, **overlap.step_kwargs(...))."""
+  step(dst, src, extent, iters, **overlap.step_kwargs(...)).
+  `residual`: the device address of 32 bytes on this rank.  The LAST round is
+  then called as step(..., keep=slab.keep, residual=residual, box_iterate=n),
+  n = `iterations_before` + `iterate`: the iterations the state has seen since
+  it was the program's input (chained runs pass what the earlier ones did).
+  An engine built on Program.run_device hands these on together with
+  origin=slab.origin and global_extent=slab.extent
+  (soda_hip_run_device_slab_residual): the struct then holds this rank's share
+  of the residual of the last iteration, over its own rows of the global box;
+  `combine_residual` folds the ranks' shares.  Earlier rounds are untouched."""
   cur, nxt = list(src), list(work_a)
   spare = list(work_b)
   done = 0
   fresh = ghosts_fresh
   while done < iterate:
     k = min(slab.exchange_every, iterate - done)
+    extra = {}
+    if residual is not None and done + k == iterate:
+      extra = dict(keep=slab.keep, residual=residual,
+                   box_iterate=iterations_before + iterate)
     if overlap is not None:
       token = 0 if fresh else overlap.start(slab, cur, dist_module, group)
-      step(nxt, cur, slab.local_extent, k, **overlap.step_kwargs(slab, token))
+      extra.update(overlap.step_kwargs(slab, token))
+      step(nxt, cur, slab.local_extent, k, **extra)
       if done == 0:
         cur, nxt = nxt, spare
       else:
@@ -273,7 +288,7 @@ def run(slab: Slab, src: Sequence, work_a: Sequence, work_b: Sequence,
       continue
     if not fresh:
       exchange(slab, cur, dist_module, group)
-    step(nxt, cur, slab.local_extent, k)
+    step(nxt, cur, slab.local_extent, k, **extra)
     if done == 0:
       cur, nxt = nxt, spare          # src drops out of the rotation
     else:
@@ -281,6 +296,81 @@ def run(slab: Slab, src: Sequence, work_a: Sequence, work_b: Sequence,
     done += k
     fresh = False
   return cur
+
+
+def fold_residuals(parts: Sequence[bytes]):
+  """The residual of the whole grid from the ranks' 32-byte structs
+  (soda_hip_residual_t, little-endian): counts add, maxima take the larger --
+  sums and maxima of exact per-cell values, so the fold is exact in any order.
+  Returns a runtime.Residual."""
+  import struct
+  from soda_amd import runtime
+  changed = unordered = max_bits = max_int = 0
+  for raw in parts:
+    c, u, f, m = struct.unpack('<4Q', bytes(raw))
+    changed, unordered = changed + c, unordered + u
+    max_bits, max_int = max(max_bits, f), max(max_int, m)
+  return runtime.Residual(changed, unordered,
+                          struct.unpack('<d', struct.pack('<Q', max_bits))[0],
+                          max_int)
+
+
+def combine_residual(raw32, dist_module, group=None):
+  """Every rank's share of a residual -> the residual of the whole grid, the
+  same on every rank.  `raw32`: this rank's 32 bytes (bytes, a numpy array or
+  a torch tensor of 32 bytes, on the host or -- for a transport that moves
+  device memory, RCCL -- on the device).  The bytes are all_gather'ed and
+  folded on the host: never all_reduce'd -- `max_int` exceeds 2^63 for uint64
+  cells, and no transport reduces unsigned 64-bit integers."""
+  import torch
+  if isinstance(raw32, torch.Tensor):
+    mine = raw32.contiguous().view(torch.uint8).reshape(-1)
+  else:
+    mine = torch.frombuffer(bytearray(bytes(raw32)), dtype=torch.uint8)
+  if mine.numel() != 32:
+    raise util.InputError('combine_residual: a residual is 32 bytes, got %d' %
+                          mine.numel())
+  world = dist_module.get_world_size(group) if group is not None else \
+      dist_module.get_world_size()
+  parts = [torch.empty_like(mine) for _ in range(world)]
+  if group is not None:
+    dist_module.all_gather(parts, mine, group=group)
+  else:
+    dist_module.all_gather(parts, mine)
+  return fold_residuals([bytes(p.cpu().numpy().tobytes()) for p in parts])
+
+
+def run_until(slab: Slab, src: Sequence, work_a: Sequence, work_b: Sequence,
+              step: Callable[..., None], residual: int,
+              fetch: Callable[[], bytes], tol: float, max_iterate: int,
+              dist_module, check_every: int = 8, int_tol: int = 0, group=None,
+              overlap: Optional[StreamOverlap] = None):
+  """Iterates until converged, one rank per GPU: `check_every` iterations at a
+  time through run(..., residual=residual) (the last chunk may be shorter);
+  after each, `fetch()` -- the engine's: wait for this rank's streams, return
+  the 32 bytes at `residual` -- and `combine_residual`.  Stops when the
+  combined struct has `unordered == 0`, `max_float <= tol` and `max_int <=
+  int_tol`, or after `max_iterate` iterations: the rule of
+  soda_hip_run_device_until.  Every rank folds the same structs, so every rank
+  takes the same decision.  The state rotates through the THREE sets `src`,
+  `work_a` and `work_b`: the first chunk only reads `src`, later chunks may
+  write any of them.  Returns (the list that holds the result, iterations
+  done, Residual)."""
+  if max_iterate < 1 or check_every < 1:
+    raise util.InputError('run_until: max_iterate and check_every must be >= 1')
+  pool = [list(src), list(work_a), list(work_b)]
+  cur, done, res = pool[0], 0, None
+  while done < max_iterate:
+    n = min(check_every, max_iterate - done)
+    others = [x for x in pool if x[0] is not cur[0]]
+    cur = run(slab, cur, others[0], others[1], step, n, dist_module, group,
+              ghosts_fresh=done == 0, overlap=overlap, residual=residual,
+              iterations_before=done)
+    done += n
+    res = combine_residual(fetch(), dist_module, group)
+    if res.unordered == 0 and res.max_float <= tol and res.max_int <= int_tol:
+      break
+  return cur, done, res
 
 
 def auto_exchange_every(stencil: core.Stencil, extent: Sequence[int],

@@ -72,10 +72,13 @@ def _symbol_bytes(code: bytes, sym: Tuple[int, int, int, int]) -> bytes:
   return code[off:off + size]
 
 
-def isa_key(code: bytes, kernel: str) -> Optional[str]:
+def isa_key(code: bytes, kernel: str, placed: bool = True) -> Optional[str]:
   """Content key of ONE kernel of a code object: sha256 over its machine code
   and its kernel descriptor (`<kernel>.kd`: register counts, LDS, flags).
-  None if the symbols cannot be read."""
+  None if the symbols cannot be read.  placed=False leaves out the one field
+  of the descriptor that says WHERE in the object the code lies
+  (kernel_code_entry_byte_offset, bytes 16..23): the key then compares one
+  kernel across two modules that hold other kernels beside it."""
   try:
     if code[:4] != b'\x7fELF':
       return None
@@ -86,14 +89,18 @@ def isa_key(code: bytes, kernel: str) -> Optional[str]:
     h.update(_symbol_bytes(code, syms[kernel]))
     kd = syms.get(kernel + '.kd')
     if kd:
-      h.update(_symbol_bytes(code, kd))
+      desc = _symbol_bytes(code, kd)
+      if not placed and len(desc) >= 24:
+        desc = desc[:16] + bytes(8) + desc[24:]
+      h.update(desc)
     return h.hexdigest()[:24]
   except Exception:      # noqa: BLE001 -- a malformed object has no key
     return None
 
 
-def isa_keys(code: bytes, kernels: Sequence[str]) -> Dict[str, Optional[str]]:
-  return {k: isa_key(code, k) for k in kernels}
+def isa_keys(code: bytes, kernels: Sequence[str],
+             placed: bool = True) -> Dict[str, Optional[str]]:
+  return {k: isa_key(code, k, placed) for k in kernels}
 
 
 def objdump() -> Optional[str]:

@@ -262,6 +262,27 @@ API = {
         ctypes.POINTER(Plan), _pi32, _i32, _pi32, _pi32
     ]),
     'soda_hip_last_residual': (ctypes.c_int, [_vp, _pi32, _pi32]),
+    'soda_hip_plan_residual_slab_box': (ctypes.c_int, [
+        ctypes.POINTER(Plan), _pi32, _pi32, _pi32, _i32, _i32, _i32, _pi32,
+        _pi32
+    ]),
+    'soda_hip_run_device_slab_residual': (ctypes.c_int, [
+        _vp, _pvp, _pvp, _pi32, _pi32, _pi32, _i32, _i32,
+        ctypes.POINTER(SlabRun), _vp, _vp
+    ]),
+    'soda_hip_plan_launches_residual': (ctypes.c_int, [
+        ctypes.POINTER(Plan), _pi32, _i32, ctypes.POINTER(SlabRun), _i32,
+        ctypes.POINTER(LaunchInfo), _pi32, _pi32
+    ]),
+    'soda_hip_group_run_residual': (ctypes.c_int, [_vp, _i32]),
+    'soda_hip_group_residual': (ctypes.c_int, [
+        _vp, ctypes.POINTER(ResidualStruct), ctypes.POINTER(ResidualStruct)
+    ]),
+    'soda_hip_group_last_residual': (ctypes.c_int, [_vp, _i32, _pi32, _pi32]),
+    'soda_hip_group_run_until': (ctypes.c_int, [
+        _vp, _i32, _i32, ctypes.c_double, ctypes.c_uint64,
+        ctypes.POINTER(ResidualStruct), _pi32
+    ]),
     'soda_hip_run_device_window': (ctypes.c_int, [_vp, _pvp, _pvp, _pi32, _pi32,
                                                   _pi32, _i32, _vp]),
     'soda_hip_run_device_cone': (ctypes.c_int, [_vp, _pvp, _pvp, _pi32, _pi32,
@@ -739,20 +760,58 @@ def plan_schedule(plan: Plan, extent: Sequence[int], iterate: int):
 
 
 def plan_launches(plan: Plan, extent: Sequence[int], iterate: int,
-                  run: Optional[SlabRun] = None):
+                  run: Optional[SlabRun] = None, residual: bool = False):
   """The launches a run on `extent` would issue (soda_hip_plan_launches): a
-  list of dicts, one per launch, in order.  No GPU needed."""
+  list of dicts, one per launch, in order.  No GPU needed.  `residual`: those
+  of a run that takes a residual (soda_hip_plan_launches_residual) -- returns
+  (launches, 'twin' | 'generic'): the last entry is the pass that takes it."""
   lib = library()
   ext = (ctypes.c_int32 * MAX_DIM)(*(list(extent) + [1] * (MAX_DIM - len(extent))))
   n = ctypes.c_int32(0)
   cap = 4096
   arr = (LaunchInfo * cap)()
-  check(lib.soda_hip_plan_launches(ctypes.byref(plan), ext, iterate,
-                                   ctypes.byref(run) if run is not None else
-                                   None, cap, arr, ctypes.byref(n)),
-        'launches of %d iterations' % iterate)
-  return [{name: getattr(arr[i], name) for name, _ in LaunchInfo._fields_}
-          for i in range(min(n.value, cap))]
+  run_p = ctypes.byref(run) if run is not None else None
+  mode = ctypes.c_int32(0)
+  if residual:
+    check(lib.soda_hip_plan_launches_residual(ctypes.byref(plan), ext, iterate,
+                                              run_p, cap, arr, ctypes.byref(n),
+                                              ctypes.byref(mode)),
+          'launches of %d iterations with a residual' % iterate)
+  else:
+    check(lib.soda_hip_plan_launches(ctypes.byref(plan), ext, iterate, run_p,
+                                     cap, arr, ctypes.byref(n)),
+          'launches of %d iterations' % iterate)
+  out = [{name: getattr(arr[i], name) for name, _ in LaunchInfo._fields_}
+         for i in range(min(n.value, cap))]
+  return (out, {1: 'twin', 2: 'generic'}[mode.value]) if residual else out
+
+
+def plan_residual_box(plan: Plan, extent: Sequence[int], iterate: int,
+                      origin: Optional[Sequence[int]] = None,
+                      global_extent: Optional[Sequence[int]] = None,
+                      keep: Optional[Sequence[int]] = None):
+  """[(lo, hi)] per output: the cells a residual over `iterate` iterations
+  counts on `extent` (soda_hip_plan_residual_box) or, with any of `origin` /
+  `global_extent` / `keep`, on that slab of a larger grid
+  (soda_hip_plan_residual_slab_box).  No GPU needed."""
+  dim, n = plan.dim, plan.num_outputs
+  ext = (ctypes.c_int32 * MAX_DIM)(*(list(extent) + [1] * (MAX_DIM - dim)))
+  lo, hi = (ctypes.c_int32 * (n * dim))(), (ctypes.c_int32 * (n * dim))()
+  if origin is None and global_extent is None and keep is None:
+    check(library().soda_hip_plan_residual_box(ctypes.byref(plan), ext,
+                                               iterate, lo, hi),
+          'residual_box')
+  else:
+    org = (ctypes.c_int32 * MAX_DIM)(*(list(origin or [0] * dim) +
+                                      [0] * (MAX_DIM - dim)))
+    gext = (ctypes.c_int32 * MAX_DIM)(*(list(global_extent or extent) +
+                                       [1] * (MAX_DIM - dim)))
+    keep = keep if keep is not None else (0, extent[dim - 1])
+    check(library().soda_hip_plan_residual_slab_box(
+        ctypes.byref(plan), gext, org, ext, int(keep[0]), int(keep[1]),
+        iterate, lo, hi), 'residual_box of a slab')
+  return [(tuple(lo[o * dim:(o + 1) * dim]), tuple(hi[o * dim:(o + 1) * dim]))
+          for o in range(n)]
 
 
 def pick_vec(stencil: core.Stencil, extent: Optional[Sequence[int]]) -> int:
@@ -1129,7 +1188,8 @@ class Program:
                  sends: Optional[Sequence[int]] = None,
                  ghosts_ready: int = 0, sendable: int = 0,
                  batch: Optional[int] = None,
-                 residual: Optional[int] = None) -> None:
+                 residual: Optional[int] = None,
+                 box_iterate: Optional[int] = None) -> None:
     """`outputs` / `inputs` are device addresses (e.g. tensor.data_ptr()) of
     dense dim-0-fastest arrays; asynchronous on `stream`.  `inputs` holds the
     input tensors followed by the program's `param` arrays (C order).
@@ -1186,7 +1246,15 @@ class Program:
     (soda_hip_run_device_residual; `residual()` reads and decodes them).  The
     struct is zeroed on `stream` inside the call; the run stays asynchronous
     and can be captured like any other.  Needs a program built with
-    LowerOptions.residual; runs on whole grids only."""
+    LowerOptions.residual.  Together with `origin` / `global_extent` / `keep`
+    / `ghosts` / `sends` the struct is the SLAB's share
+    (soda_hip_run_device_slab_residual): the cells of `residual_box(...,
+    origin=, global_extent=, keep=)` at `box_iterate` -- the iterations the
+    state has seen since its inputs were the caller's (default: `iterate`; no
+    less) -- ghost rows of the result not among them; the shares of all slabs
+    add up (counts) and take the larger (maxima).  A last pass split around
+    the exchange completes the struct with its interior part, behind
+    `sendable`.  Not together with `batch`."""
     st = self.stencil
     iterate = st.iterate if iterate is None else iterate
     self._check_extent(extent)
@@ -1197,12 +1265,33 @@ class Program:
     ins = (ctypes.c_void_p * len(inputs))(*inputs)
     ext = (ctypes.c_int32 * len(extent))(*extent)
     if residual is not None:
-      if batch is not None or keep is not None or ghosts is not None or \
-          sends is not None or origin is not None or \
-          global_extent is not None or ghosts_ready or sendable:
+      if batch is not None:
         raise util.InputError(
-            'run_device: a residual is that of a run on one whole grid: no '
-            'batch / keep / ghosts / sends / origin')
+            'run_device: no residual of a batch (a residual per item is a '
+            'reduction of its own)')
+      if keep is not None or ghosts is not None or sends is not None or \
+          origin is not None or global_extent is not None or ghosts_ready or \
+          sendable:
+        keep = keep if keep is not None else (0, extent[-1])
+        reach_lo, reach_hi = st.reach_along(st.dim - 1)
+        run = SlabRun(int(keep[0]), int(keep[1]), reach_lo, reach_hi,
+                      *(int(v) for v in (ghosts or (0, 0))),
+                      *(int(v) for v in (sends or (0, 0))),
+                      ghosts_ready or None, sendable or None)
+        org = (ctypes.c_int32 * len(extent))(*(origin or [0] * len(extent)))
+        gext = (ctypes.c_int32 * len(extent))(*(global_extent or extent))
+        check(
+            self._lib.soda_hip_run_device_slab_residual(
+                self._handle, outs, ins, ext, org, gext, iterate,
+                iterate if box_iterate is None else int(box_iterate),
+                ctypes.byref(run), ctypes.c_void_p(residual),
+                ctypes.c_void_p(stream)),
+            'running `%s` on a slab with a residual' % st.app_name)
+        return
+      if box_iterate is not None and int(box_iterate) != iterate:
+        raise util.InputError(
+            'run_device: box_iterate is for a slab run (origin / keep / '
+            'ghosts / sends)')
       check(
           self._lib.soda_hip_run_device_residual(
               self._handle, outs, ins, ext, iterate, ctypes.c_void_p(residual),
@@ -1272,18 +1361,18 @@ class Program:
           'last_residual')
     return {0: None, 1: 'twin', 2: 'generic'}[mode.value], fused.value
 
-  def residual_box(self, extent: Sequence[int], iterate: int):
+  def residual_box(self, extent: Sequence[int], iterate: int,
+                   origin: Optional[Sequence[int]] = None,
+                   global_extent: Optional[Sequence[int]] = None,
+                   keep: Optional[Sequence[int]] = None):
     """[(lo, hi)] per output: the cells a residual over `iterate` iterations
-    on `extent` counts, as the library derives them from the plan."""
-    dim = self.stencil.dim
-    n = len(self.stencil.output_names)
-    ext = (ctypes.c_int32 * MAX_DIM)(*(list(extent) + [1] * (MAX_DIM - dim)))
-    lo, hi = (ctypes.c_int32 * (n * dim))(), (ctypes.c_int32 * (n * dim))()
-    check(library().soda_hip_plan_residual_box(ctypes.byref(self.plan), ext,
-                                               iterate, lo, hi),
-          'residual_box')
-    return [(tuple(lo[o * dim:(o + 1) * dim]), tuple(hi[o * dim:(o + 1) * dim]))
-            for o in range(n)]
+    on `extent` counts, as the library derives them from the plan.  With
+    `origin` / `global_extent` / `keep`: the cells a SLAB counts, in the
+    coordinates of its arrays -- the global grid's box cut to the rows `keep`
+    = (lo, hi) of the slab's last dimension
+    (soda_hip_plan_residual_slab_box)."""
+    return plan_residual_box(self.plan, extent, iterate, origin, global_extent,
+                             keep)
 
   def run_until(self, inputs: Dict[str, 'numpy.ndarray'], tol: float,
                 max_iterate: int, check_every: int = 8, int_tol: int = 0):
@@ -1676,12 +1765,62 @@ class Group:
     """The caller filled the slabs' input arrays on the devices itself."""
     check(self._lib.soda_hip_group_loaded(self._handle), 'group loaded')
 
-  def run(self, iterate: Optional[int] = None) -> None:
-    """Enqueues `iterate` iterations on every slab; asynchronous."""
+  def run(self, iterate: Optional[int] = None, residual: bool = False) -> None:
+    """Enqueues `iterate` iterations on every slab; asynchronous.  `residual`:
+    every slab's last interval also takes its share of the residual of the
+    last iteration, over the box of all iterations since `load` / `loaded`
+    (soda_hip_group_run_residual; `residual()` fetches and folds the shares).
+    Needs a group built with LowerOptions(residual=True)."""
     iterate = self.stencil.iterate if iterate is None else iterate
-    check(self._lib.soda_hip_group_run(self._handle, iterate),
-          'running `%s` on %d slabs' % (self.stencil.app_name,
-                                        len(self.devices)))
+    run = self._lib.soda_hip_group_run_residual if residual else \
+        self._lib.soda_hip_group_run
+    check(run(self._handle, iterate),
+          'running `%s` on %d slabs%s' % (self.stencil.app_name,
+                                          len(self.devices),
+                                          ' with a residual' if residual else
+                                          ''))
+
+  def residual(self, per_slab: bool = False):
+    """The residual of the last `run(..., residual=True)`: the slabs' structs
+    folded on the host, counts added, maxima the larger -- exactly the
+    residual of the whole grid.  Synchronises.  `per_slab`: (Residual, [one
+    Residual per slab])."""
+    raw = ResidualStruct()
+    each = (ResidualStruct * len(self.devices))()
+    check(self._lib.soda_hip_group_residual(self._handle, ctypes.byref(raw),
+                                            each),
+          'group residual')
+    total = Residual.from_struct(raw)
+    if per_slab:
+      return total, [Residual.from_struct(r) for r in each]
+    return total
+
+  def last_residual(self, slab: int):
+    """How slab `slab` took its share in the last residual run: ('twin' |
+    'generic' | None, fusion depth of its last pass)."""
+    mode, fused = ctypes.c_int32(), ctypes.c_int32()
+    check(self._lib.soda_hip_group_last_residual(self._handle, int(slab),
+                                                 ctypes.byref(mode),
+                                                 ctypes.byref(fused)),
+          'group last_residual')
+    return {0: None, 1: 'twin', 2: 'generic'}[mode.value], fused.value
+
+  def run_until(self, tol: float, max_iterate: int, check_every: int = 8,
+                int_tol: int = 0):
+    """Iterates the loaded state until converged: `check_every` iterations at
+    a time, stopping when the last iteration's residual has `unordered == 0`,
+    `max_float <= tol` and `max_int <= int_tol`, or after `max_iterate`
+    iterations (soda_hip_group_run_until; synchronous).  Returns (iterations
+    done, Residual); `store(iterations since the load)` delivers the grid."""
+    raw = ResidualStruct()
+    done = ctypes.c_int32(0)
+    check(self._lib.soda_hip_group_run_until(self._handle, int(max_iterate),
+                                             int(check_every), float(tol),
+                                             int(int_tol), ctypes.byref(raw),
+                                             ctypes.byref(done)),
+          'running `%s` on %d slabs until converged' % (
+              self.stencil.app_name, len(self.devices)))
+    return done.value, Residual.from_struct(raw)
 
   def synchronize(self) -> None:
     check(self._lib.soda_hip_group_synchronize(self._handle),

@@ -116,6 +116,13 @@ step c5_n${n} bench $n --iterate 1000 --steps 5 --warmup 2 --full \
     --no-cpu-baseline --no-rehearsal --no-single-iter --no-other-configs || exit 1
 # 7. weak scaling: every rank keeps the single-GPU grid
 step weak_n${n} bench $n --scaling weak $quick || exit 1
+# 7b. a group run until converged: the residual of every slab on its own
+#    device, folded on the host (soda_hip_group_run_until; never yet run on
+#    more than one physical GPU)
+step until_n2 python -m soda_amd.sodac tests/golden/soda/jacobi2d.soda \
+    --iterate 64 --border preserve --hip-backend --hip-extent 1024 1024 \
+    --hip-gpus 2 ${virtual:+--hip-virtual} --hip-until 0.003 \
+    --hip-check-every 16 || exit 1
 if [ -n "$rehearsal" ]; then echo "first_multi_gpu: rehearsal done, see $out"; exit 0; fi
 # 8. what the exchange looks like on the wire: a kernel trace of two ranks,
 #    one step, exchange hidden (rank 0's trace: the send/recv kernels of RCCL

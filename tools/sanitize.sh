@@ -5,6 +5,9 @@
 #      launch geometry, schedules, launch planning by brute force, group
 #      planning, the pack / unpack threads of the host-array entry;
 #   2. the same sources under -fsanitize=thread for the worker pool;
+#   2b. tests/host/residual_slab_box_main.cpp linked with the same sources into
+#      one program (its own main) under ASan + UBSan: the residual's slab
+#      boxes and the launch order of a residual slab run;
 #   3. the CPU oracle's GENERATED loop nests under ASan + UBSan (corpus, fuzz
 #      seeds, independent nests): an out-of-box load in the oracle is caught.
 # The reference builds its csim with -fsanitize=address
@@ -26,7 +29,7 @@ lib=$PWD/soda_amd/_sanitize
 fail=0
 {
   echo "# tools/sanitize.sh, $(date -u +%FT%TZ), $(gcc --version | head -1)"
-  make -C soda_amd/csrc asan tsan 2>&1 | tail -3 || fail=1
+  make -C soda_amd/csrc asan tsan plan_asan 2>&1 | tail -3 || fail=1
   # the product library up to date BEFORE a sanitizer runtime is preloaded (the
   # tests' `built` fixture would otherwise run hipcc under it)
   python -c "import __graft_entry__ as g; g.build_library()" || fail=1
@@ -55,6 +58,9 @@ fail=0
       --deselect tests/test_group.py::test_geometry_of_a_tall_stream_is_cheap
   # (deselected: a wall-clock assertion -- plan_geometry of a 2M-row stream in
   # under 10 ms -- that an instrumented build on a busy box misses now and then)
+  # (a program with its own main: no runtime preloaded, no interpreter)
+  run "residual planning, ASan + UBSan, stand-alone: slab boxes partition the global box, launches of a residual slab run" \
+      "" $lib/libsoda_hip_asan.so $lib/residual_slab_box_asan
   run "libsoda_hip, TSan: the worker pool of the host-array entry (pack / unpack on 8 threads)" \
       "$tsan" $lib/libsoda_hip_tsan.so \
       python -m pytest -q -m "not gpu" -p no:cacheprovider tests/test_host.py -k "pack_and_unpack"
