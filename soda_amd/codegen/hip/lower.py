@@ -311,6 +311,15 @@ def lower(stencil: core.Stencil, opts: Optional[LowerOptions] = None) -> Module:
   if opts.xshare_block is not None and not 2 <= opts.xshare_block <= 16:
     raise util.SemanticError('xshare_block %r: None or 2 to 16 waves per block'
                              % (opts.xshare_block,))
+  if (opts.pipe or 1) > 1 and (
+      not isinstance(opts.pipe_rows, int) or opts.pipe_rows < 1 or
+      opts.pipe_rows & (opts.pipe_rows - 1)):
+    # (refused here, whatever the strategy: the marching generator's own
+    # refusal is caught by the ladder below, which would drop the fused depth
+    # and hand back the one-iteration kernel without a word)
+    raise util.SemanticError(
+        'pipe_rows %r: the row steps per barrier of a stage-pipelined block '
+        '(pipe %d) are a power of two' % (opts.pipe_rows, opts.pipe))
   if opts.batch and opts.banks:
     raise util.SemanticError(
         'batch: the wire format has no batch, `banks` cannot be combined with '

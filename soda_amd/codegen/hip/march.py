@@ -1546,18 +1546,30 @@ class _MarchKernel:
               self.cfg.chunk_rows)
     if self.seg:
       tile = (self.seg_cells,) + tile[1:]
+    # the rings a stage-pipelined block declares (the cells x-halo sharing
+    # hands over are a few hundred bytes more, not counted: `lds_rings`)
+    table = self.st.symbol_table
+    lds_rings = sum(
+        2 * self.R * self.rows_in * 64 * self.V *
+        table[n.key[1] if n.key[0] == 'in' else n.key[0]].size_in_bytes
+        for n in self.nodes if n.to_lds)
     lds_pad = 0
     if self.cfg.occupancy:
       blocks_per_cu = max(1, 4 * self.cfg.occupancy // self.waves)
-      # smallest allocation of which blocks_per_cu + 1 no longer fit
-      lds_pad = min(65536, (LDS_PER_CU // (blocks_per_cu + 1)) // 1024 * 1024
-                    + 1024)
+      # smallest allocation of which blocks_per_cu + 1 no longer fit -- of
+      # which the block's own rings are a part: the pad is what is missing
+      # beside them (on top of them, 64 KiB beside the 24 KiB of jacobi2d
+      # T = 12 pipe 4 x 4 asked for 88 KiB a block where 81 KiB were meant; an
+      # MI355X accepts such a launch -- 160 KiB a block -- and ran it right)
+      need = (LDS_PER_CU // (blocks_per_cu + 1)) // 1024 * 1024 + 1024
+      lds_pad = min(65536, max(0, need - lds_rings))
     idx = self.mod.add_kernel(
         KernelDesc(self.name, (self.block, 1, 1), tile, lds_bytes=lds_pad,
                    note='%s %s' % (self.kind, self.cfg.key()),
                    tune=dict(axis=self.ax, waves_along=self.cfg.waves_y if self.dim == 2 else 1,
                              waves_per_block=self.waves, warm=self.warm,
                              fixed=self.cfg.chunk_fixed, occupancy=self.cfg.occupancy,
+                             lds_rings=lds_rings, lds_pad=lds_pad,
                              pipe=self.W, vec=self.V, step_ops=step_ops,
                              lane_shift=self.cfg.lane_shift,
                              warm_saved=saved,

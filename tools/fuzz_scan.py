@@ -155,8 +155,10 @@ def options_scan(first, last, only=None):
   """Random programs on grids of several strips and chunks with random backend
   knobs: chunk length (the launch-time tuner may pick any), peeled warm-up,
   fusion depth, prefetch depth, lane-shift flavour, cells per lane, blocks that
-  share rows, pipelined waves, the rewrites on / off."""
+  share rows, pipelined waves, rows per barrier, spare lanes, the occupancy
+  pad and register hint, waves side by side, the rewrites on / off."""
   import fuzz
+  import knobs
   from oracle import c_oracle
   from soda_amd import core, runtime, util
   from soda_amd.codegen.hip import lower
@@ -201,6 +203,12 @@ def options_scan(first, last, only=None):
       kw['pipe'] = 2
     if rng.random() < 0.15:
       kw['waves_y'] = 2
+    # (the value lists of tests/knobs.py, so that the two cannot drift; drawn
+    # after everything else: the earlier draws of a seed stay what they were)
+    for name in ('pipe_rows', 'align_lanes', 'occupancy', 'min_waves',
+                 'waves_x'):
+      if rng.random() < 0.2:
+        kw[name] = pick(knobs.SCAN_VALUES[name])
     ins = fuzz.inputs_for(stencil, extent, seed)
     want = c_oracle.COracle(stencil, openmp=False).run(ins)
     what = 'seed %d %s%s extent %s %s' % (seed, kind, ' preserve' if border else '',
