@@ -261,7 +261,7 @@ def lowered(prog, row, extent=None, probe=False):
   return _lowered(prog, freeze(row), extent, probe)
 
 
-def _grid(prog, k):
+def _grid(k):
   """2 S + 9 V cells along x; 9 rows in 3-D; the marched dimension comes from
   the launch geometry (extent_of)."""
   s, v = k.tile[0], k.tune['vec']
@@ -275,16 +275,19 @@ def _rows_for(k, dim):
   return 7 * k.tile[dim - 1] + RAGGED[dim]
 
 
-@functools.lru_cache(maxsize=None)
-def _setup(prog, frozen, probe=False):
-  st = stencil_of(prog)
-  row = dict(frozen)
-  mod = lowered(prog, row, None, probe)
-  k = deepest(mod)
+def settle(dim, lower_for, what, width=None, pick=None):
+  """(extent, extent to build the program for or None) of the module
+  `lower_for(extent or None)` answers with: the grid of its deepest kernel.
+  `width(kernel)`: the cells along x, where they are not 2 S + 9 V;
+  `pick(module)`: the kernel the grid is sized from, where `deepest` does not
+  find it."""
+  pick = pick or deepest
+  mod = lower_for(None)
+  k = pick(mod)
 
   def grid(k):
-    x = _grid(prog, k)
-    return (x, _rows_for(k, 2)) if st.dim == 2 else (x, 9, _rows_for(k, 3))
+    x = width(k) if width else _grid(k)
+    return (x, _rows_for(k, 2)) if dim == 2 else (x, 9, _rows_for(k, 3))
 
   extent = grid(k)
   widest = max(q.tune.get('vec', 1) for q in mod.kernels if q.tune)
@@ -292,12 +295,20 @@ def _setup(prog, frozen, probe=False):
     return extent, None
   # the vector width follows the row length, the row length the width
   for _ in range(4):
-    k = deepest(lowered(prog, row, extent, probe))
+    k = pick(lower_for(extent))
     new = grid(k)
     if new == extent:
       return extent, extent
     extent = new
-  raise AssertionError('%s %s: no stable grid' % (prog, row_id(row)))
+  raise AssertionError('%s: no stable grid' % (what,))
+
+
+@functools.lru_cache(maxsize=None)
+def _setup(prog, frozen, probe=False):
+  row = dict(frozen)
+  return settle(stencil_of(prog).dim,
+                lambda extent: lowered(prog, row, extent, probe),
+                '%s %s' % (prog, row_id(row)))
 
 
 def setup(prog, row, probe=False):

@@ -713,7 +713,8 @@ CHUNK_PROGRAMS = [(n, False) for n in sorted(SEAM_PROGRAMS)] + [('back3d', True)
 def test_chunk_seams(built, name, tall, chunk, planes):
   """Blocks that start at m_begin > 0: the clipped input window (wlo, in_end),
   the first step and the last (start, t_end) and the rebased buffers, with a
-  reach along z that is one-sided, on every cell type, through both depths."""
+  reach along z that is one-sided, on every cell type tile3d accepts (float,
+  int32, uint32), through both depths."""
   from soda_amd.codegen.hip import lower
   iterate, fuse = 7, (4, 3)
   need = _tiles_for_a_valid_row(name, fuse, iterate, 3)
