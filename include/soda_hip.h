@@ -68,7 +68,10 @@ extern "C" {
  * on slabs and groups -- soda_hip_plan_residual_slab_box,
  * soda_hip_run_device_slab_residual, soda_hip_plan_launches_residual,
  * soda_hip_group_run_residual, soda_hip_group_residual,
- * soda_hip_group_last_residual, soda_hip_group_run_until. */
+ * soda_hip_group_last_residual, soda_hip_group_run_until; and the exact L1 /
+ * L2 norms of the residual -- soda_hip_norms_t with soda_hip_norms_fold /
+ * _value / _host / _create / _destroy / _zero / _accumulate,
+ * soda_hip_run_device_norms and soda_hip_run_device_until_norm. */
 #define SODA_HIP_ABI_VERSION 9
 #define SODA_HIP_MAX_DIM 4
 #define SODA_HIP_MAX_TENSORS 16
@@ -299,8 +302,8 @@ int soda_hip_device_count(int* count);
 /* sizeof() of the ABI structs as this library was compiled, for bindings to
  * check their mirrors: 0 kargs, 1 kernel_desc, 2 pass_desc, 3 plan,
  * 4 host_tensor, 5 stream_desc, 6 slab_run, 7 group_desc, 8 slab_info,
- * 9 group_stats, 10 launch_info, 11 residual, 12 resbox; 0 for anything
- * else. */
+ * 9 group_stats, 10 launch_info, 11 residual, 12 resbox, 14 norms; 0 for
+ * anything else (13 among them). */
 size_t soda_hip_sizeof(int which);
 
 /* -- JIT: HIP source text -> gfx950 code object (hiprtc; needs no GPU) ---- */
@@ -647,6 +650,129 @@ int soda_hip_plan_launches_residual(const soda_hip_plan_t* plan,
                                     int32_t capacity,
                                     soda_hip_launch_info_t* launches,
                                     int32_t* count, int32_t* mode);
+
+/* -- exact L1 and L2 norms of the residual ---------------- */
+/* The sums of |d| and of d^2 over the deltas d that soda_hip_residual_t takes
+ * its maxima of -- same pairs, same cells, same per-cell delta -- accumulated
+ * as wide integers (a long accumulator): every finite delta is an integer
+ * times 2^u, so is its square, and integer addition has no order.  The words
+ * equal the CPU's, bit for bit, however lanes, waves, blocks and slabs add.
+ *   kind       SODA_HIP_NORMS_*: which units apply (0: a struct never zeroed)
+ *   count      cells whose delta is finite (zero included): those summed
+ *   unordered  cells whose delta is NaN, left out of both sums
+ *   infinite   cells whose delta is +inf, left out of both sums
+ *   l1, l2     little-endian multiword unsigned integers: the sum of |d| in
+ *              units of 2^u1, the sum of d^2 in units of 2^u2:
+ *                F32  u1 = -149,  u2 = -298     I32 (cells up to 32 bits)  0, 0
+ *                F64  u1 = -1074, u2 = -2148    I64                        0, 0
+ *              Sized for F64 and 2^64 cells: the largest double is below
+ *              2^1024, so a sum is below 2^(1024 + 1074 + 64) = 2^2162 (34
+ *              words), of squares below 2^(2048 + 2148 + 64) = 2^4260 (67).
+ * The square is exact: an fp32 mantissa squared has 48 bits, an fp64 one 106
+ * (the two 53-bit integers multiplied as integers), a 64-bit integer delta
+ * 128.  One struct size serves every kind; 840 bytes, 8-byte aligned. */
+#define SODA_HIP_NORMS_L1_WORDS 34
+#define SODA_HIP_NORMS_L2_WORDS 67
+enum soda_hip_norms_kind {
+  SODA_HIP_NORMS_F32 = 1,
+  SODA_HIP_NORMS_F64 = 2,
+  SODA_HIP_NORMS_I32 = 3,   /* integer cells of 8, 16 or 32 bits */
+  SODA_HIP_NORMS_I64 = 4
+};
+/* The ten cell types a norms handle is made for; the kind follows. */
+enum soda_hip_cell {
+  SODA_HIP_CELL_FLOAT = 0, SODA_HIP_CELL_DOUBLE = 1,
+  SODA_HIP_CELL_INT8 = 2, SODA_HIP_CELL_UINT8 = 3,
+  SODA_HIP_CELL_INT16 = 4, SODA_HIP_CELL_UINT16 = 5,
+  SODA_HIP_CELL_INT32 = 6, SODA_HIP_CELL_UINT32 = 7,
+  SODA_HIP_CELL_INT64 = 8, SODA_HIP_CELL_UINT64 = 9
+};
+typedef struct soda_hip_norms {
+  uint32_t kind;
+  uint32_t reserved;
+  uint64_t count;
+  uint64_t unordered;
+  uint64_t infinite;
+  uint64_t l1[SODA_HIP_NORMS_L1_WORDS];
+  uint64_t l2[SODA_HIP_NORMS_L2_WORDS];
+} soda_hip_norms_t;
+#define SODA_HIP_NORMS_WHICH_L1 1
+#define SODA_HIP_NORMS_WHICH_L2 2
+
+/* Pure host functions: no GPU, no allocation, no error text (the status says
+ * it all), safe from any thread. */
+/* SODA_HIP_NORMS_* of a SODA_HIP_CELL_*, bytes per cell in *elem (may be
+ * NULL); 0 for anything else. */
+int soda_hip_norms_kind_of(int32_t cell, int32_t* elem);
+/* dst += src: counts and sums add.  Kinds must match (SODA_HIP_ERR_INVALID);
+ * a sum that leaves its words -- more than 2^64 cells -- is
+ * SODA_HIP_ERR_INVALID too, dst then unspecified. */
+int soda_hip_norms_fold(soda_hip_norms_t* dst, const soda_hip_norms_t* src);
+/* The correctly rounded (to nearest, ties to even) double of the sum of |d|
+ * (which = SODA_HIP_NORMS_WHICH_L1) or of d^2 (_L2); +inf above the double
+ * range, and +inf when infinite != 0.  `unordered` does not enter: the caller
+ * looks at it. */
+int soda_hip_norms_value(const soda_hip_norms_t* acc, int32_t which,
+                         double* out);
+/* The same reduction in plain C++: the cells [lo, hi) (dim values each) of two
+ * dense dim-0-fastest host arrays of `extent`, ADDED to *acc, whose kind must
+ * be the cell type's (SODA_HIP_ERR_INVALID otherwise; a zeroed struct of that
+ * kind to start from: memset and set `kind`). */
+int soda_hip_norms_host(const void* cur, const void* prev, int32_t cell,
+                        int32_t dim, const int32_t* extent, const int32_t* lo,
+                        const int32_t* hi, soda_hip_norms_t* acc);
+
+/* The kernels (soda_amd/codegen/hip/norms.py: a module of its own per cell
+ * type and dimension count, independent of any stencil) loaded on `device`.
+ * Allocates nothing after create. */
+typedef struct soda_hip_norms_handle soda_hip_norms_handle_t;   /* opaque */
+int soda_hip_norms_create(const void* code, size_t code_size, int32_t cell,
+                          int32_t dim, int32_t device,
+                          soda_hip_norms_handle_t** handle);
+int soda_hip_norms_destroy(soda_hip_norms_handle_t* handle);
+/* Zeroes the 840 device bytes `acc_dev` (8-byte aligned) and sets their kind:
+ * a one-block kernel on `stream`, a kernel node like every other under
+ * capture. */
+int soda_hip_norms_zero(soda_hip_norms_handle_t* handle, void* acc_dev,
+                        void* stream);
+/* Adds the cells [lo, hi) of the dense device arrays `cur` against `prev`
+ * (both of `extent`, aligned to the cell size) to *acc_dev.  Asynchronous on
+ * `stream` under "Streams, scratch, graphs"; never allocates, never waits:
+ * capturable as it stands.  Does not zero: several pairs, bands or boxes may
+ * add into one struct.  An empty box launches nothing. */
+int soda_hip_norms_accumulate(soda_hip_norms_handle_t* handle, const void* cur,
+                              const void* prev, const int32_t* extent,
+                              const int32_t* lo, const int32_t* hi,
+                              void* acc_dev, void* stream);
+/* soda_hip_run_device_residual by its generic path, with the norms in place of
+ * `<app>_residual`: iterate - 1 iterations are scheduled, the run ends in the
+ * one-iteration pass, then *acc_dev is zeroed and every pair's outputs are
+ * accumulated against that pass's inputs over the box of
+ * soda_hip_plan_residual_box after `iterate` iterations.  Same refusals, same
+ * contract checks, inputs never written; asynchronous and capturable like
+ * that entry.  SODA_HIP_ERR_UNSUPPORTED, nothing launched: a program built
+ * without `residual`; pairs whose cell sizes give another kind or size than
+ * the handle's (a program of mixed cell types).  SODA_HIP_ERR_INVALID: a
+ * handle of another dimension count or device, a struct that overlaps an
+ * output. */
+int soda_hip_run_device_norms(soda_hip_program_t* program,
+                              soda_hip_norms_handle_t* norms,
+                              void* const* outputs, const void* const* inputs,
+                              const int32_t* extent, int32_t iterate,
+                              void* acc_dev, void* stream);
+/* soda_hip_run_device_until with the stop rule
+ *   unordered == 0 && infinite == 0 && norm <= tol
+ * norm = value(l1) for which = SODA_HIP_NORMS_WHICH_L1, sqrt(value(l2)) for
+ * _L2.  SYNCHRONOUS; fetches the struct after each chunk; *result_host is the
+ * struct of the last chunk. */
+int soda_hip_run_device_until_norm(soda_hip_program_t* program,
+                                   soda_hip_norms_handle_t* norms,
+                                   void* const* outputs,
+                                   const void* const* inputs,
+                                   const int32_t* extent, int32_t max_iterate,
+                                   int32_t check_every, int32_t which,
+                                   double tol, soda_hip_norms_t* result_host,
+                                   int32_t* iterations_done, void* stream);
 
 /* Replaces soda::app::<app>(): host arrays described by (ptr, extent, stride,
  * min) per tensor, inputs then outputs; copies in, runs, copies the outputs

@@ -96,6 +96,12 @@ def add_arguments(parser) -> None:
                       'iterations); implies --hip-residual; prints the '
                       'iterations and the residual; with --hip-gpus N on the '
                       'slabs (soda_hip_group_run_until)')
+  parser.add_argument('--hip-norm', choices=('max', 'l1', 'l2'),
+                      dest='hip_norm', default='max',
+                      help='with --hip-until: what TOL bounds -- the largest '
+                      'change of a cell (max, the default), or the exact sum '
+                      'of |change| (l1) or root of the sum of squares (l2) '
+                      'over the grid (soda_hip_run_device_until_norm; one GPU)')
   parser.add_argument('--hip-check-every', type=int, dest='hip_check_every',
                       default=8, metavar='K',
                       help='with --hip-until: iterations between two looks at '
@@ -231,6 +237,9 @@ def run(stencil: core.Stencil, args: argparse.Namespace) -> None:
                                                     0) or 0))
     t0 = time.time()
     res = None
+    if getattr(args, 'hip_norm', 'max') != 'max':
+      raise util.InputError('--hip-norm l1 / l2 runs on one GPU (the slabs\' '
+                            'norms are not served yet)')
     if getattr(args, 'hip_until', None) is not None:
       # the one-GPU form's loop on the slabs (soda_hip_group_run_until)
       prog.load(inputs)
@@ -259,7 +268,18 @@ def run(stencil: core.Stencil, args: argparse.Namespace) -> None:
     prog = runtime.Program(stencil, options_from_args(args),
                            device=args.hip_device, extent=extent)
     t0 = time.time()
-    if getattr(args, 'hip_until', None) is not None:
+    norm = getattr(args, 'hip_norm', 'max')
+    if getattr(args, 'hip_until', None) is not None and norm != 'max':
+      outputs, done, acc = prog.run_until(
+          inputs, args.hip_until, stencil.iterate,
+          check_every=max(1, int(args.hip_check_every)), norm=norm)
+      extra = {'until': args.hip_until, 'norm': norm, 'iterations': done,
+               'norms': {'count': int(acc.count),
+                         'unordered': int(acc.unordered),
+                         'infinite': int(acc.infinite),
+                         'l1': runtime.norms_value(acc, 'l1'),
+                         'l2_squared': runtime.norms_value(acc, 'l2')}}
+    elif getattr(args, 'hip_until', None) is not None:
       outputs, done, res = prog.run_until(
           inputs, args.hip_until, stencil.iterate,
           check_every=max(1, int(args.hip_check_every)))

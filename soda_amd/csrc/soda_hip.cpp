@@ -140,6 +140,7 @@ size_t soda_hip_sizeof(int which) {
     case 9: return sizeof(soda_hip_group_stats_t);
     case 10: return sizeof(soda_hip_launch_info_t);
     case 11: return sizeof(soda_hip_residual_t);
+    case 14: return sizeof(soda_hip_norms_t);
     case 12: return sizeof(soda_hip_resbox_t);
     default: return 0;
   }
@@ -385,6 +386,7 @@ int soda_hip_program_destroy(soda_hip_program_t* p) {
     for (auto& b : *v)
       if (b.ptr) (void)hipFree(b.ptr);
   if (p->until_res.ptr) (void)hipFree(p->until_res.ptr);
+  if (p->until_norms.ptr) (void)hipFree(p->until_norms.ptr);
   for (int i = 0; i < 2; ++i) {
     if (p->ev_pre[i]) (void)hipEventDestroy(p->ev_pre[i]);
     if (p->ev_bnd[i]) (void)hipEventDestroy(p->ev_bnd[i]);
@@ -757,6 +759,111 @@ int launch_residual(soda_hip_program* p, const soda_hip_kargs_t& base,
   return SODA_HIP_OK;
 }
 
+// ---- exact norms (soda_hip_norms_t; the kernels: soda_rt_norms.h) -----------
+// the kernels' one argument, as soda_rt_norms.h declares it
+struct NormsArgs {
+  const void* cur;
+  const void* prev;
+  void* acc;
+  int32_t extent[SODA_HIP_MAX_DIM];
+  int32_t lo[SODA_HIP_MAX_DIM];
+  int32_t hi[SODA_HIP_MAX_DIM];
+};
+
+int norms_zero(soda_hip_norms_handle* h, void* acc_dev, hipStream_t stream) {
+  struct {
+    void* acc;
+    uint64_t kind;     // word 0 of the struct: kind | reserved = 0
+  } args = {acc_dev, (uint64_t)h->kind};
+  size_t size = sizeof args;
+  void* extra[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &args,
+                   HIP_LAUNCH_PARAM_BUFFER_SIZE, &size, HIP_LAUNCH_PARAM_END};
+  HIP_TRY(hipModuleLaunchKernel(h->zero, 1, 1, 1, 256, 1, 1, 0, stream,
+                                nullptr, extra));
+  return SODA_HIP_OK;
+}
+
+// the cells [lo, hi) of dense `cur` against dense `prev`, added to *acc_dev
+int norms_accumulate(soda_hip_norms_handle* h, const void* cur,
+                     const void* prev, const int32_t* extent,
+                     const int32_t* lo, const int32_t* hi, void* acc_dev,
+                     hipStream_t stream) {
+  NormsArgs args;
+  memset(&args, 0, sizeof args);
+  args.cur = cur;
+  args.prev = prev;
+  args.acc = acc_dev;
+  int64_t rows = 1;
+  bool empty = false;
+  for (int d = 0; d < SODA_HIP_MAX_DIM; ++d) {
+    const bool in = d < h->dim;
+    args.extent[d] = in ? extent[d] : 1;
+    args.lo[d] = in ? lo[d] : 0;
+    args.hi[d] = in ? hi[d] : 1;
+    if (args.extent[d] < 1 || args.lo[d] < 0 || args.hi[d] > args.extent[d])
+      return fail(SODA_HIP_ERR_INVALID,
+                  "norms_accumulate: the box does not lie in the arrays; "
+                  "nothing was launched");
+    if (args.hi[d] <= args.lo[d]) empty = true;
+    if (d > 0) rows *= args.extent[d];
+  }
+  if (empty) return SODA_HIP_OK;
+  // the widest fragment that divides the row length and that both arrays are
+  // aligned to (the narrowest is one cell: always there)
+  const uintptr_t both = reinterpret_cast<uintptr_t>(cur) |
+                         reinterpret_cast<uintptr_t>(prev);
+  if (both % (uintptr_t)h->elem)
+    return fail(SODA_HIP_ERR_INVALID,
+                "norms_accumulate: an array is not aligned to its cell size; "
+                "nothing was launched");
+  hipFunction_t fn = nullptr;
+  int32_t vec = 1;
+  for (const auto& w : h->widths)
+    if (args.extent[0] % w.first == 0 &&
+        both % ((uintptr_t)w.first * h->elem) == 0) {
+      vec = w.first;
+      fn = w.second;
+      break;
+    }
+  if (!fn) return fail(SODA_HIP_ERR_INVALID, "norms_accumulate: no kernel");
+  // grid: as launch_residual -- the segments of 256 fragments a row has, times
+  // as many rows in flight as make about a thousand blocks
+  // (a block takes `rpb` whole rows at a time where a row has fewer fragments
+  // than the block has lanes: soda_rt_norms.h computes the same two numbers)
+  const int64_t frags = args.extent[0] / vec;
+  const int64_t rpb = frags < 256 ? 256 / frags : 1;
+  const int64_t nx = rpb > 1 ? 1 : (frags + 255) / 256;
+  if (rows > 0x7fffffffLL || nx > 0x7fffffLL)
+    return fail(SODA_HIP_ERR_INVALID,
+                "norms_accumulate: grid does not fit a launch");
+  const int64_t groups = (rows + rpb - 1) / rpb;
+  int64_t in_flight = 1024 / nx;
+  if (in_flight < 1) in_flight = 1;
+  if (in_flight > groups) in_flight = groups;
+  size_t size = sizeof args;
+  void* extra[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &args,
+                   HIP_LAUNCH_PARAM_BUFFER_SIZE, &size, HIP_LAUNCH_PARAM_END};
+  HIP_TRY(hipModuleLaunchKernel(fn, (unsigned)(nx * in_flight), 1, 1, 256, 1, 1,
+                                0, stream, nullptr, extra));
+  return SODA_HIP_OK;
+}
+
+// What follows the one-iteration pass of a residual run that no twin serves:
+// `<app>_residual`, or the norms kernel once per pair (cur: the output slot,
+// prev: the input slot of the launch's arrays)
+int launch_generic(soda_hip_program* p, const soda_hip_kargs_t& args,
+                   hipStream_t stream, const soda_detail::ResidualRun& res,
+                   const soda_hip_resbox_t& box) {
+  if (!res.norms) return launch_residual(p, args, stream, res.dev, box);
+  const int out0 = p->plan.num_inputs;
+  for (int o = 0; o < p->plan.num_outputs; ++o)
+    if (int rc = norms_accumulate(res.norms, args.buf[out0 + o], args.buf[o],
+                                  args.extent, box.lo[o], box.hi[o], res.dev,
+                                  stream))
+      return rc;
+  return SODA_HIP_OK;
+}
+
 // The cells a residual over `iterate` iterations counts (soda_hip.h,
 // soda_hip_residual_plan_t): the plan's recurrence run `iterate` times from
 // zero windows, the box the array less the window, clipped like every valid
@@ -910,9 +1017,9 @@ int schedule(const soda_hip_plan_t& plan, const std::vector<double>& pass_ns,
 int residual_order(const soda_hip_plan_t& plan,
                    const std::vector<double>& pass_ns, int32_t iterate,
                    int32_t* count, int32_t* total, int* res_pass,
-                   bool* res_twin) {
+                   bool* res_twin, bool generic_only) {
   const char* g = getenv("SODA_HIP_RESIDUAL_GENERIC");
-  const bool generic = g && !strcmp(g, "1");
+  const bool generic = generic_only || (g && !strcmp(g, "1"));
   *res_pass = -1;
   *res_twin = false;
   for (int i = 0; i < plan.num_passes && !generic && *res_pass < 0; ++i)
@@ -1375,7 +1482,7 @@ int run_core(soda_hip_program_t* p, void* const* outputs,
     const std::vector<double>& pass_ns =
         it != measured.end() ? it->second : ep->model_ns;
     if (int rc = residual_order(plan, pass_ns, iterate, count, &total,
-                                &res_last, &res_twin))
+                                &res_last, &res_twin, res->norms != nullptr))
       return rc;
   }
 
@@ -1443,7 +1550,9 @@ int run_core(soda_hip_program_t* p, void* const* outputs,
     // zeroed inside the call, on the caller's stream, by a kernel of the
     // program: a captured call zeroes and refills the struct at every replay
     // (as a 32-byte memset node the zeroing did not survive a replay)
-    {
+    if (res->norms) {
+      if (int rc = norms_zero(res->norms, res->dev, stream)) return rc;
+    } else {
       const int zk = plan.residual.zero_kernel;
       void* dev = res->dev;
       size_t size = sizeof dev;
@@ -1533,7 +1642,7 @@ int run_core(soda_hip_program_t* p, void* const* outputs,
       if (take_generic) {
         // behind both parts: it reads all of what the pass wrote and writes
         // the struct only, so `sendable` need not wait for it
-        if (int rc = launch_residual(p, args, stream, res->dev, lbox)) return rc;
+        if (int rc = launch_generic(p, args, stream, *res, lbox)) return rc;
         ++p->last_launches;
       }
     } else if (L.split) {
@@ -1561,7 +1670,7 @@ int run_core(soda_hip_program_t* p, void* const* outputs,
       if (i == 0) ++p->last_fused;
       ++p->last_split;
       if (take_generic) {
-        if (int rc = launch_residual(p, args, stream, res->dev, lbox)) return rc;
+        if (int rc = launch_generic(p, args, stream, *res, lbox)) return rc;
         ++p->last_launches;
       }
     } else {
@@ -1577,7 +1686,7 @@ int run_core(soda_hip_program_t* p, void* const* outputs,
       }
       if (take_generic) {
         // cur: what the pass just wrote; prev: what it read
-        if (int rc = launch_residual(p, args, stream, res->dev, lbox))
+        if (int rc = launch_generic(p, args, stream, *res, lbox))
           return rc;
         ++p->last_launches;
       }
@@ -1758,6 +1867,237 @@ int soda_hip_last_residual(soda_hip_program_t* p, int32_t* mode,
   if (!p || !mode) return fail(SODA_HIP_ERR_INVALID, "last_residual: NULL");
   *mode = p->last_res_mode;
   if (fused_iters) *fused_iters = p->last_res_fused;
+  return SODA_HIP_OK;
+}
+
+// ---- exact norms: the handle and its entries ---------------------------------
+int soda_hip_norms_create(const void* code, size_t code_size, int32_t cell,
+                          int32_t dim, int32_t device,
+                          soda_hip_norms_handle_t** handle) {
+  static const char* const kCType[10] = {
+      "float", "double", "int8_t", "uint8_t", "int16_t", "uint16_t",
+      "int32_t", "uint32_t", "int64_t", "uint64_t"};
+  if (!code || !code_size || !handle)
+    return fail(SODA_HIP_ERR_INVALID, "norms_create: NULL argument");
+  *handle = nullptr;
+  int32_t elem = 0;
+  const int kind = soda_hip_norms_kind_of(cell, &elem);
+  if (!kind || dim < 1 || dim > SODA_HIP_MAX_DIM)
+    return fail(SODA_HIP_ERR_INVALID, "norms_create: bad cell type or dim");
+  int n = 0;
+  if (int rc = soda_hip_device_count(&n)) return rc;
+  if (n < 1) return fail(SODA_HIP_ERR_NODEVICE, "no GPU visible");
+  if (device < 0 || device >= n)
+    return fail(SODA_HIP_ERR_INVALID, "norms_create: no such device");
+  HIP_TRY(hipSetDevice(device));
+  soda_hip_norms_handle* h = new (std::nothrow) soda_hip_norms_handle;
+  if (!h) return fail(SODA_HIP_ERR_NOMEM, "new norms handle");
+  h->device = device;
+  h->cell = cell;
+  h->kind = kind;
+  h->elem = elem;
+  h->dim = dim;
+  hipError_t e = hipModuleLoadData(&h->module, code);
+  if (e != hipSuccess) {
+    delete h;
+    return hip_fail(e, "hipModuleLoadData");
+  }
+  e = hipModuleGetFunction(&h->zero, h->module, "soda_norms_zero");
+  for (int32_t v = 16 / elem; e == hipSuccess && v >= 1; v /= 2) {
+    const std::string name = std::string("soda_norms_") + kCType[cell] + "_v" +
+                             std::to_string(v);
+    hipFunction_t fn = nullptr;
+    e = hipModuleGetFunction(&fn, h->module, name.c_str());
+    h->widths.emplace_back(v, fn);
+  }
+  if (e != hipSuccess) {
+    (void)hipModuleUnload(h->module);
+    delete h;
+    return hip_fail(e, "norms_create: hipModuleGetFunction (is this the norms "
+                       "module of that cell type?)");
+  }
+  *handle = h;
+  return SODA_HIP_OK;
+}
+
+int soda_hip_norms_destroy(soda_hip_norms_handle_t* h) {
+  if (!h) return SODA_HIP_OK;
+  (void)hipSetDevice(h->device);
+  if (h->module) (void)hipModuleUnload(h->module);
+  delete h;
+  return SODA_HIP_OK;
+}
+
+static int check_norms_struct(const void* acc_dev, const char* who) {
+  if (reinterpret_cast<uintptr_t>(acc_dev) % 8)
+    return fail(SODA_HIP_ERR_INVALID,
+                std::string(who) + ": the norms struct is not 8-byte aligned; "
+                                   "nothing was launched");
+  return SODA_HIP_OK;
+}
+
+int soda_hip_norms_zero(soda_hip_norms_handle_t* h, void* acc_dev,
+                        void* stream) {
+  if (!h || !acc_dev)
+    return fail(SODA_HIP_ERR_INVALID, "norms_zero: NULL argument");
+  if (int rc = check_norms_struct(acc_dev, "norms_zero")) return rc;
+  HIP_TRY(hipSetDevice(h->device));
+  return norms_zero(h, acc_dev, static_cast<hipStream_t>(stream));
+}
+
+int soda_hip_norms_accumulate(soda_hip_norms_handle_t* h, const void* cur,
+                              const void* prev, const int32_t* extent,
+                              const int32_t* lo, const int32_t* hi,
+                              void* acc_dev, void* stream) {
+  if (!h || !cur || !prev || !extent || !lo || !hi || !acc_dev)
+    return fail(SODA_HIP_ERR_INVALID, "norms_accumulate: NULL argument");
+  if (int rc = check_norms_struct(acc_dev, "norms_accumulate")) return rc;
+  HIP_TRY(hipSetDevice(h->device));
+  return norms_accumulate(h, cur, prev, extent, lo, hi, acc_dev,
+                          static_cast<hipStream_t>(stream));
+}
+
+// what both norms runs ask of a program, a handle and the struct
+static int check_norms_run(const soda_hip_program* p,
+                           const soda_hip_norms_handle* h,
+                           void* const* outputs, const int32_t* extent,
+                           const void* acc_dev, const char* who) {
+  if (int rc = check_residual(p, outputs, extent, nullptr, who)) return rc;
+  const soda_hip_plan_t& plan = p->plan;
+  if (h->dim != plan.dim || h->device != p->device)
+    return fail(SODA_HIP_ERR_INVALID,
+                std::string(who) + ": the norms handle is of another dimension "
+                                   "count or device; nothing was launched");
+  for (int o = 0; o < plan.num_outputs; ++o)
+    if (plan.elem_size[o] != h->elem ||
+        plan.elem_size[plan.num_inputs + o] != h->elem)
+      return fail(SODA_HIP_ERR_UNSUPPORTED,
+                  std::string(who) + ": a pair's cells are not of the handle's "
+                                     "type (one struct holds one kind of "
+                                     "units); nothing was launched");
+  if (!acc_dev) return SODA_HIP_OK;
+  if (int rc = check_norms_struct(acc_dev, who)) return rc;
+  uint64_t cells = 1;
+  for (int d = 0; d < plan.dim; ++d)
+    cells *= (uint64_t)(extent[d] > 0 ? extent[d] : 0);
+  const uintptr_t r0 = reinterpret_cast<uintptr_t>(acc_dev);
+  for (int o = 0; o < plan.num_outputs; ++o) {
+    const uintptr_t o0 = reinterpret_cast<uintptr_t>(outputs[o]);
+    if (outputs[o] && r0 < o0 + cells * plan.elem_size[plan.num_inputs + o] &&
+        o0 < r0 + sizeof(soda_hip_norms_t))
+      return fail(SODA_HIP_ERR_INVALID,
+                  std::string(who) + ": the norms struct overlaps an output; "
+                                     "nothing was launched");
+  }
+  return SODA_HIP_OK;
+}
+
+int soda_hip_run_device_norms(soda_hip_program_t* p,
+                              soda_hip_norms_handle_t* h, void* const* outputs,
+                              const void* const* inputs, const int32_t* extent,
+                              int32_t iterate, void* acc_dev, void* stream_) {
+  if (!p || !h || !outputs || !inputs || !extent || !acc_dev)
+    return fail(SODA_HIP_ERR_INVALID, "run_device_norms: NULL argument");
+  p->last_res_mode = 0;
+  p->last_res_fused = 0;
+  p->last_launches = 0;
+  p->last_fused = 0;
+  if (int rc = check_norms_run(p, h, outputs, extent, acc_dev,
+                               "run_device_norms"))
+    return rc;
+  ResidualRun run = {acc_dev, iterate};
+  run.norms = h;
+  return run_core(p, outputs, inputs, extent, nullptr, nullptr, iterate,
+                  stream_, -1, nullptr, 1, &run);
+}
+
+int soda_hip_run_device_until_norm(soda_hip_program_t* p,
+                                   soda_hip_norms_handle_t* h,
+                                   void* const* outputs,
+                                   const void* const* inputs,
+                                   const int32_t* extent, int32_t max_iterate,
+                                   int32_t check_every, int32_t which,
+                                   double tol, soda_hip_norms_t* result_host,
+                                   int32_t* iterations_done, void* stream_) {
+  if (!p || !h || !outputs || !inputs || !extent)
+    return fail(SODA_HIP_ERR_INVALID, "run_device_until_norm: NULL argument");
+  if (max_iterate < 1 || check_every < 1)
+    return fail(SODA_HIP_ERR_INVALID,
+                "run_device_until_norm: max_iterate and check_every must be "
+                ">= 1");
+  if (which != SODA_HIP_NORMS_WHICH_L1 && which != SODA_HIP_NORMS_WHICH_L2)
+    return fail(SODA_HIP_ERR_INVALID, "run_device_until_norm: bad `which`");
+  if (int rc = check_norms_run(p, h, outputs, extent, nullptr,
+                               "run_device_until_norm"))
+    return rc;
+  const soda_hip_plan_t& plan = p->plan;
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  HIP_TRY(hipSetDevice(p->device));
+  hipStreamCaptureStatus capture = hipStreamCaptureStatusNone;
+  if (hipStreamIsCapturing(stream, &capture) != hipSuccess) {
+    (void)hipGetLastError();
+    capture = hipStreamCaptureStatusNone;
+  }
+  if (capture != hipStreamCaptureStatusNone)
+    return fail(SODA_HIP_ERR_INVALID,
+                "run_device_until_norm: synchronous, not for a stream that is "
+                "being captured; nothing was launched");
+  int64_t cells = 1;
+  for (int d = 0; d < plan.dim; ++d) {
+    if (extent[d] < 1)
+      return fail(SODA_HIP_ERR_INVALID, "run_device_until_norm: extent < 1");
+    cells *= extent[d];
+  }
+  if (int rc = ensure(p->until_norms, sizeof(soda_hip_norms_t))) return rc;
+  const int out0 = plan.num_inputs;
+  std::vector<const void*> in(inputs,
+                              inputs + plan.num_inputs + plan.num_params);
+  std::vector<void*> tmp(plan.num_outputs, nullptr);
+  std::vector<void*> own(outputs, outputs + plan.num_outputs);
+  soda_hip_norms_t host;
+  memset(&host, 0, sizeof host);
+  int32_t done = 0;
+  bool in_tmp = false;
+  for (int32_t chunk = 0; done < max_iterate; ++chunk) {
+    const int32_t n =
+        max_iterate - done < check_every ? max_iterate - done : check_every;
+    in_tmp = chunk % 2 == 1;
+    if (in_tmp && !tmp[0])
+      for (int o = 0; o < plan.num_outputs; ++o) {
+        if (int rc = ensure(p->until_tmp[o],
+                            (size_t)cells * plan.elem_size[out0 + o]))
+          return rc;
+        tmp[o] = p->until_tmp[o].ptr;
+      }
+    void* const* dst = in_tmp ? tmp.data() : own.data();
+    ResidualRun run = {p->until_norms.ptr, done + n};
+    run.norms = h;
+    if (int rc = run_core(p, dst, in.data(), extent, nullptr, nullptr, n,
+                          stream_, -1, nullptr, 1, &run))
+      return rc;
+    HIP_TRY(hipMemcpyAsync(&host, p->until_norms.ptr, sizeof host,
+                           hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    done += n;
+    // the next chunk continues from this one's result; the caller's inputs
+    // were read by the first chunk only
+    for (int j = 0; j < plan.num_inputs; ++j) in[j] = dst[j];
+    double norm = 0.0;
+    if (soda_hip_norms_value(&host, which, &norm))
+      return fail(SODA_HIP_ERR_RUNTIME,
+                  "run_device_until_norm: the struct fetched is of no kind");
+    if (which == SODA_HIP_NORMS_WHICH_L2) norm = sqrt(norm);
+    if (host.unordered == 0 && host.infinite == 0 && norm <= tol) break;
+  }
+  if (in_tmp) {
+    for (int o = 0; o < plan.num_outputs; ++o)
+      HIP_TRY(hipMemcpyAsync(outputs[o], tmp[o],
+                             (size_t)cells * plan.elem_size[out0 + o],
+                             hipMemcpyDeviceToDevice, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+  }
+  if (result_host) *result_host = host;
+  if (iterations_done) *iterations_done = done;
   return SODA_HIP_OK;
 }
 

@@ -106,6 +106,8 @@ struct soda_hip_program {
   // the caller's outputs (one per output), and the 32 bytes it fetches
   std::vector<soda_detail::DeviceBuffer> until_tmp;
   soda_detail::DeviceBuffer until_res;
+  // ... and the soda_hip_norms_t soda_hip_run_device_until_norm fetches
+  soda_detail::DeviceBuffer until_norms;
   // how the last soda_hip_run_device_residual took its residual (0 none,
   // 1 twin, 2 `<app>_residual`) and the fusion depth of its last pass
   int32_t last_res_mode = 0;
@@ -159,6 +161,16 @@ struct soda_hip_program {
   int ev_turn = 0;
 };
 
+// The kernels of one norms module (codegen/hip/norms.py) on one device: the
+// zeroing kernel and one accumulating kernel per fragment width, widest first
+struct soda_hip_norms_handle {
+  int device = 0;
+  int32_t cell = 0, kind = 0, elem = 0, dim = 0;
+  hipModule_t module = nullptr;
+  hipFunction_t zero = nullptr;
+  std::vector<std::pair<int32_t, hipFunction_t>> widths;
+};
+
 namespace soda_detail {
 
 // A run that also takes the residual of its last iteration
@@ -168,9 +180,13 @@ namespace soda_detail {
 // between two exchanges: the iterations since the state was the caller's).
 // On a slab (run_core's `slab`, `origin`, `global_extent`) the box is the
 // global grid's, cut to the slab's kept rows (soda_hip_plan_residual_slab_box)
+// `norms` != nullptr (soda_hip_run_device_norms): `dev` is a soda_hip_norms_t,
+// the run always ends in the one-iteration pass, and the handle's kernels run
+// in place of `<app>_residual_zero` and `<app>_residual`.
 struct ResidualRun {
   void* dev;
   int32_t box_iterate;
+  soda_hip_norms_handle* norms = nullptr;
 };
 
 // force_pass >= 0: use only that pass (calibration).  batch > 1: every
@@ -217,11 +233,12 @@ int plan_launches(const soda_hip_plan_t& plan,
 // whether it runs as its twin: the deepest scheduled pass whose kernel has
 // one; else the one-iteration pass, behind which `<app>_residual` runs --
 // taken out of a deeper pass's count where the schedule had none (iterate - 1
-// iterations rescheduled by `pass_ns`, one added).
+// iterations rescheduled by `pass_ns`, one added).  `generic_only`: never a
+// twin (a run that takes the norms; SODA_HIP_RESIDUAL_GENERIC=1 says the same).
 int residual_order(const soda_hip_plan_t& plan,
                    const std::vector<double>& pass_ns, int32_t iterate,
                    int32_t* count, int32_t* total, int* res_pass,
-                   bool* res_twin);
+                   bool* res_twin, bool generic_only = false);
 
 // tiles, modelled pass times and schedules of `plan` on `ext` (all
 // SODA_HIP_MAX_DIM entries filled) for launches over `batch` grids,

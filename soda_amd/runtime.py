@@ -113,6 +113,27 @@ class ResidualPlan(ctypes.Structure):
                MAX_RES_PAIRS)]
 
 
+NORMS_L1_WORDS, NORMS_L2_WORDS = 34, 67
+NORMS_L1, NORMS_L2 = 1, 2      # SODA_HIP_NORMS_WHICH_*
+
+
+class NormsStruct(ctypes.Structure):
+  """Mirror of soda_hip_norms_t: the exact sums of |d| and d^2 as wide
+  integers (include/soda_hip.h has the definition and the units)."""
+  _fields_ = [('kind', ctypes.c_uint32), ('reserved', ctypes.c_uint32),
+              ('count', ctypes.c_uint64), ('unordered', ctypes.c_uint64),
+              ('infinite', ctypes.c_uint64),
+              ('l1', ctypes.c_uint64 * NORMS_L1_WORDS),
+              ('l2', ctypes.c_uint64 * NORMS_L2_WORDS)]
+
+  def l1_int(self) -> int:
+    """The sum of |d| as a Python integer, in the kind's units."""
+    return sum(int(w) << (64 * i) for i, w in enumerate(self.l1))
+
+  def l2_int(self) -> int:
+    return sum(int(w) << (64 * i) for i, w in enumerate(self.l2))
+
+
 @dataclasses.dataclass(frozen=True)
 class Residual:
   """soda_hip_residual_t decoded: how much the last iteration of a run changed
@@ -283,6 +304,25 @@ API = {
         _vp, _i32, _i32, ctypes.c_double, ctypes.c_uint64,
         ctypes.POINTER(ResidualStruct), _pi32
     ]),
+    'soda_hip_norms_kind_of': (ctypes.c_int, [_i32, _pi32]),
+    'soda_hip_norms_fold': (ctypes.c_int, [ctypes.POINTER(NormsStruct),
+                                           ctypes.POINTER(NormsStruct)]),
+    'soda_hip_norms_value': (ctypes.c_int, [ctypes.POINTER(NormsStruct), _i32,
+                                            ctypes.POINTER(ctypes.c_double)]),
+    'soda_hip_norms_host': (ctypes.c_int, [_vp, _vp, _i32, _i32, _pi32, _pi32,
+                                           _pi32, ctypes.POINTER(NormsStruct)]),
+    'soda_hip_norms_create': (ctypes.c_int, [_vp, ctypes.c_size_t, _i32, _i32,
+                                             _i32, _pvp]),
+    'soda_hip_norms_destroy': (ctypes.c_int, [_vp]),
+    'soda_hip_norms_zero': (ctypes.c_int, [_vp, _vp, _vp]),
+    'soda_hip_norms_accumulate': (ctypes.c_int, [_vp, _vp, _vp, _pi32, _pi32,
+                                                 _pi32, _vp, _vp]),
+    'soda_hip_run_device_norms': (ctypes.c_int, [_vp, _vp, _pvp, _pvp, _pi32,
+                                                 _i32, _vp, _vp]),
+    'soda_hip_run_device_until_norm': (ctypes.c_int, [
+        _vp, _vp, _pvp, _pvp, _pi32, _i32, _i32, _i32, ctypes.c_double,
+        ctypes.POINTER(NormsStruct), _pi32, _vp
+    ]),
     'soda_hip_run_device_window': (ctypes.c_int, [_vp, _pvp, _pvp, _pi32, _pi32,
                                                   _pi32, _i32, _vp]),
     'soda_hip_run_device_cone': (ctypes.c_int, [_vp, _pvp, _pvp, _pi32, _pi32,
@@ -419,7 +459,7 @@ def library() -> ctypes.CDLL:
                           (4, HostTensor), (5, StreamDesc), (6, SlabRun),
                           (7, GroupDesc), (8, SlabInfo), (9, GroupStats),
                           (10, LaunchInfo), (11, ResidualStruct),
-                          (12, ResBox)):
+                          (12, ResBox), (14, NormsStruct)):
       if lib.soda_hip_sizeof(which) != ctypes.sizeof(mirror):
         raise util.BackendError(
             'struct layout mismatch between libsoda_hip.so and runtime.py '
@@ -1060,6 +1100,139 @@ def clipped_box(box, extent: Sequence[int]):
   return lo, hi
 
 
+# -- exact L1 / L2 norms of a residual -----------------------
+def norms_value(acc: NormsStruct, which: str) -> float:
+  """The correctly rounded double of the sum of |d| (`which` = 'l1') or of d^2
+  ('l2') an accumulator holds (soda_hip_norms_value; no GPU needed): +inf
+  above the double range or when a delta was infinite."""
+  out = ctypes.c_double()
+  check(library().soda_hip_norms_value(
+      ctypes.byref(acc), {'l1': NORMS_L1, 'l2': NORMS_L2}[which],
+      ctypes.byref(out)), 'norms_value')
+  return out.value
+
+
+def norms_fold(dst: NormsStruct, src: NormsStruct) -> NormsStruct:
+  """dst += src, exactly (soda_hip_norms_fold; no GPU needed): how the shares
+  of bands, slabs or pairs become the norms of the whole.  Returns dst."""
+  check(library().soda_hip_norms_fold(ctypes.byref(dst), ctypes.byref(src)),
+        'norms_fold (kinds must match)')
+  return dst
+
+
+def _norms_cell(c_type: str):
+  from soda_amd.codegen.hip import norms as _norms
+  if c_type not in _norms.CELLS:
+    raise util.InputError('norms: no kernels for cells of type `%s`' % c_type)
+  return _norms.CELLS[c_type]
+
+
+def norms_empty(c_type: str) -> NormsStruct:
+  """A zeroed accumulator of the kind of `c_type` cells."""
+  acc = NormsStruct()
+  acc.kind = _norms_cell(c_type)[2]
+  return acc
+
+
+def norms_host(cur, prev, lo: Sequence[int], hi: Sequence[int],
+               acc: Optional[NormsStruct] = None) -> NormsStruct:
+  """The reduction in plain C++ on numpy arrays (soda_hip_norms_host; no GPU
+  needed): the cells [lo, hi) -- dimension 0, the fastest, first -- of `cur`
+  against `prev`, added to `acc` (default: a fresh one)."""
+  import numpy as np
+  cur, prev = np.ascontiguousarray(cur), np.ascontiguousarray(prev)
+  if cur.dtype != prev.dtype or cur.shape != prev.shape:
+    raise util.InputError('norms_host: two arrays of one dtype and shape')
+  c_type = {'float32': 'float', 'float64': 'double'}.get(
+      cur.dtype.name, cur.dtype.name + '_t')
+  cell = _norms_cell(c_type)[0]
+  acc = norms_empty(c_type) if acc is None else acc
+  dim = cur.ndim
+  ext = (ctypes.c_int32 * dim)(*cur.shape[::-1])
+  check(library().soda_hip_norms_host(
+      cur.ctypes.data, prev.ctypes.data, cell, dim, ext,
+      (ctypes.c_int32 * dim)(*lo), (ctypes.c_int32 * dim)(*hi),
+      ctypes.byref(acc)), 'norms_host')
+  return acc
+
+
+def norms_resources(c_type: str, dim: int):
+  """(code object, kernel_resources of it) of the norms module of a cell type
+  and dimension count: JIT-built like every module, cached like them; needs
+  no GPU."""
+  from soda_amd.codegen.hip import norms as _norms
+  code = compile_source(_norms.source(c_type, dim),
+                        'norms_%s_%dd.hip' % (c_type, dim))
+  return code, kernel_resources(code)
+
+
+class Norms:
+  """The norms kernels of one cell type and dimension count on one GPU
+  (soda_hip_norms_create): zero / accumulate / fetch on a caller's 840 device
+  bytes.  Independent of any Program; `Program.norms()` makes the one that
+  fits a program."""
+
+  def __init__(self, c_type: str, dim: int, device: int = 0):
+    self.c_type, self.dim, self.device = c_type, dim, device
+    self.cell, self.elem, self.kind = _norms_cell(c_type)
+    self.code, self.resources = norms_resources(c_type, dim)
+    self._lib = library()
+    self._handle = ctypes.c_void_p()
+    check(self._lib.soda_hip_norms_create(self.code, len(self.code), self.cell,
+                                          dim, device,
+                                          ctypes.byref(self._handle)),
+          'loading the norms kernels (%s, %d-D) on GPU %d' % (c_type, dim,
+                                                              device))
+
+  def close(self) -> None:
+    if getattr(self, '_handle', None):
+      self._lib.soda_hip_norms_destroy(self._handle)
+      self._handle = None
+
+  def __del__(self):
+    try:
+      self.close()
+    except Exception:  # interpreter shutdown
+      pass
+
+  def __enter__(self):
+    return self
+
+  def __exit__(self, *exc):
+    self.close()
+
+  def zero(self, acc: int, stream: int = 0) -> None:
+    """Zeroes the struct at device address `acc` (a kernel on `stream`)."""
+    check(self._lib.soda_hip_norms_zero(self._handle, ctypes.c_void_p(acc),
+                                        ctypes.c_void_p(stream)), 'norms: zero')
+
+  def accumulate(self, cur: int, prev: int, extent: Sequence[int],
+                 lo: Sequence[int], hi: Sequence[int], acc: int,
+                 stream: int = 0) -> None:
+    """Adds the cells [lo, hi) of the dense device arrays `cur` against `prev`
+    to the struct at `acc`; asynchronous on `stream`, never allocates, does
+    not zero (soda_hip_norms_accumulate)."""
+    n = self.dim
+    if len(extent) != n or len(lo) != n or len(hi) != n:
+      raise util.InputError('norms: extent, lo and hi must have %d entries' % n)
+    check(self._lib.soda_hip_norms_accumulate(
+        self._handle, ctypes.c_void_p(cur), ctypes.c_void_p(prev),
+        (ctypes.c_int32 * n)(*extent), (ctypes.c_int32 * n)(*lo),
+        (ctypes.c_int32 * n)(*hi), ctypes.c_void_p(acc),
+        ctypes.c_void_p(stream)), 'norms: accumulate')
+
+  def fetch(self, acc: int, stream: int = 0) -> NormsStruct:
+    """The struct at device address `acc`: copied on `stream`, waited for."""
+    raw = NormsStruct()
+    check(self._lib.soda_hip_memcpy_d2h(ctypes.byref(raw), ctypes.c_void_p(acc),
+                                        ctypes.sizeof(raw),
+                                        ctypes.c_void_p(stream)),
+          'norms: copy out')
+    check(self._lib.soda_hip_stream_synchronize(ctypes.c_void_p(stream)),
+          'norms: synchronize')
+    return raw
+
+
 class Program:
   """A SODA program JIT-built for gfx950 and loaded on one GPU."""
 
@@ -1155,6 +1328,9 @@ class Program:
 
   # -- lifecycle -----------------------------------------------------------
   def close(self) -> None:
+    if getattr(self, '_norms', None) is not None:
+      self._norms.close()
+      self._norms = None
     if getattr(self, '_handle', None):
       self._lib.soda_hip_program_destroy(self._handle)
       self._handle = None
@@ -1189,7 +1365,8 @@ class Program:
                  ghosts_ready: int = 0, sendable: int = 0,
                  batch: Optional[int] = None,
                  residual: Optional[int] = None,
-                 box_iterate: Optional[int] = None) -> None:
+                 box_iterate: Optional[int] = None,
+                 norms: Optional[int] = None) -> None:
     """`outputs` / `inputs` are device addresses (e.g. tensor.data_ptr()) of
     dense dim-0-fastest arrays; asynchronous on `stream`.  `inputs` holds the
     input tensors followed by the program's `param` arrays (C order).
@@ -1254,7 +1431,16 @@ class Program:
     less) -- ghost rows of the result not among them; the shares of all slabs
     add up (counts) and take the larger (maxima).  A last pass split around
     the exchange completes the struct with its interior part, behind
-    `sendable`.  Not together with `batch`."""
+    `sendable`.  Not together with `batch`.
+    `norms` = the device address of a soda_hip_norms_t (840 bytes, 8-byte
+    aligned; ctypes.sizeof(NormsStruct)): the run also leaves there the exact
+    sums of |d| and d^2 over the deltas of its LAST iteration
+    (soda_hip_run_device_norms; `norms().fetch(ptr)` reads them,
+    `norms_value` rounds them).  The run ends in the one-iteration pass, then
+    the struct is zeroed and filled on `stream`: asynchronous and capturable
+    like a `residual` run.  Needs a program built with LowerOptions.residual
+    whose tensors all have one cell type.  Whole grids only: not together with
+    `residual`, `batch`, `origin` / `keep` / `ghosts` / `sends`."""
     st = self.stencil
     iterate = st.iterate if iterate is None else iterate
     self._check_extent(extent)
@@ -1264,6 +1450,20 @@ class Program:
     outs = (ctypes.c_void_p * len(outputs))(*outputs)
     ins = (ctypes.c_void_p * len(inputs))(*inputs)
     ext = (ctypes.c_int32 * len(extent))(*extent)
+    if norms is not None:
+      if residual is not None or batch is not None or keep is not None or \
+          ghosts is not None or sends is not None or origin is not None or \
+          global_extent is not None or ghosts_ready or sendable or \
+          box_iterate is not None:
+        raise util.InputError(
+            'run_device: norms are taken on whole grids: not together with '
+            'residual / batch / keep / ghosts / sends / origin')
+      check(
+          self._lib.soda_hip_run_device_norms(
+              self._handle, self.norms()._handle, outs, ins, ext, iterate,
+              ctypes.c_void_p(norms), ctypes.c_void_p(stream)),
+          'running `%s` with norms' % st.app_name)
+      return
     if residual is not None:
       if batch is not None:
         raise util.InputError(
@@ -1352,6 +1552,22 @@ class Program:
           'residual: synchronize')
     return Residual.from_struct(raw)
 
+  def norms(self) -> Norms:
+    """The norms kernels that fit this program (one per Program, made on first
+    use, closed with it): its cell type, its dimension count, its GPU.
+    util.InputError for a program of mixed cell types: one accumulator holds
+    one kind of units."""
+    if getattr(self, '_norms', None) is None:
+      st = self.stencil
+      types = {t.c_type for t in list(st.input_types) + list(st.output_types)}
+      if len(types) != 1:
+        raise util.InputError(
+            'norms: the tensors of `%s` have cells of types %s; one '
+            'accumulator holds one kind of units' %
+            (st.app_name, ', '.join(sorted(types))))
+      self._norms = Norms(types.pop(), st.dim, self.device)
+    return self._norms
+
   def last_residual(self):
     """How the last `run_device(..., residual=)` took its residual: ('twin' |
     'generic' | None, fusion depth of the pass launched last)."""
@@ -1375,7 +1591,8 @@ class Program:
                              keep)
 
   def run_until(self, inputs: Dict[str, 'numpy.ndarray'], tol: float,
-                max_iterate: int, check_every: int = 8, int_tol: int = 0):
+                max_iterate: int, check_every: int = 8, int_tol: int = 0,
+                norm: Optional[str] = None):
     """Iterates on numpy arrays until converged: `check_every` iterations at a
     time, stopping when the last iteration's residual has `unordered == 0`,
     `max_float <= tol` and `max_int <= int_tol`, or after `max_iterate`
@@ -1383,8 +1600,17 @@ class Program:
     iterations done, Residual).  Like `run`, the outputs start as zeros and
     only each output's valid box after the iterations done is written; the
     input arrays are not touched.  Needs a program built with
-    LowerOptions.residual."""
+    LowerOptions.residual.
+    `norm` = 'l1' | 'l2': stop on the exact norm of the last iteration's
+    deltas instead -- `unordered == 0`, `infinite == 0` and sum |d| <= tol
+    ('l1') or sqrt(sum d^2) <= tol ('l2'), the sums rounded once
+    (soda_hip_run_device_until_norm); the third value returned is then the
+    NormsStruct of the last chunk and `int_tol` is not used.  None: the rule
+    above, exactly as before."""
     import numpy as np
+    if norm not in (None, 'l1', 'l2'):
+      raise util.InputError("run_until: norm is None, 'l1' or 'l2'")
+    norms = self.norms() if norm is not None else None
     st = self.stencil
     lib = self._lib
     first = np.asarray(inputs[st.input_names[0]])
@@ -1409,7 +1635,7 @@ class Program:
     dense = [np.empty(first.shape, dtype=np.dtype(t.np_name))
              for t in st.output_types]
     dev_in, dev_out = [], []
-    raw = ResidualStruct()
+    raw = ResidualStruct() if norm is None else NormsStruct()
     done = ctypes.c_int32(0)
     try:
       for arr in host_in:
@@ -1427,13 +1653,21 @@ class Program:
       outs = (ctypes.c_void_p * len(dev_out))(*[p.value for p in dev_out])
       ins = (ctypes.c_void_p * len(dev_in))(*[p.value for p in dev_in])
       ext = (ctypes.c_int32 * len(extent))(*extent)
-      check(
-          lib.soda_hip_run_device_until(self._handle, outs, ins, ext,
-                                        int(max_iterate), int(check_every),
-                                        float(tol), int(int_tol),
-                                        ctypes.byref(raw), ctypes.byref(done),
-                                        None),
-          'running `%s` until converged' % st.app_name)
+      if norm is None:
+        check(
+            lib.soda_hip_run_device_until(self._handle, outs, ins, ext,
+                                          int(max_iterate), int(check_every),
+                                          float(tol), int(int_tol),
+                                          ctypes.byref(raw), ctypes.byref(done),
+                                          None),
+            'running `%s` until converged' % st.app_name)
+      else:
+        check(
+            lib.soda_hip_run_device_until_norm(
+                self._handle, norms._handle, outs, ins, ext, int(max_iterate),
+                int(check_every), {'l1': NORMS_L1, 'l2': NORMS_L2}[norm],
+                float(tol), ctypes.byref(raw), ctypes.byref(done), None),
+            'running `%s` until its %s norm is small' % (st.app_name, norm))
       for arr, ptr in zip(dense, dev_out):
         check(lib.soda_hip_memcpy_d2h(arr.ctypes.data, ptr, arr.nbytes, None),
               'run_until: copy out')
@@ -1447,7 +1681,8 @@ class Program:
       box = tuple(slice(l, h) for l, h in zip(lo, hi))[::-1]
       result[n] = np.zeros_like(arr)
       result[n][box] = arr[box]
-    return result, done.value, Residual.from_struct(raw)
+    return result, done.value, (Residual.from_struct(raw) if norm is None
+                                else raw)
 
   def last_split(self) -> int:
     """Passes of the last run launched in two parts around a halo exchange."""
