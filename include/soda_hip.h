@@ -71,7 +71,9 @@ extern "C" {
  * soda_hip_group_last_residual, soda_hip_group_run_until; and the exact L1 /
  * L2 norms of the residual -- soda_hip_norms_t with soda_hip_norms_fold /
  * _value / _host / _create / _destroy / _zero / _accumulate,
- * soda_hip_run_device_norms and soda_hip_run_device_until_norm. */
+ * soda_hip_run_device_norms and soda_hip_run_device_until_norm; and periodic
+ * domains -- soda_hip_wrap_host, soda_hip_periodic_plan / _create / _destroy /
+ * _info / _fill / _run_padded / _run_device. */
 #define SODA_HIP_ABI_VERSION 9
 #define SODA_HIP_MAX_DIM 4
 #define SODA_HIP_MAX_TENSORS 16
@@ -302,8 +304,8 @@ int soda_hip_device_count(int* count);
 /* sizeof() of the ABI structs as this library was compiled, for bindings to
  * check their mirrors: 0 kargs, 1 kernel_desc, 2 pass_desc, 3 plan,
  * 4 host_tensor, 5 stream_desc, 6 slab_run, 7 group_desc, 8 slab_info,
- * 9 group_stats, 10 launch_info, 11 residual, 12 resbox, 14 norms; 0 for
- * anything else (13 among them). */
+ * 9 group_stats, 10 launch_info, 11 residual, 12 resbox, 14 norms,
+ * 15 periodic_desc, 16 periodic_info; 0 for anything else (13 among them). */
 size_t soda_hip_sizeof(int which);
 
 /* -- JIT: HIP source text -> gfx950 code object (hiprtc; needs no GPU) ---- */
@@ -773,6 +775,137 @@ int soda_hip_run_device_until_norm(soda_hip_program_t* program,
                                    int32_t check_every, int32_t which,
                                    double tol, soda_hip_norms_t* result_host,
                                    int32_t* iterations_done, void* stream);
+
+/* -- periodic domains: a program on a torus ---------------- */
+/* Every run entry above computes on an open box.  Here the domain of extent N
+ * is a torus: cell N is cell 0, in every dimension.  The state lives in PADDED
+ * arrays of extent P[d] = ghost_lo[d] + N[d] + ghost_hi[d], dense and
+ * dim-0-fastest; the interior [ghost_lo, ghost_lo + N) is the torus, and a
+ * ghost cell at padded index i mirrors the interior cell
+ *   ghost_lo + ((i - ghost_lo) mod N)        (the mathematical modulo)
+ * in every dimension at once -- a domain narrower than its ghost frame wraps
+ * more than once.  An array whose ghost cells all hold that is WRAPPED.
+ * A frame as wide as k iterations reach carries k iterations of the program's
+ * ordinary kernels on the padded extent: SODA programs are translation
+ * invariant, so a ghost cell evolves into what the wrap of the evolved
+ * interior gives, for as long as its window stays inside the array.  The run
+ * entries advance k iterations through the ordinary run path on P, refill
+ * the frame with one small kernel (codegen/hip/wrap.py, a module of its own
+ * per cell size and dimension count), and go on.  The result does not depend
+ * on k, bit for bit.
+ * Not served on a torus: residuals, norms, run_until, slabs, groups, ranks,
+ * batches, the wire format, `border: preserve` (a torus has no border). */
+typedef struct soda_hip_periodic_desc {
+  int32_t extent[SODA_HIP_MAX_DIM];    /* N, the torus */
+  int32_t refill_every;                /* k: iterations between two refills;
+                                          0: the largest fused_iters of the
+                                          plan's passes, so that a chunk is one
+                                          launch at the deepest depth */
+  int32_t ghost_lo[SODA_HIP_MAX_DIM];  /* cells k iterations reach below ... */
+  int32_t ghost_hi[SODA_HIP_MAX_DIM];  /* ... and above a cell, at least: the
+                                          most over all outputs of the window
+                                          of k iterations (the caller's to
+                                          compute: Stencil.window_bounds(k)).
+                                          The library rounds ghost_hi[0] up
+                                          until P[0] is a multiple of the
+                                          plan's widest `vec` */
+  int32_t preserve;                    /* != 0: the program was written with
+                                          `border: preserve`, which the plan
+                                          does not say: refused */
+  int32_t not_iterable;                /* != 0: the outputs are not of the
+                                          inputs' types (the plan holds cell
+                                          sizes only): iterate > 1 is refused
+                                          as on a plan with other numbers of
+                                          inputs and outputs */
+} soda_hip_periodic_desc_t;
+typedef struct soda_hip_periodic_info {
+  int32_t refill_every;                /* k as resolved */
+  int32_t ghost_lo[SODA_HIP_MAX_DIM];
+  int32_t ghost_hi[SODA_HIP_MAX_DIM];  /* [0] as rounded */
+  int32_t padded[SODA_HIP_MAX_DIM];    /* P */
+  int32_t reserved;
+  int64_t scratch_bytes;               /* device bytes a handle holds: one
+                                          padded array per input, two per
+                                          output (one if the program cannot
+                                          iterate) */
+} soda_hip_periodic_info_t;
+/* The fill on a host array, in plain C++ (no GPU, no allocation): every ghost
+ * cell of the padded, dense, dim-0-fastest `array` of `elem_bytes`-byte cells
+ * (1, 2, 4 or 8) takes its interior cell.  `extent` is N. */
+int soda_hip_wrap_host(void* array, int32_t elem_bytes, int32_t dim,
+                       const int32_t* extent, const int32_t* ghost_lo,
+                       const int32_t* ghost_hi);
+/* What a handle over `plan` and `desc` would use, and how `iterate`
+ * iterations are cut: *info (ghosts, P, k; scratch_bytes), and the iterations
+ * of every chunk -- k each, the last may be shorter -- in chunks[0, *count)
+ * (at most `capacity` written; `chunks` may be NULL, iterate 0: no chunks).
+ * Pure function (no GPU, no program).  Refuses what
+ * soda_hip_periodic_create and the run entries refuse:
+ *   SODA_HIP_ERR_UNSUPPORTED  desc->preserve or a plan whose residual says
+ *                             `whole`; a batched plan;
+ *   SODA_HIP_ERR_INVALID      extent < 1, negative ghosts or k; with
+ *                             plan->has_reach, ghosts along the last
+ *                             dimension below k x reach; iterate > 1 on a
+ *                             plan with other numbers or cell sizes of
+ *                             inputs and outputs, or desc->not_iterable;
+ *                             P the kernels cannot run: P[0] beyond a
+ *                             max_extent0, a plane above the 1 GiB window
+ *                             (soda_hip_plan_geometry on P). */
+int soda_hip_periodic_plan(const soda_hip_plan_t* plan,
+                           const soda_hip_periodic_desc_t* desc,
+                           int32_t iterate, soda_hip_periodic_info_t* info,
+                           int32_t capacity, int32_t* chunks, int32_t* count);
+/* A handle over `program` for ONE torus.  wrap_code[i] / wrap_code_size[i]:
+ * the code object of the wrap module of 1 << i byte cells and the program's
+ * dimension count, i = 0..3; needed for every cell size among the program's
+ * inputs and outputs, NULL elsewhere.  All scratch of the handle is allocated
+ * here.  A refusal (soda_hip_periodic_plan's, or a program on wire-format
+ * banks: SODA_HIP_ERR_UNSUPPORTED) launches nothing and allocates nothing.
+ * The handle must be destroyed before its program. */
+typedef struct soda_hip_periodic soda_hip_periodic_t;   /* opaque */
+int soda_hip_periodic_create(soda_hip_program_t* program,
+                             const soda_hip_periodic_desc_t* desc,
+                             const void* const* wrap_code,
+                             const size_t* wrap_code_size,
+                             soda_hip_periodic_t** handle);
+int soda_hip_periodic_destroy(soda_hip_periodic_t* handle);
+int soda_hip_periodic_info(soda_hip_periodic_t* handle,
+                           soda_hip_periodic_info_t* info);
+/* The primitive: refills the ghost frame of `count` caller-owned padded device
+ * arrays in place, array i with the cells of the program's output i (count <=
+ * num_outputs), each aligned to its cell size.  One launch per cell size
+ * among them -- one in all for a program of one cell type.  Reads interior
+ * cells only, writes ghost cells only.  Asynchronous on `stream`, never
+ * allocates, capturable as it stands. */
+int soda_hip_periodic_fill(soda_hip_periodic_t* handle, void* const* arrays,
+                           int32_t count, void* stream);
+/* `iterate` iterations on PADDED device arrays; the state stays padded and
+ * device-resident across calls.  `inputs` (the num_inputs tensors, then the
+ * param arrays, which pass through unchanged) arrive WRAPPED, `outputs` leave
+ * wrapped, the inputs are never written.  Chunks of k iterations (the last
+ * may be shorter) go through soda_hip_run_device on P, a fill behind each;
+ * they ping-pong between `outputs` and one scratch set of the handle so that
+ * the last chunk lands in `outputs`.  The device entry contract holds on the
+ * padded arrays.  Under "Streams, scratch, graphs": asynchronous on `stream`,
+ * never allocates in the handle; the PROGRAM's own scratch is sized for P by
+ * the first call like any soda_hip_run_device on P (and that call calibrates,
+ * where the program does), after which the call can be captured.  One queue:
+ * the handle shares its program's.  SODA_HIP_ERR_INVALID, nothing launched:
+ * iterate < 1, iterate > 1 on a program that cannot iterate. */
+int soda_hip_periodic_run_padded(soda_hip_periodic_t* handle,
+                                 void* const* outputs,
+                                 const void* const* inputs, int32_t iterate,
+                                 void* stream);
+/* The same on DENSE domain arrays of N: the inputs are padded into scratch
+ * (every cell, ghosts included), the loop above runs on scratch, the interior
+ * is cropped into `outputs`.  The device entry contract of soda_hip_run_device
+ * holds on the dense arrays -- overlap, alignment, inputs never written, no
+ * byte outside the outputs -- and so does "Streams, scratch, graphs" as for
+ * the entry above.  Every cell of every output is defined. */
+int soda_hip_periodic_run_device(soda_hip_periodic_t* handle,
+                                 void* const* outputs,
+                                 const void* const* inputs, int32_t iterate,
+                                 void* stream);
 
 /* Replaces soda::app::<app>(): host arrays described by (ptr, extent, stride,
  * min) per tensor, inputs then outputs; copies in, runs, copies the outputs

@@ -12,7 +12,7 @@ opencl.py:55-142).  This module slots into the same place:
   --hip-backend       JIT-build the kernels for gfx950 and RUN the program on
                       the GPU with the reference harness's inputs, checking
                       nothing by itself (the oracle lives in tests/); prints
-                      one JSON line with timing.
+                      one JSON line with timing.  --hip-periodic: on a torus.
 """
 import argparse
 import json
@@ -106,6 +106,17 @@ def add_arguments(parser) -> None:
                       default=8, metavar='K',
                       help='with --hip-until: iterations between two looks at '
                       'the residual (default 8)')
+  parser.add_argument('--hip-periodic', action='store_true',
+                      dest='hip_periodic',
+                      help='--hip-backend: run on a torus -- cell N is cell 0 '
+                      'in every dimension, every cell of the outputs is '
+                      'defined; the ghost frame is refilled on the GPU '
+                      '(soda_hip_periodic_run_device; one GPU, no --hip-until)')
+  parser.add_argument('--hip-refill-every', type=int, dest='hip_refill_every',
+                      default=None, metavar='K',
+                      help='with --hip-periodic: iterations between two '
+                      'refills of the ghost frame (default: the deepest '
+                      'fusion depth)')
   parser.add_argument('--hip-nt-store', action='store_true',
                       dest='hip_nt_store',
                       help='non-temporal instead of plain output stores')
@@ -228,6 +239,12 @@ def run(stencil: core.Stencil, args: argparse.Namespace) -> None:
         pstmt.haoda_type.np_name)
   gpus = max(1, int(getattr(args, 'hip_gpus', 1) or 1))
   extra = {}
+  periodic = bool(getattr(args, 'hip_periodic', False))
+  if periodic and (gpus > 1 or getattr(args, 'hip_until', None) is not None
+                   or getattr(args, 'hip_residual', False)):
+    raise util.InputError('--hip-periodic runs on one GPU, without --hip-until '
+                          'or --hip-residual (slabs, groups and residuals are '
+                          'not served on a torus yet)')
   if gpus > 1:
     # one host thread, N GPUs: slabs along the streamed dimension
     devices = ([args.hip_device] * gpus if getattr(args, 'hip_virtual', False)
@@ -287,6 +304,11 @@ def run(stencil: core.Stencil, args: argparse.Namespace) -> None:
                'residual': {'changed': res.changed, 'unordered': res.unordered,
                             'max_float': res.max_float,
                             'max_int': res.max_int}}
+    elif periodic:
+      k = getattr(args, 'hip_refill_every', None)
+      outputs = prog.run_periodic(inputs, refill_every=k)
+      extra = {'periodic': True, 'refill_every': k or max(
+          p.fused_iters for p in prog.module.passes)}
     else:
       outputs = prog.run(inputs)
     seconds = time.time() - t0

@@ -142,6 +142,8 @@ size_t soda_hip_sizeof(int which) {
     case 11: return sizeof(soda_hip_residual_t);
     case 14: return sizeof(soda_hip_norms_t);
     case 12: return sizeof(soda_hip_resbox_t);
+    case 15: return sizeof(soda_hip_periodic_desc_t);
+    case 16: return sizeof(soda_hip_periodic_info_t);
     default: return 0;
   }
 }

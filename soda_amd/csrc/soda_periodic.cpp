@@ -1,0 +1,551 @@
+// soda_periodic.cpp -- periodic domains: a program on a torus (DESIGN.md 4.11,
+// include/soda_hip.h soda_hip_periodic_*).  A handle over an existing program
+// keeps the state in padded arrays, advances it k iterations at a time through
+// the program's ordinary run path on the padded extent (run_core) and refills
+// the ghost frame in between with the wrap kernel (soda_rt_wrap.h), which also
+// pads the dense entry's inputs and crops its outputs.  The program, its
+// module and its plan know nothing of this.
+#include "soda_internal.h"
+
+#include <cstring>
+#include <new>
+
+using namespace soda_detail;
+
+namespace {
+
+const int kWrapBlock = 256;
+const int kWrapMaxRegions = 5;
+const int64_t kWrapMaxBlocks = 1 << 15;   // the lanes stride over the items
+
+// the kernel's one argument, as soda_rt_wrap.h declares it
+struct WrapArgs {
+  void* dst[16];
+  const void* src[16];
+  int32_t dext[4];
+  int32_t sext[4];
+  int32_t n[4];
+  int32_t sub[4];
+  int32_t add[4];
+  int32_t glo[4];
+  int32_t nreg;
+  int32_t level[kWrapMaxRegions];
+  uint32_t per_row[kWrapMaxRegions];
+  uint32_t ends[kWrapMaxRegions];
+  uint32_t reserved;
+  uint64_t start[kWrapMaxRegions];
+  uint64_t total;
+};
+
+enum WrapJob { kFill, kPad, kCrop };
+
+struct Torus {
+  int dim;
+  int32_t n[4], glo[4], ghi[4], p[4];
+};
+
+int32_t plan_vec(const soda_hip_plan_t& plan) {
+  int32_t vec = 1;
+  for (int k = 0; k < plan.num_kernels; ++k)
+    if (plan.kernels[k].vec > vec) vec = plan.kernels[k].vec;
+  return vec;
+}
+
+// The regions of a job on cells of `elem` bytes (soda_rt_wrap.h); false if a
+// region has 2^31 rows or more (the kernel counts rows in 32 bits).
+bool wrap_regions(const Torus& t, WrapJob job, int elem, WrapArgs* a) {
+  const int dim = t.dim, v = 16 / elem;
+  for (int d = 0; d < 4; ++d) {
+    const bool in = d < dim;
+    a->n[d] = in ? t.n[d] : 1;
+    a->glo[d] = in ? t.glo[d] : 0;
+    a->dext[d] = in ? (job == kCrop ? t.n[d] : t.p[d]) : 1;
+    a->sext[d] = in ? (job == kPad ? t.n[d] : t.p[d]) : 1;
+    a->sub[d] = in && job != kCrop ? t.glo[d] : 0;
+    a->add[d] = in && job != kPad ? t.glo[d] : 0;
+  }
+  a->nreg = 0;
+  a->total = 0;
+  auto add = [&](int level, int64_t rows, int64_t per_row, bool ends) {
+    if (rows < 1 || per_row < 1) return true;     // an empty region
+    if (rows > 0x7fffffffLL || per_row > 0x7fffffffLL) return false;
+    const int k = a->nreg++;
+    a->level[k] = level;
+    a->per_row[k] = (uint32_t)per_row;
+    a->ends[k] = ends ? 1u : 0u;
+    a->start[k] = a->total;
+    a->total += (uint64_t)rows * (uint64_t)per_row;
+    return true;
+  };
+  // fragments a whole row may need: it starts up to v - 1 cells behind a
+  // 16-byte boundary
+  const int64_t frags = ((int64_t)a->dext[0] + 2 * v - 2) / v;
+  if (job != kFill) {
+    int64_t rows = 1;
+    for (int d = 1; d < dim; ++d) rows *= a->dext[d];
+    return add(dim, rows, frags, false);
+  }
+  // fill: the rows with dimension `level` in the ghost frame, the dimensions
+  // above it inside the torus, those below it anywhere -- every ghost row
+  // exactly once -- and the two ends of the rows inside the torus
+  for (int level = dim - 1; level >= 1; --level) {
+    int64_t rows = t.p[level] - t.n[level];
+    for (int d = 1; d < dim; ++d)
+      if (d != level) rows *= d < level ? t.p[d] : t.n[d];
+    if (!add(level, rows, frags, false)) return false;
+  }
+  int64_t inner = 1;
+  for (int d = 1; d < dim; ++d) inner *= t.n[d];
+  return add(0, inner, (int64_t)t.glo[0] + t.ghi[0], true);
+}
+
+}  // namespace
+
+struct soda_hip_periodic {
+  soda_hip_program* prog = nullptr;
+  Torus t;
+  int32_t k = 1;
+  bool not_iterable = false;
+  hipModule_t module[4] = {nullptr, nullptr, nullptr, nullptr};
+  hipFunction_t fn[4] = {nullptr, nullptr, nullptr, nullptr};   // by log2(elem)
+  std::vector<DeviceBuffer> pad_in;    // dense entry: the padded inputs
+  std::vector<DeviceBuffer> pad_out;   // ... and outputs
+  std::vector<DeviceBuffer> pong;      // the chunks' partner of the outputs
+};
+
+namespace {
+
+int log2_elem(int elem) {
+  return elem == 1 ? 0 : elem == 2 ? 1 : elem == 4 ? 2 : elem == 8 ? 3 : -1;
+}
+
+int64_t cells_of(const int32_t* e, int dim) {
+  int64_t c = 1;
+  for (int d = 0; d < dim; ++d) c *= e[d];
+  return c;
+}
+
+// One job on `count` tensors: dst[i] / src[i] with cells of elem[i] bytes; one
+// launch per cell size among them.
+int wrap_launch(soda_hip_periodic* h, WrapJob job, void* const* dst,
+                const void* const* src, const int32_t* elem, int count,
+                hipStream_t stream) {
+  for (int size = 1; size <= 8; size *= 2) {
+    WrapArgs a;
+    memset(&a, 0, sizeof a);
+    int m = 0;
+    for (int i = 0; i < count; ++i)
+      if (elem[i] == size) {
+        a.dst[m] = dst[i];
+        a.src[m] = src[i];
+        ++m;
+      }
+    if (!m) continue;
+    if (!wrap_regions(h->t, job, size, &a))
+      return fail(SODA_HIP_ERR_INVALID,
+                  "periodic: 2^31 rows or more; nothing was launched");
+    if (!a.total) continue;          // no ghost cells: nothing to fill
+    hipFunction_t fn = h->fn[log2_elem(size)];
+    if (!fn) return fail(SODA_HIP_ERR_INVALID, "periodic: no wrap kernel");
+    int64_t blocks = (int64_t)((a.total + kWrapBlock - 1) / kWrapBlock);
+    if (blocks > kWrapMaxBlocks) blocks = kWrapMaxBlocks;
+    size_t bytes = sizeof a;
+    void* extra[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &a,
+                     HIP_LAUNCH_PARAM_BUFFER_SIZE, &bytes,
+                     HIP_LAUNCH_PARAM_END};
+    HIP_TRY(hipModuleLaunchKernel(fn, (unsigned)blocks, (unsigned)m, 1,
+                                  kWrapBlock, 1, 1, 0, stream, nullptr,
+                                  extra));
+  }
+  return SODA_HIP_OK;
+}
+
+bool can_iterate(const soda_hip_plan_t& plan, bool not_iterable) {
+  if (not_iterable || plan.num_inputs != plan.num_outputs) return false;
+  for (int i = 0; i < plan.num_inputs; ++i)
+    if (plan.elem_size[i] != plan.elem_size[plan.num_inputs + i]) return false;
+  return true;
+}
+
+int check_iterate(const soda_hip_plan_t& plan, bool not_iterable,
+                  int32_t iterate, const char* who) {
+  if (iterate < 1)
+    return fail(SODA_HIP_ERR_INVALID,
+                std::string(who) + ": cannot iterate < 1 times; nothing was "
+                                   "launched");
+  if (iterate > 1 && !can_iterate(plan, not_iterable))
+    return fail(SODA_HIP_ERR_INVALID,
+                std::string(who) + ": the program cannot iterate (it needs as "
+                                   "many outputs as inputs, of the same "
+                                   "types) and iterate > 1; nothing was "
+                                   "launched");
+  return SODA_HIP_OK;
+}
+
+// The device entry contract (include/soda_hip.h, soda_hip_run_device) on the
+// caller's arrays, each the dense array of `extent`: no output shares a byte
+// with an input, a param array or another output; inputs and outputs are
+// aligned to min(16, vec x cell size) bytes.
+int check_contract(const soda_hip_plan_t& plan, void* const* outputs,
+                   const void* const* inputs, const int32_t* extent,
+                   const char* who_) {
+  const std::string who(who_);
+  const int nin = plan.num_inputs, nout = plan.num_outputs;
+  const int prm0 = nin + nout + plan.num_locals;
+  for (int i = 0; i < nin + plan.num_params; ++i)
+    if (!inputs[i]) return fail(SODA_HIP_ERR_INVALID, who + ": NULL input");
+  for (int o = 0; o < nout; ++o)
+    if (!outputs[o]) return fail(SODA_HIP_ERR_INVALID, who + ": NULL output");
+  const uint64_t cells = (uint64_t)cells_of(extent, plan.dim);
+  auto overlap = [](const void* a, uint64_t na, const void* b, uint64_t nb) {
+    const uintptr_t a0 = reinterpret_cast<uintptr_t>(a);
+    const uintptr_t b0 = reinterpret_cast<uintptr_t>(b);
+    return a0 < b0 + nb && b0 < a0 + na;
+  };
+  for (int o = 0; o < nout; ++o) {
+    const uint64_t no = cells * plan.elem_size[nin + o];
+    for (int i = 0; i < nin; ++i)
+      if (overlap(outputs[o], no, inputs[i], cells * plan.elem_size[i]))
+        return fail(SODA_HIP_ERR_INVALID,
+                    who + ": an output overlaps an input; nothing was "
+                          "launched");
+    for (int k = 0; k < plan.num_params; ++k)
+      if (overlap(outputs[o], no, inputs[nin + k],
+                  (uint64_t)plan.param_elems[k] * plan.elem_size[prm0 + k]))
+        return fail(SODA_HIP_ERR_INVALID,
+                    who + ": an output overlaps a param array; nothing was "
+                          "launched");
+    for (int q = 0; q < o; ++q)
+      if (overlap(outputs[o], no, outputs[q],
+                  cells * plan.elem_size[nin + q]))
+        return fail(SODA_HIP_ERR_INVALID,
+                    who + ": two outputs overlap; nothing was launched");
+  }
+  const int32_t vec = plan_vec(plan);
+  for (int t = 0; t < nin + nout; ++t) {
+    const void* ptr = t < nin ? inputs[t] : outputs[t - nin];
+    int64_t align = (int64_t)vec * plan.elem_size[t];
+    if (align > 16) align = 16;
+    if (reinterpret_cast<uintptr_t>(ptr) % (uintptr_t)align) {
+      char buf[200];
+      snprintf(buf, sizeof buf,
+               ": %s %d at %p is not aligned to %d bytes; nothing was "
+               "launched", t < nin ? "input" : "output",
+               t < nin ? t : t - nin, ptr, (int)align);
+      return fail(SODA_HIP_ERR_INVALID, who + buf);
+    }
+  }
+  return SODA_HIP_OK;
+}
+
+// The chunks of a run on padded arrays: `inputs` wrapped in, `outputs` wrapped
+// out, the chunks alternating between `outputs` and the handle's `pong` so
+// that the last one lands in `outputs`.
+int run_chunks(soda_hip_periodic* h, void* const* outputs,
+               const void* const* inputs, int32_t iterate, void* stream) {
+  soda_hip_program* p = h->prog;
+  const soda_hip_plan_t& plan = p->plan;
+  const int nin = plan.num_inputs, nout = plan.num_outputs;
+  const int chunks = (iterate + h->k - 1) / h->k;
+  std::vector<const void*> src(inputs, inputs + nin + plan.num_params);
+  std::vector<void*> dst(nout);
+  std::vector<int32_t> elem(nout);
+  for (int o = 0; o < nout; ++o) elem[o] = plan.elem_size[nin + o];
+  int32_t left = iterate;
+  for (int c = 0; c < chunks; ++c) {
+    const int32_t n = left < h->k ? left : h->k;
+    const bool to_out = ((chunks - 1 - c) % 2) == 0;
+    for (int o = 0; o < nout; ++o)
+      dst[o] = to_out ? outputs[o] : h->pong[o].ptr;
+    if (int rc = run_core(p, dst.data(), src.data(), h->t.p, nullptr, nullptr,
+                          n, stream, -1, nullptr))
+      return rc;
+    if (int rc = wrap_launch(h, kFill, dst.data(), dst.data(), elem.data(),
+                             nout, static_cast<hipStream_t>(stream)))
+      return rc;
+    left -= n;
+    if (c + 1 < chunks)
+      for (int i = 0; i < nin; ++i) src[i] = dst[i];
+  }
+  return SODA_HIP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int soda_hip_periodic_plan(const soda_hip_plan_t* plan,
+                           const soda_hip_periodic_desc_t* desc,
+                           int32_t iterate, soda_hip_periodic_info_t* info,
+                           int32_t capacity, int32_t* chunks, int32_t* count) {
+  if (!plan || !desc)
+    return fail(SODA_HIP_ERR_INVALID, "periodic_plan: NULL argument");
+  if (plan->abi_version != SODA_HIP_ABI_VERSION || plan->dim < 1 ||
+      plan->dim > SODA_HIP_MAX_DIM || plan->num_passes < 1 ||
+      plan->num_passes > SODA_HIP_MAX_PASSES)
+    return fail(SODA_HIP_ERR_INVALID, "periodic_plan: bad plan");
+  if (desc->preserve || (plan->residual.present && plan->residual.whole))
+    return fail(SODA_HIP_ERR_UNSUPPORTED,
+                "periodic: a program with `border: preserve` pins its border, "
+                "and a torus has none; nothing was launched");
+  if (plan->batched)
+    return fail(SODA_HIP_ERR_UNSUPPORTED,
+                "periodic: batched plans are not served on a torus; nothing "
+                "was launched");
+  const int dim = plan->dim;
+  int32_t k = desc->refill_every;
+  if (k < 0)
+    return fail(SODA_HIP_ERR_INVALID, "periodic: refill_every < 0");
+  if (k == 0)
+    for (int i = 0; i < plan->num_passes; ++i)
+      if (plan->passes[i].fused_iters > k) k = plan->passes[i].fused_iters;
+  if (k < 1) return fail(SODA_HIP_ERR_INVALID, "periodic: bad plan");
+  soda_hip_periodic_info_t out;
+  memset(&out, 0, sizeof out);
+  out.refill_every = k;
+  for (int d = 0; d < SODA_HIP_MAX_DIM; ++d) out.padded[d] = 1;
+  for (int d = 0; d < dim; ++d) {
+    if (desc->extent[d] < 1 || desc->ghost_lo[d] < 0 || desc->ghost_hi[d] < 0)
+      return fail(SODA_HIP_ERR_INVALID,
+                  "periodic: extent < 1 or a negative ghost width; nothing was "
+                  "launched");
+    out.ghost_lo[d] = desc->ghost_lo[d];
+    out.ghost_hi[d] = desc->ghost_hi[d];
+  }
+  if (plan->has_reach) {
+    const int ax = dim - 1;
+    if ((int64_t)out.ghost_lo[ax] < (int64_t)k * plan->reach_lo ||
+        (int64_t)out.ghost_hi[ax] < (int64_t)k * plan->reach_hi) {
+      char buf[256];
+      snprintf(buf, sizeof buf,
+               "periodic: ghosts of %d / %d cells along the last dimension, "
+               "%d iterations between refills reach %d / %d; nothing was "
+               "launched", out.ghost_lo[ax], out.ghost_hi[ax], k,
+               k * plan->reach_lo, k * plan->reach_hi);
+      return fail(SODA_HIP_ERR_INVALID, buf);
+    }
+  }
+  const int32_t vec = plan_vec(*plan);
+  int64_t cells = 1;
+  for (int d = 0; d < dim; ++d) {
+    int64_t p = (int64_t)out.ghost_lo[d] + desc->extent[d] + out.ghost_hi[d];
+    if (d == 0 && p % vec) {
+      out.ghost_hi[0] += (int32_t)(vec - p % vec);
+      p += vec - p % vec;
+    }
+    if (p > 0x7fffffffLL)
+      return fail(SODA_HIP_ERR_INVALID, "periodic: padded extent overflows");
+    out.padded[d] = (int32_t)p;
+    cells *= p;
+  }
+  if (iterate < 0) return fail(SODA_HIP_ERR_INVALID, "periodic: iterate < 0");
+  if (iterate > 1)
+    if (int rc = check_iterate(*plan, desc->not_iterable != 0, iterate,
+                               "periodic"))
+      return rc;
+  // what the kernels ask of the padded extent: row length, max_extent0, the
+  // 1 GiB window of a plane
+  if (int rc = soda_hip_plan_geometry(plan, out.padded, nullptr, nullptr))
+    return rc;
+  const int nin = plan->num_inputs, nout = plan->num_outputs;
+  for (int i = 0; i < nin; ++i)
+    out.scratch_bytes += cells * plan->elem_size[i];
+  for (int o = 0; o < nout; ++o)
+    out.scratch_bytes +=
+        cells * plan->elem_size[nin + o] *
+        (can_iterate(*plan, desc->not_iterable != 0) ? 2 : 1);
+  if (info) *info = out;
+  int32_t n = 0;
+  for (int32_t left = iterate; left > 0; left -= k, ++n)
+    if (chunks && n < capacity) chunks[n] = left < k ? left : k;
+  if (count) *count = n;
+  return SODA_HIP_OK;
+}
+
+int soda_hip_periodic_create(soda_hip_program_t* p,
+                             const soda_hip_periodic_desc_t* desc,
+                             const void* const* wrap_code,
+                             const size_t* wrap_code_size,
+                             soda_hip_periodic_t** handle) {
+  if (handle) *handle = nullptr;
+  if (!p || !desc || !wrap_code || !wrap_code_size || !handle)
+    return fail(SODA_HIP_ERR_INVALID, "periodic_create: NULL argument");
+  const soda_hip_plan_t& plan = p->plan;
+  if (p->bank_tensors)
+    return fail(SODA_HIP_ERR_UNSUPPORTED,
+                "periodic: programs on wire-format banks are not served on a "
+                "torus; nothing was launched");
+  soda_hip_periodic_info_t info;
+  if (int rc = soda_hip_periodic_plan(&plan, desc, 0, &info, 0, nullptr,
+                                      nullptr))
+    return rc;
+  const int nin = plan.num_inputs, nout = plan.num_outputs;
+  bool need[4] = {false, false, false, false};
+  for (int s = 0; s < nin + nout; ++s) {
+    const int l = log2_elem(plan.elem_size[s]);
+    if (l < 0)
+      return fail(SODA_HIP_ERR_UNSUPPORTED,
+                  "periodic: cells of 1, 2, 4 or 8 bytes only");
+    need[l] = true;
+  }
+  for (int l = 0; l < 4; ++l)
+    if (need[l] && (!wrap_code[l] || !wrap_code_size[l]))
+      return fail(SODA_HIP_ERR_INVALID,
+                  "periodic_create: the wrap module of a cell size of the "
+                  "program is missing");
+  HIP_TRY(hipSetDevice(p->device));
+  soda_hip_periodic* h = new (std::nothrow) soda_hip_periodic;
+  if (!h) return fail(SODA_HIP_ERR_NOMEM, "new periodic handle");
+  h->prog = p;
+  h->k = info.refill_every;
+  h->not_iterable = desc->not_iterable != 0;
+  const bool iterates = can_iterate(plan, h->not_iterable);
+  h->t.dim = plan.dim;
+  for (int d = 0; d < 4; ++d) {
+    h->t.n[d] = d < plan.dim ? desc->extent[d] : 1;
+    h->t.glo[d] = info.ghost_lo[d];
+    h->t.ghi[d] = info.ghost_hi[d];
+    h->t.p[d] = info.padded[d];
+  }
+  int rc = SODA_HIP_OK;
+  for (int l = 0; l < 4 && !rc; ++l) {
+    if (!need[l]) continue;
+    hipError_t e = hipModuleLoadData(&h->module[l], wrap_code[l]);
+    if (e != hipSuccess) {
+      rc = hip_fail(e, "periodic_create: hipModuleLoadData");
+      break;
+    }
+    char name[64];
+    snprintf(name, sizeof name, "soda_wrap_e%d_d%d", 1 << l, plan.dim);
+    e = hipModuleGetFunction(&h->fn[l], h->module[l], name);
+    if (e != hipSuccess)
+      rc = hip_fail(e, "periodic_create: hipModuleGetFunction (is this the "
+                       "wrap module of the cell size and dimension count?)");
+  }
+  const int64_t cells = cells_of(h->t.p, plan.dim);
+  h->pad_in.resize(nin);
+  h->pad_out.resize(nout);
+  h->pong.resize(iterates ? nout : 0);
+  for (int i = 0; i < nin && !rc; ++i)
+    rc = ensure(h->pad_in[i], (size_t)cells * plan.elem_size[i]);
+  for (int o = 0; o < nout && !rc; ++o) {
+    rc = ensure(h->pad_out[o], (size_t)cells * plan.elem_size[nin + o]);
+    if (!rc && iterates)
+      rc = ensure(h->pong[o], (size_t)cells * plan.elem_size[nin + o]);
+  }
+  if (rc) {
+    const std::string why = last_error_text();
+    soda_hip_periodic_destroy(h);
+    return fail(rc, why);
+  }
+  *handle = h;
+  return SODA_HIP_OK;
+}
+
+int soda_hip_periodic_destroy(soda_hip_periodic_t* h) {
+  if (!h) return SODA_HIP_OK;
+  (void)hipSetDevice(h->prog->device);
+  for (auto* v : {&h->pad_in, &h->pad_out, &h->pong})
+    for (auto& b : *v)
+      if (b.ptr) (void)hipFree(b.ptr);
+  for (auto& m : h->module)
+    if (m) (void)hipModuleUnload(m);
+  delete h;
+  return SODA_HIP_OK;
+}
+
+int soda_hip_periodic_info(soda_hip_periodic_t* h,
+                           soda_hip_periodic_info_t* info) {
+  if (!h || !info)
+    return fail(SODA_HIP_ERR_INVALID, "periodic_info: NULL argument");
+  memset(info, 0, sizeof *info);
+  info->refill_every = h->k;
+  for (int d = 0; d < 4; ++d) {
+    info->ghost_lo[d] = h->t.glo[d];
+    info->ghost_hi[d] = h->t.ghi[d];
+    info->padded[d] = h->t.p[d];
+  }
+  for (const auto* v : {&h->pad_in, &h->pad_out, &h->pong})
+    for (const auto& b : *v) info->scratch_bytes += (int64_t)b.bytes;
+  return SODA_HIP_OK;
+}
+
+int soda_hip_periodic_fill(soda_hip_periodic_t* h, void* const* arrays,
+                           int32_t count, void* stream) {
+  if (!h || !arrays)
+    return fail(SODA_HIP_ERR_INVALID, "periodic_fill: NULL argument");
+  const soda_hip_plan_t& plan = h->prog->plan;
+  if (count < 0 || count > plan.num_outputs)
+    return fail(SODA_HIP_ERR_INVALID,
+                "periodic_fill: one array per output at most; nothing was "
+                "launched");
+  int32_t elem[SODA_HIP_MAX_TENSORS];
+  for (int i = 0; i < count; ++i) {
+    elem[i] = plan.elem_size[plan.num_inputs + i];
+    if (!arrays[i] || reinterpret_cast<uintptr_t>(arrays[i]) % elem[i])
+      return fail(SODA_HIP_ERR_INVALID,
+                  "periodic_fill: an array is NULL or not aligned to its cell "
+                  "size; nothing was launched");
+  }
+  HIP_TRY(hipSetDevice(h->prog->device));
+  return wrap_launch(h, kFill, arrays,
+                     const_cast<const void* const*>(arrays), elem, count,
+                     static_cast<hipStream_t>(stream));
+}
+
+int soda_hip_periodic_run_padded(soda_hip_periodic_t* h, void* const* outputs,
+                                 const void* const* inputs, int32_t iterate,
+                                 void* stream) {
+  if (!h || !outputs || !inputs)
+    return fail(SODA_HIP_ERR_INVALID, "periodic_run_padded: NULL argument");
+  if (int rc = check_iterate(h->prog->plan, h->not_iterable, iterate,
+                             "periodic_run_padded"))
+    return rc;
+  if (int rc = check_contract(h->prog->plan, outputs, inputs, h->t.p,
+                              "periodic_run_padded"))
+    return rc;
+  return run_chunks(h, outputs, inputs, iterate, stream);
+}
+
+int soda_hip_periodic_run_device(soda_hip_periodic_t* h, void* const* outputs,
+                                 const void* const* inputs, int32_t iterate,
+                                 void* stream_) {
+  if (!h || !outputs || !inputs)
+    return fail(SODA_HIP_ERR_INVALID, "periodic_run_device: NULL argument");
+  soda_hip_program* p = h->prog;
+  const soda_hip_plan_t& plan = p->plan;
+  if (int rc = check_iterate(plan, h->not_iterable, iterate,
+                             "periodic_run_device"))
+    return rc;
+  const int nin = plan.num_inputs, nout = plan.num_outputs;
+  // the device entry contract on the caller's dense arrays of N
+  if (int rc = check_contract(plan, outputs, inputs, h->t.n,
+                              "periodic_run_device"))
+    return rc;
+  HIP_TRY(hipSetDevice(p->device));
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  // pad: every cell of the padded inputs, ghosts included
+  std::vector<void*> pin(nin), pout(nout);
+  std::vector<const void*> src(nin + plan.num_params);
+  std::vector<int32_t> ein(nin), eout(nout);
+  for (int i = 0; i < nin; ++i) {
+    pin[i] = h->pad_in[i].ptr;
+    src[i] = pin[i];
+    ein[i] = plan.elem_size[i];
+  }
+  for (int k = 0; k < plan.num_params; ++k) src[nin + k] = inputs[nin + k];
+  for (int o = 0; o < nout; ++o) {
+    pout[o] = h->pad_out[o].ptr;
+    eout[o] = plan.elem_size[nin + o];
+  }
+  if (int rc = wrap_launch(h, kPad, pin.data(), inputs, ein.data(), nin,
+                           stream))
+    return rc;
+  if (int rc = run_chunks(h, pout.data(), src.data(), iterate, stream_))
+    return rc;
+  return wrap_launch(h, kCrop, outputs,
+                     const_cast<const void* const*>(pout.data()), eout.data(),
+                     nout, stream);
+}
+
+}  // extern "C"

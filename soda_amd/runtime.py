@@ -236,6 +236,26 @@ class HostTensor(ctypes.Structure):
               ('min', ctypes.POINTER(ctypes.c_int32))]
 
 
+class PeriodicDesc(ctypes.Structure):
+  """Mirror of soda_hip_periodic_desc_t: a torus and its ghost frame."""
+  _fields_ = [('extent', ctypes.c_int32 * MAX_DIM),
+              ('refill_every', ctypes.c_int32),
+              ('ghost_lo', ctypes.c_int32 * MAX_DIM),
+              ('ghost_hi', ctypes.c_int32 * MAX_DIM),
+              ('preserve', ctypes.c_int32),
+              ('not_iterable', ctypes.c_int32)]
+
+
+class PeriodicInfo(ctypes.Structure):
+  """Mirror of soda_hip_periodic_info_t: what a periodic handle uses."""
+  _fields_ = [('refill_every', ctypes.c_int32),
+              ('ghost_lo', ctypes.c_int32 * MAX_DIM),
+              ('ghost_hi', ctypes.c_int32 * MAX_DIM),
+              ('padded', ctypes.c_int32 * MAX_DIM),
+              ('reserved', ctypes.c_int32),
+              ('scratch_bytes', ctypes.c_int64)]
+
+
 # every symbol include/soda_hip.h declares: name -> (restype, argtypes)
 _vp = ctypes.c_void_p
 _i32 = ctypes.c_int32
@@ -323,6 +343,24 @@ API = {
         _vp, _vp, _pvp, _pvp, _pi32, _i32, _i32, _i32, ctypes.c_double,
         ctypes.POINTER(NormsStruct), _pi32, _vp
     ]),
+    'soda_hip_wrap_host': (ctypes.c_int, [_vp, _i32, _i32, _pi32, _pi32,
+                                          _pi32]),
+    'soda_hip_periodic_plan': (ctypes.c_int, [
+        ctypes.POINTER(Plan), ctypes.POINTER(PeriodicDesc), _i32,
+        ctypes.POINTER(PeriodicInfo), _i32, _pi32, _pi32
+    ]),
+    'soda_hip_periodic_create': (ctypes.c_int, [
+        _vp, ctypes.POINTER(PeriodicDesc), _pvp,
+        ctypes.POINTER(ctypes.c_size_t), _pvp
+    ]),
+    'soda_hip_periodic_destroy': (ctypes.c_int, [_vp]),
+    'soda_hip_periodic_info': (ctypes.c_int, [_vp,
+                                              ctypes.POINTER(PeriodicInfo)]),
+    'soda_hip_periodic_fill': (ctypes.c_int, [_vp, _pvp, _i32, _vp]),
+    'soda_hip_periodic_run_padded': (ctypes.c_int, [_vp, _pvp, _pvp, _i32,
+                                                    _vp]),
+    'soda_hip_periodic_run_device': (ctypes.c_int, [_vp, _pvp, _pvp, _i32,
+                                                    _vp]),
     'soda_hip_run_device_window': (ctypes.c_int, [_vp, _pvp, _pvp, _pi32, _pi32,
                                                   _pi32, _i32, _vp]),
     'soda_hip_run_device_cone': (ctypes.c_int, [_vp, _pvp, _pvp, _pi32, _pi32,
@@ -459,7 +497,8 @@ def library() -> ctypes.CDLL:
                           (4, HostTensor), (5, StreamDesc), (6, SlabRun),
                           (7, GroupDesc), (8, SlabInfo), (9, GroupStats),
                           (10, LaunchInfo), (11, ResidualStruct),
-                          (12, ResBox), (14, NormsStruct)):
+                          (12, ResBox), (14, NormsStruct),
+                          (15, PeriodicDesc), (16, PeriodicInfo)):
       if lib.soda_hip_sizeof(which) != ctypes.sizeof(mirror):
         raise util.BackendError(
             'struct layout mismatch between libsoda_hip.so and runtime.py '
@@ -1233,6 +1272,221 @@ class Norms:
     return raw
 
 
+# -- periodic domains: a program on a torus ------------------
+def wrap_host(arr, ghost_lo: Sequence[int], ghost_hi: Sequence[int]):
+  """Refills the ghost frame of the padded numpy array `arr` IN PLACE from its
+  interior, every ghost cell taking the interior cell it mirrors on the torus
+  (soda_hip_wrap_host, plain C++; no GPU needed).  `ghost_lo` / `ghost_hi`:
+  ghost cells below / above the torus per dimension, dimension 0 (the fastest,
+  the LAST numpy axis) first.  Returns `arr`."""
+  import numpy as np
+  if not isinstance(arr, np.ndarray) or not arr.flags['C_CONTIGUOUS'] or \
+      not arr.flags['WRITEABLE']:
+    raise util.InputError('wrap_host: a writable C-contiguous numpy array')
+  dim = arr.ndim
+  if len(ghost_lo) != dim or len(ghost_hi) != dim:
+    raise util.InputError('wrap_host: %d ghost widths per side' % dim)
+  padded = arr.shape[::-1]
+  extent = [p - l - h for p, l, h in zip(padded, ghost_lo, ghost_hi)]
+  if arr.dtype.itemsize not in (1, 2, 4, 8) or not 1 <= dim <= MAX_DIM or \
+      min(extent) < 1 or min(ghost_lo) < 0 or min(ghost_hi) < 0:
+    raise util.InputError(
+        'wrap_host: cells of 1, 2, 4 or 8 bytes, 1 to %d dimensions, ghosts '
+        '>= 0 that leave a torus of at least one cell' % MAX_DIM)
+  check(library().soda_hip_wrap_host(
+      arr.ctypes.data, arr.dtype.itemsize, dim, (ctypes.c_int32 * dim)(*extent),
+      (ctypes.c_int32 * dim)(*ghost_lo), (ctypes.c_int32 * dim)(*ghost_hi)),
+        'wrap_host')
+  return arr
+
+
+def periodic_ghosts(stencil: core.Stencil, refill_every: int):
+  """(ghost_lo, ghost_hi) a frame must have to carry `refill_every` iterations
+  of `stencil`: the most `Stencil.window_bounds(refill_every)` reaches below /
+  above over ALL outputs (one-sided programs get one-sided ghosts, coupled
+  outputs the widest), and along the last dimension at least `refill_every`
+  times the per-iteration reach the plan carries -- the library refuses
+  less."""
+  boxes = stencil.window_bounds(refill_every)
+  dim = stencil.dim
+  lo = [max(0, max(-boxes[o][0][d] for o in stencil.output_names))
+        for d in range(dim)]
+  hi = [max(0, max(boxes[o][1][d] for o in stencil.output_names))
+        for d in range(dim)]
+  rl, rh = stencil.reach_along(dim - 1)
+  lo[-1] = max(lo[-1], refill_every * rl)
+  hi[-1] = max(hi[-1], refill_every * rh)
+  return lo, hi
+
+
+def _periodic_desc(dim: int, extent: Sequence[int], refill_every: int,
+                   ghost_lo: Sequence[int], ghost_hi: Sequence[int],
+                   preserve: bool, not_iterable: bool = False
+                   ) -> PeriodicDesc:
+  if len(extent) != dim or len(ghost_lo) != dim or len(ghost_hi) != dim:
+    raise util.InputError('periodic: extent and ghosts must have %d entries' %
+                          dim)
+  desc = PeriodicDesc()
+  for d in range(dim):
+    desc.extent[d] = extent[d]
+    desc.ghost_lo[d], desc.ghost_hi[d] = ghost_lo[d], ghost_hi[d]
+  desc.refill_every = refill_every
+  desc.preserve = 1 if preserve else 0
+  desc.not_iterable = 1 if not_iterable else 0
+  return desc
+
+
+def _periodic_info(raw: PeriodicInfo, dim: int) -> dict:
+  return {'refill_every': raw.refill_every,
+          'ghost_lo': tuple(raw.ghost_lo[:dim]),
+          'ghost_hi': tuple(raw.ghost_hi[:dim]),
+          'padded': tuple(raw.padded[:dim]),
+          'scratch_bytes': int(raw.scratch_bytes)}
+
+
+def periodic_plan(plan: Plan, extent: Sequence[int], refill_every: int,
+                  ghost_lo: Sequence[int], ghost_hi: Sequence[int],
+                  iterate: int = 0, preserve: bool = False,
+                  not_iterable: bool = False):
+  """(info, chunks) a periodic handle over `plan` would use for a torus of
+  `extent` (soda_hip_periodic_plan; no GPU needed): info as Periodic.info(),
+  chunks the iterations of every chunk of a run of `iterate`.  Refuses what
+  the handle refuses (BackendError)."""
+  desc = _periodic_desc(plan.dim, extent, refill_every, ghost_lo, ghost_hi,
+                        preserve, not_iterable)
+  raw = PeriodicInfo()
+  cap = max(1, iterate)
+  chunks = (ctypes.c_int32 * cap)()
+  n = ctypes.c_int32()
+  check(library().soda_hip_periodic_plan(ctypes.byref(plan),
+                                         ctypes.byref(desc), iterate,
+                                         ctypes.byref(raw), cap, chunks,
+                                         ctypes.byref(n)), 'periodic_plan')
+  return _periodic_info(raw, plan.dim), list(chunks[:n.value])
+
+
+def wrap_resources(elem: int, dim: int):
+  """(code object, kernel_resources of it) of the wrap module of a cell size
+  and dimension count: JIT-built like every module, cached like them; needs
+  no GPU."""
+  from soda_amd.codegen.hip import wrap as _wrap
+  code = compile_source(_wrap.source(elem, dim),
+                        'wrap_e%d_%dd.hip' % (elem, dim))
+  return code, kernel_resources(code)
+
+
+class Periodic:
+  """A program on a torus of ONE extent (soda_hip_periodic_create): the state
+  lives in padded arrays whose ghost frame carries `refill_every` iterations
+  of the program's ordinary kernels and is refilled on the GPU in between.
+  Made by `Program.periodic`; close it before its program."""
+
+  def __init__(self, prog: 'Program', extent: Sequence[int],
+               refill_every: Optional[int] = None,
+               ghosts: Optional[Sequence[Sequence[int]]] = None):
+    """`refill_every`: iterations between two refills (default: the deepest
+    fusion depth of the program, so that a chunk is one launch).  `ghosts` =
+    (lo, hi): the frame, for callers that size it themselves (default:
+    periodic_ghosts)."""
+    st = prog.stencil
+    self.prog, self.extent = prog, tuple(int(e) for e in extent)
+    prog._check_extent(self.extent)
+    k = int(refill_every or 0)
+    if k < 0:
+      raise util.InputError('periodic: refill_every < 0')
+    if not k:
+      k = max(p.fused_iters for p in prog.module.passes)
+    lo, hi = ghosts if ghosts is not None else periodic_ghosts(st, k)
+    desc = _periodic_desc(
+        st.dim, self.extent, k, lo, hi, st.preserve_border,
+        not_iterable=list(st.input_types) != list(st.output_types))
+    codes = (ctypes.c_void_p * 4)()
+    sizes = (ctypes.c_size_t * 4)()
+    self._codes = []
+    if not st.preserve_border:      # (refused below: nothing to build for)
+      sizes_needed = {t.size_in_bytes
+                      for t in list(st.input_types) + list(st.output_types)}
+      for elem in sorted(sizes_needed & {1, 2, 4, 8}):
+        code, _ = wrap_resources(elem, st.dim)
+        buf = ctypes.create_string_buffer(code, len(code))
+        self._codes.append(buf)
+        i = elem.bit_length() - 1
+        codes[i] = ctypes.cast(buf, ctypes.c_void_p)
+        sizes[i] = len(code)
+    self._lib = library()
+    self._handle = ctypes.c_void_p()
+    check(self._lib.soda_hip_periodic_create(prog._handle, ctypes.byref(desc),
+                                             codes, sizes,
+                                             ctypes.byref(self._handle)),
+          '`%s` on a torus of %s' % (st.app_name, 'x'.join(
+              map(str, self.extent))))
+    prog._periodic.append(self)
+
+  def close(self) -> None:
+    if getattr(self, '_handle', None):
+      self._lib.soda_hip_periodic_destroy(self._handle)
+      self._handle = None
+      if self in self.prog._periodic:
+        self.prog._periodic.remove(self)
+
+  def __del__(self):
+    try:
+      self.close()
+    except Exception:  # interpreter shutdown
+      pass
+
+  def __enter__(self):
+    return self
+
+  def __exit__(self, *exc):
+    self.close()
+
+  def info(self) -> dict:
+    """{'refill_every', 'ghost_lo', 'ghost_hi', 'padded', 'scratch_bytes'}:
+    what the library chose (ghost_hi[0] rounded up until padded[0] is a
+    multiple of the program's vector width) and holds."""
+    raw = PeriodicInfo()
+    check(self._lib.soda_hip_periodic_info(self._handle, ctypes.byref(raw)),
+          'periodic: info')
+    return _periodic_info(raw, self.prog.stencil.dim)
+
+  def fill(self, arrays: Sequence[int], stream: int = 0) -> None:
+    """Refills the ghost frame of padded device arrays in place (array i: the
+    cells of output i); asynchronous on `stream`."""
+    arr = (ctypes.c_void_p * max(1, len(arrays)))(*arrays)
+    check(self._lib.soda_hip_periodic_fill(self._handle, arr, len(arrays),
+                                           ctypes.c_void_p(stream)),
+          'periodic: fill')
+
+  def _run(self, fn, what, outputs, inputs, iterate, stream):
+    st = self.prog.stencil
+    iterate = st.iterate if iterate is None else iterate
+    if len(outputs) != len(st.output_names) or \
+        len(inputs) != len(st.input_names) + len(st.param_stmts):
+      raise util.InputError('%s: %d outputs, %d inputs and param arrays' % (
+          what, len(st.output_names),
+          len(st.input_names) + len(st.param_stmts)))
+    outs = (ctypes.c_void_p * len(outputs))(*outputs)
+    ins = (ctypes.c_void_p * len(inputs))(*inputs)
+    check(fn(self._handle, outs, ins, iterate, ctypes.c_void_p(stream)),
+          '%s of `%s`' % (what, st.app_name))
+
+  def run_padded(self, outputs: Sequence[int], inputs: Sequence[int],
+                 iterate: Optional[int] = None, stream: int = 0) -> None:
+    """`iterate` iterations on PADDED device arrays of info()['padded']: the
+    inputs (then the param arrays) arrive wrapped, the outputs leave wrapped,
+    the inputs are never written (soda_hip_periodic_run_padded)."""
+    self._run(self._lib.soda_hip_periodic_run_padded, 'periodic run_padded',
+              outputs, inputs, iterate, stream)
+
+  def run_device(self, outputs: Sequence[int], inputs: Sequence[int],
+                 iterate: Optional[int] = None, stream: int = 0) -> None:
+    """The same on DENSE device arrays of the torus's extent: padded into the
+    handle's scratch, run, cropped (soda_hip_periodic_run_device)."""
+    self._run(self._lib.soda_hip_periodic_run_device, 'periodic run_device',
+              outputs, inputs, iterate, stream)
+
+
 class Program:
   """A SODA program JIT-built for gfx950 and loaded on one GPU."""
 
@@ -1248,6 +1502,7 @@ class Program:
     module (diagnostic builds only: tests/test_compiler_pins.py switches a
     compiler-fault workaround of soda_rt.h off with a #define)."""
     self.stencil = stencil
+    self._periodic = []         # Periodic handles over this program
     self.opts = resolve_options(stencil, opts, extent)   # never the caller's
     self.device = device
     self.module = lower.lower(stencil, self.opts)
@@ -1328,6 +1583,8 @@ class Program:
 
   # -- lifecycle -----------------------------------------------------------
   def close(self) -> None:
+    for per in list(getattr(self, '_periodic', ())):
+      per.close()               # a handle goes before its program
     if getattr(self, '_norms', None) is not None:
       self._norms.close()
       self._norms = None
@@ -1782,6 +2039,74 @@ class Program:
     check(
         self._lib.soda_hip_run_host_box(self._handle, ins, outs, iterate, vlo,
                                         vhi), 'running `%s`' % st.app_name)
+    return result
+
+  # -- periodic domains ------------------------------------------------------
+  def periodic(self, extent: Sequence[int],
+               refill_every: Optional[int] = None,
+               ghosts: Optional[Sequence[Sequence[int]]] = None) -> Periodic:
+    """This program on a torus of `extent` (runtime.Periodic).
+    The handle is closed with the program at the latest."""
+    return Periodic(self, extent, refill_every, ghosts)
+
+  def run_periodic(self, inputs: Dict[str, 'numpy.ndarray'],
+                   iterate: Optional[int] = None,
+                   refill_every: Optional[int] = None
+                   ) -> Dict[str, 'numpy.ndarray']:
+    """`run` on a torus: numpy arrays of the domain in (shape = extent
+    reversed; params as in `run`), the outputs out, EVERY cell of them
+    defined.  A plain allocate / copy in / Periodic.run_device / copy out."""
+    import numpy as np
+    st = self.stencil
+    lib = self._lib
+    iterate = st.iterate if iterate is None else iterate
+    first = np.asarray(inputs[st.input_names[0]])
+    extent = tuple(first.shape[::-1])
+    self._check_extent(extent)
+    host_in = []
+    for n, t in zip(st.input_names, st.input_types):
+      arr = np.ascontiguousarray(inputs[n])
+      if arr.dtype != np.dtype(t.np_name):
+        raise util.InputError('expected dtype %s, got %s' % (t.np_name,
+                                                             arr.dtype))
+      if arr.shape != first.shape:
+        raise util.InputError('all tensors must share one shape')
+      host_in.append(arr)
+    for pstmt in st.param_stmts:        # param arrays follow, C order
+      arr = np.ascontiguousarray(inputs[pstmt.name]).reshape(-1)
+      if arr.dtype != np.dtype(pstmt.haoda_type.np_name) or \
+          arr.size != st.param_elems(pstmt):
+        raise util.InputError('param %s must be %d x %s' % (
+            pstmt.name, st.param_elems(pstmt), pstmt.haoda_type.np_name))
+      host_in.append(arr)
+    result = {n: np.empty(first.shape, dtype=np.dtype(t.np_name))
+              for n, t in zip(st.output_names, st.output_types)}
+    dev_in, dev_out = [], []
+    with self.periodic(extent, refill_every) as per:
+      try:
+        for arr in host_in:
+          ptr = ctypes.c_void_p()
+          check(lib.soda_hip_malloc(self.device, arr.nbytes,
+                                    ctypes.byref(ptr)),
+                'run_periodic: allocating an input')
+          dev_in.append(ptr)
+          check(lib.soda_hip_memcpy_h2d(ptr, arr.ctypes.data, arr.nbytes,
+                                        None), 'run_periodic: copy in')
+        for arr in result.values():
+          ptr = ctypes.c_void_p()
+          check(lib.soda_hip_malloc(self.device, arr.nbytes,
+                                    ctypes.byref(ptr)),
+                'run_periodic: allocating an output')
+          dev_out.append(ptr)
+        per.run_device([p.value for p in dev_out], [p.value for p in dev_in],
+                       iterate)
+        for arr, ptr in zip(result.values(), dev_out):
+          check(lib.soda_hip_memcpy_d2h(arr.ctypes.data, ptr, arr.nbytes,
+                                        None), 'run_periodic: copy out')
+      finally:
+        lib.soda_hip_stream_synchronize(None)
+        for ptr in dev_in + dev_out:
+          lib.soda_hip_free(self.device, ptr)
     return result
 
   def run_batch(self, inputs: Dict[str, 'numpy.ndarray'],
