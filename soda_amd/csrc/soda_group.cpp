@@ -180,7 +180,7 @@ typedef int (*PassTimes)(void* ctx, const soda_hip_plan_t& plan,
 int model_times(void* ctx, const soda_hip_plan_t& plan, const int32_t* ext,
                 std::vector<double>* ns) {
   auto* cache = static_cast<std::map<ExtentKey, ExtentPlan>*>(ctx);
-  const ExtentPlan* ep = nullptr;
+  ExtentPlan* ep = nullptr;
   if (int rc = extent_plan(plan, cache, ext, &ep)) return rc;
   *ns = ep->model_ns;
   return SODA_HIP_OK;
@@ -407,10 +407,12 @@ int enqueue_interval(soda_hip_group* g, int s, int64_t j, int32_t iters,
   for (auto& prm : me.params) ins.push_back(prm.ptr);
   std::vector<void*> outs = g->outputs_of(me, j);
   const ResidualRun res = {me.res.ptr, box_iterate};
-  if (int rc = run_core(me.prog, outs.data(), ins.data(), me.extent, me.origin,
-                        g->desc.extent, iters, me.main, -1, &run, 1,
-                        box_iterate > 0 ? &res : nullptr))
-    return rc;
+  RunRequest rq = {outs.data(), ins.data(), me.extent, iters, me.main};
+  rq.origin = me.origin;
+  rq.global_extent = g->desc.extent;
+  rq.slab = &run;
+  if (box_iterate > 0) rq.residual = &res;
+  if (int rc = run_core(me.prog, rq)) return rc;
   if (box_iterate > 0) {
     me.res_mode = me.prog->last_res_mode;
     me.res_fused = me.prog->last_res_fused;
@@ -975,10 +977,7 @@ int soda_hip_group_run_until(soda_hip_group_t* g, int32_t max_iterate,
     if (int rc = group_run(g, n, true)) return rc;
     if (int rc = soda_hip_group_residual(g, &host, nullptr)) return rc;
     done += n;
-    double max_float;
-    memcpy(&max_float, &host.max_float_bits, sizeof max_float);
-    if (host.unordered == 0 && max_float <= tol && host.max_int <= int_tol)
-      break;
+    if (residual_converged(host, tol, int_tol)) break;
   }
   if (result_host) *result_host = host;
   if (iterations_done) *iterations_done = done;

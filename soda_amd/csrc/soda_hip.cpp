@@ -387,8 +387,7 @@ int soda_hip_program_destroy(soda_hip_program_t* p) {
                   &p->host_in, &p->host_out, &p->host_prm})
     for (auto& b : *v)
       if (b.ptr) (void)hipFree(b.ptr);
-  if (p->until_res.ptr) (void)hipFree(p->until_res.ptr);
-  if (p->until_norms.ptr) (void)hipFree(p->until_norms.ptr);
+  if (p->until_struct.ptr) (void)hipFree(p->until_struct.ptr);
   for (int i = 0; i < 2; ++i) {
     if (p->ev_pre[i]) (void)hipEventDestroy(p->ev_pre[i]);
     if (p->ev_bnd[i]) (void)hipEventDestroy(p->ev_bnd[i]);
@@ -1046,7 +1045,7 @@ int residual_order(const soda_hip_plan_t& plan,
 
 int extent_plan(const soda_hip_plan_t& plan,
                 std::map<ExtentKey, ExtentPlan>* cache, const int32_t* ext,
-                const ExtentPlan** out, int32_t batch) {
+                ExtentPlan** out, int32_t batch) {
   ExtentKey key;
   for (int d = 0; d < SODA_HIP_MAX_DIM; ++d) key[d] = ext[d];
   auto it = cache->find(key);
@@ -1171,7 +1170,7 @@ int plan_launches(const soda_hip_plan_t& plan,
         int32_t sub[SODA_HIP_MAX_DIM];
         for (int d = 0; d < SODA_HIP_MAX_DIM; ++d) sub[d] = ext[d];
         sub[ax] = hi - lo;
-        const ExtentPlan* use = nullptr;
+        ExtentPlan* use = nullptr;
         if (int rc = extent_plan(plan, cache, sub, &use)) return rc;
         const int64_t lb = use->geo[k0].tile[ax];
         const int64_t nchunk = (hi - lo + lb - 1) / lb;
@@ -1286,188 +1285,189 @@ static bool scratch_grows(const soda_hip_program* p, bool need_locals,
   return false;
 }
 
-int run_core(soda_hip_program_t* p, void* const* outputs,
-             const void* const* inputs, const int32_t* extent,
-             const int32_t* origin, const int32_t* global_extent,
-             int32_t iterate, void* stream_, int force_pass,
-             const SlabRun* slab, int32_t batch, const ResidualRun* res) {
-  if (!p || !outputs || !inputs || !extent)
-    return fail(SODA_HIP_ERR_INVALID, "run_device: NULL argument");
-  const soda_hip_plan_t& plan = p->plan;
-  if (res && (batch != 1 || force_pass >= 0 || !plan.residual.present ||
-              !res->dev || res->box_iterate < iterate))
-    return fail(SODA_HIP_ERR_INVALID, "run_core: bad residual run");
-  if (batch < 1 || (batch > 1 && (!plan.batched || slab)))
-    return fail(SODA_HIP_ERR_INVALID, "run_core: bad batch");
-  // plans, schedules and measured times of this batch size
-  std::map<ExtentKey, ExtentPlan>& extents = extents_of(p, batch);
-  std::map<ExtentKey, std::vector<double>>& measured = measured_of(p, batch);
-  if (iterate < 1) return fail(SODA_HIP_ERR_INVALID, "cannot iterate < 1 times");
-  if (iterate > 1 && plan.num_inputs != plan.num_outputs)
-    return fail(SODA_HIP_ERR_INVALID,
-                "number of input tensors must be the same as output if "
-                "iterate > 1 times");
-  hipStream_t stream = static_cast<hipStream_t>(stream_);
-  HIP_TRY(hipSetDevice(p->device));
-  const Cone* cone = slab ? &slab->cone : nullptr;
+// ---- a run, step by step (run_core below) -----------------------------------
 
-  soda_hip_kargs_t base;
-  memset(&base, 0, sizeof base);
-  int64_t cells = 1;
+// The kernel arguments that hold for every launch of the run -- extent,
+// strides, the window's place in the global grid -- and the cells of one grid.
+static int run_geometry(const soda_hip_plan_t& plan, const RunRequest& rq,
+                        soda_hip_kargs_t* base, int64_t* cells) {
+  memset(base, 0, sizeof *base);
+  *cells = 1;
   for (int d = 0; d < SODA_HIP_MAX_DIM; ++d) {
-    int32_t e = d < plan.dim ? extent[d] : 1;
+    int32_t e = d < plan.dim ? rq.extent[d] : 1;
     if (e < 1) return fail(SODA_HIP_ERR_INVALID, "run_device: extent < 1");
-    base.extent[d] = e;
-    base.stride[d] = cells;
-    cells *= e;
-    base.origin[d] = (origin && d < plan.dim) ? origin[d] : 0;
-    base.gextent[d] = (global_extent && d < plan.dim) ? global_extent[d] : e;
-    if (base.origin[d] < 0 || base.origin[d] + e > base.gextent[d])
+    base->extent[d] = e;
+    base->stride[d] = *cells;
+    *cells *= e;
+    base->origin[d] = (rq.origin && d < plan.dim) ? rq.origin[d] : 0;
+    base->gextent[d] =
+        (rq.global_extent && d < plan.dim) ? rq.global_extent[d] : e;
+    if (base->origin[d] < 0 || base->origin[d] + e > base->gextent[d])
       return fail(SODA_HIP_ERR_INVALID,
                   "run_device: the window does not lie in the global grid");
   }
   for (int i = 0; i < plan.num_inputs + plan.num_params; ++i)
-    if (!inputs[i]) return fail(SODA_HIP_ERR_INVALID, "run_device: NULL input");
+    if (!rq.inputs[i])
+      return fail(SODA_HIP_ERR_INVALID, "run_device: NULL input");
   for (int i = 0; i < plan.num_outputs; ++i)
-    if (!outputs[i]) return fail(SODA_HIP_ERR_INVALID, "run_device: NULL output");
-  // The caller's addresses: no output may share a byte with an input, a
-  // param array or another output (passes read their inputs while they write
-  // their outputs, and ping-pong through the outputs), each tensor taken as
-  // the dense array of `extent` -- `batch` of them -- that the kernels address.
-  if (!p->bank_tensors) {
-    const int out0 = plan.num_inputs;
-    const int prm0 = out0 + plan.num_outputs + plan.num_locals;
-    auto bytes_of = [&](int slot) {
-      return (uint64_t)cells * (uint64_t)batch * (uint64_t)plan.elem_size[slot];
-    };
-    auto overlap = [](const void* a, uint64_t na, const void* b, uint64_t nb) {
-      const uintptr_t a0 = reinterpret_cast<uintptr_t>(a);
-      const uintptr_t b0 = reinterpret_cast<uintptr_t>(b);
-      return a0 < b0 + nb && b0 < a0 + na;
-    };
-    for (int o = 0; o < plan.num_outputs; ++o) {
-      for (int i = 0; i < plan.num_inputs; ++i)
-        if (overlap(outputs[o], bytes_of(out0 + o), inputs[i], bytes_of(i)))
-          return fail(SODA_HIP_ERR_INVALID,
-                      std::string("run_device: an output ") +
-                          (outputs[o] == inputs[i] ? "aliases" : "overlaps") +
-                          " an input (in-place runs are not supported: inputs "
-                          "are read while outputs are written); nothing was "
-                          "launched");
-      for (int k = 0; k < plan.num_params; ++k)
-        if (overlap(outputs[o], bytes_of(out0 + o),
-                    inputs[plan.num_inputs + k],
-                    (uint64_t)plan.param_elems[k] * plan.elem_size[prm0 + k]))
-          return fail(SODA_HIP_ERR_INVALID,
-                      "run_device: an output overlaps a param array; nothing "
-                      "was launched");
-      for (int q = 0; q < o; ++q)
-        if (overlap(outputs[o], bytes_of(out0 + o), outputs[q],
-                    bytes_of(out0 + q)))
-          return fail(SODA_HIP_ERR_INVALID,
-                      "run_device: two outputs overlap; nothing was launched");
-    }
-  }
+    if (!rq.outputs[i])
+      return fail(SODA_HIP_ERR_INVALID, "run_device: NULL output");
+  return SODA_HIP_OK;
+}
 
-  // schedule: the multiset of passes that adds up to `iterate` at least total
-  // cost (100 iterations with passes of 12 / 8 / 4 / 1: 7 x 12 + 2 x 8 beats
-  // 8 x 12 + 4); without costs, as many of the deepest kind as fit, then the
-  // next...  Remembered per (extent, iterate).
-  const ExtentPlan* ep = nullptr;
-  if (int rc = extent_plan(plan, &extents, base.extent, &ep, batch)) return rc;
-  // ... and their alignment (behind the geometry, which has made sure that
-  // the row length is a multiple of every kernel's cells per lane: a row, a
-  // plane, a slab window or a band then starts on a fragment boundary iff the
-  // array does).  A kernel moves a tensor in fragments of `vec` cells, with
-  // one instruction of up to 16 bytes each -- marching and tile3d kernels
-  // through buffer resources (soda_rt.h soda_buf_load_frag /
-  // soda_buf_store_frag), direct and ldswin kernels through vector pointers
-  // (soda_load_frag / soda_store_frag; ldswin's quads are four 4-byte cells)
-  // -- so every tensor must be aligned to min(16, vec x its cell size) for
-  // the widest `vec` of the plan; param arrays are read cell by cell.
-  if (!p->bank_tensors) {
-    int32_t vec = 1;
-    for (int k = 0; k < plan.num_kernels; ++k)
-      if (plan.kernels[k].vec > vec) vec = plan.kernels[k].vec;
-    const int out0 = plan.num_inputs;
-    const int prm0 = out0 + plan.num_outputs + plan.num_locals;
-    char buf[256];
-    for (int t = 0; t < plan.num_inputs + plan.num_outputs + plan.num_params;
-         ++t) {
-      const bool prm = t >= plan.num_inputs + plan.num_outputs;
-      const int k = t - plan.num_inputs - plan.num_outputs;
-      const void* ptr = prm ? inputs[plan.num_inputs + k]
-                            : t < out0 ? inputs[t] : outputs[t - out0];
-      const int64_t elem = plan.elem_size[prm ? prm0 + k : t];
-      int64_t align = prm ? elem : (int64_t)vec * elem;
-      if (align > 16) align = 16;
-      if (align > 1 && reinterpret_cast<uintptr_t>(ptr) % (uintptr_t)align) {
-        snprintf(buf, sizeof buf,
-                 "run_device: %s %d at %p is not aligned to %d bytes (%d cells "
-                 "per lane x %d-byte cells, at most 16; params: one cell); "
-                 "nothing was launched",
-                 prm ? "param array" : t < out0 ? "input" : "output",
-                 prm ? k : t < out0 ? t : t - out0, ptr, (int)align,
-                 prm ? 1 : (int)vec, (int)elem);
-        return fail(SODA_HIP_ERR_INVALID, buf);
-      }
+int check_run_tensors(const soda_hip_plan_t& plan, bool bank_tensors,
+                      void* const* outputs, const void* const* inputs,
+                      int64_t cells, int32_t batch) {
+  if (bank_tensors) return SODA_HIP_OK;
+  const int out0 = plan.num_inputs;
+  const int prm0 = out0 + plan.num_outputs + plan.num_locals;
+  // Overlap: passes read their inputs while they write their outputs, and
+  // ping-pong through the outputs.
+  auto bytes_of = [&](int slot) {
+    return (uint64_t)cells * (uint64_t)batch * (uint64_t)plan.elem_size[slot];
+  };
+  auto overlap = [](const void* a, uint64_t na, const void* b, uint64_t nb) {
+    const uintptr_t a0 = reinterpret_cast<uintptr_t>(a);
+    const uintptr_t b0 = reinterpret_cast<uintptr_t>(b);
+    return a0 < b0 + nb && b0 < a0 + na;
+  };
+  for (int o = 0; o < plan.num_outputs; ++o) {
+    for (int i = 0; i < plan.num_inputs; ++i)
+      if (overlap(outputs[o], bytes_of(out0 + o), inputs[i], bytes_of(i)))
+        return fail(SODA_HIP_ERR_INVALID,
+                    std::string("run_device: an output ") +
+                        (outputs[o] == inputs[i] ? "aliases" : "overlaps") +
+                        " an input (in-place runs are not supported: inputs "
+                        "are read while outputs are written); nothing was "
+                        "launched");
+    for (int k = 0; k < plan.num_params; ++k)
+      if (overlap(outputs[o], bytes_of(out0 + o), inputs[plan.num_inputs + k],
+                  (uint64_t)plan.param_elems[k] * plan.elem_size[prm0 + k]))
+        return fail(SODA_HIP_ERR_INVALID,
+                    "run_device: an output overlaps a param array; nothing "
+                    "was launched");
+    for (int q = 0; q < o; ++q)
+      if (overlap(outputs[o], bytes_of(out0 + o), outputs[q],
+                  bytes_of(out0 + q)))
+        return fail(SODA_HIP_ERR_INVALID,
+                    "run_device: two outputs overlap; nothing was launched");
+  }
+  // Alignment (the geometry makes sure that the row length is a multiple of
+  // every kernel's cells per lane: a row, a plane, a slab window or a band
+  // then starts on a fragment boundary iff the array does).  A kernel moves a
+  // tensor in fragments of `vec` cells, with one instruction of up to 16
+  // bytes each -- marching and tile3d kernels through buffer resources
+  // (soda_rt.h soda_buf_load_frag / soda_buf_store_frag), direct and ldswin
+  // kernels through vector pointers (soda_load_frag / soda_store_frag;
+  // ldswin's quads are four 4-byte cells) -- so every tensor must be aligned
+  // to min(16, vec x its cell size) for the widest `vec` of the plan; param
+  // arrays are read cell by cell.
+  int32_t vec = 1;
+  for (int k = 0; k < plan.num_kernels; ++k)
+    if (plan.kernels[k].vec > vec) vec = plan.kernels[k].vec;
+  char buf[256];
+  for (int t = 0; t < plan.num_inputs + plan.num_outputs + plan.num_params;
+       ++t) {
+    const bool prm = t >= plan.num_inputs + plan.num_outputs;
+    const int k = t - plan.num_inputs - plan.num_outputs;
+    const void* ptr = prm ? inputs[plan.num_inputs + k]
+                          : t < out0 ? inputs[t] : outputs[t - out0];
+    const int64_t elem = plan.elem_size[prm ? prm0 + k : t];
+    int64_t align = prm ? elem : (int64_t)vec * elem;
+    if (align > 16) align = 16;
+    if (align > 1 && reinterpret_cast<uintptr_t>(ptr) % (uintptr_t)align) {
+      snprintf(buf, sizeof buf,
+               "run_device: %s %d at %p is not aligned to %d bytes (%d cells "
+               "per lane x %d-byte cells, at most 16; params: one cell); "
+               "nothing was launched",
+               prm ? "param array" : t < out0 ? "input" : "output",
+               prm ? k : t < out0 ? t : t - out0, ptr, (int)align,
+               prm ? 1 : (int)vec, (int)elem);
+      return fail(SODA_HIP_ERR_INVALID, buf);
     }
   }
+  return SODA_HIP_OK;
+}
+
+// Launches of every pass, their sum, and -- in a residual run -- the pass that
+// goes last and whether it runs as its twin.
+struct Schedule {
   int32_t count[SODA_HIP_MAX_PASSES];
   int32_t total = 0;
-  if (force_pass >= 0) {
-    if (force_pass >= plan.num_passes ||
-        iterate % plan.passes[force_pass].fused_iters)
-      return fail(SODA_HIP_ERR_INVALID, "run_core: bad forced pass");
-    for (int i = 0; i < plan.num_passes; ++i) count[i] = 0;
-    count[force_pass] = total = iterate / plan.passes[force_pass].fused_iters;
-  } else {
-    ExtentKey key;
-    for (int d = 0; d < SODA_HIP_MAX_DIM; ++d) key[d] = base.extent[d];
-    // Never next to a halo exchange (the caller's events say other streams
-    // are live: a calibration allocates, frees and synchronises -- it would
-    // stall the neighbours and make every rank's schedule depend on who ran
-    // beside it), never on a capturing stream (synchronising is illegal
-    // there): such runs are scheduled by the model unless the caller
-    // calibrated the extent beforehand (soda_hip_program_calibrate).
-    const bool beside_exchange = slab && (slab->ghosts_ready || slab->sendable);
-    hipStreamCaptureStatus capture = hipStreamCaptureStatusNone;
-    if (p->auto_calibrate && !p->calibrating && !beside_exchange)
-      if (hipStreamIsCapturing(stream, &capture) != hipSuccess) {
-        (void)hipGetLastError();
-        capture = hipStreamCaptureStatusNone;
-      }
-    if (p->auto_calibrate && !p->calibrating && !beside_exchange &&
-        capture == hipStreamCaptureStatusNone && iterate > 1 &&
-        plan.num_passes > 1 && plan.num_inputs == plan.num_outputs &&
-        !measured.count(key)) {
-      // first run on this extent: let the clock rank the passes
-      p->calibrating = true;
-      int rc = soda_hip_program_calibrate_batch(p, base.extent, batch, 4,
-                                                stream_);
-      p->calibrating = false;
-      if (rc) return rc;
-      if (int rc2 = extent_plan(plan, &extents, base.extent, &ep, batch))
-        return rc2;
-    }
-    auto& memo = const_cast<ExtentPlan*>(ep)->sched;
-    auto hit = memo.find(iterate);
-    if (hit == memo.end()) {
-      // measured launch times of this very extent (soda_hip_program_calibrate)
-      // outrank the model
-      auto it = measured.find(key);
-      const std::vector<double>& pass_ns =
-          it != measured.end() ? it->second : ep->model_ns;
-      if (int rc = schedule(plan, pass_ns, iterate, count, &total)) return rc;
-      std::vector<int32_t> row(count, count + plan.num_passes);
-      row.push_back(total);
-      if (memo.size() > 256) memo.clear();
-      hit = memo.emplace(iterate, std::move(row)).first;
-    }
-    for (int i = 0; i < plan.num_passes; ++i) count[i] = hit->second[i];
-    total = hit->second[plan.num_passes];
-  }
+  int res_pass = -1;
+  bool res_twin = false;
+};
 
+// The multiset of passes that adds up to `iterate` at least total cost (100
+// iterations with passes of 12 / 8 / 4 / 1: 7 x 12 + 2 x 8 beats 8 x 12 + 4);
+// without costs, as many of the deepest kind as fit, then the next...
+// Remembered per (extent, iterate).
+static int choose_schedule(soda_hip_program* p, const RunRequest& rq,
+                           const int32_t* ext, Schedule* s) {
+  const soda_hip_plan_t& plan = p->plan;
+  const int32_t iterate = rq.iterate;
+  // plans, schedules and measured times of this batch size
+  std::map<ExtentKey, ExtentPlan>& extents = extents_of(p, rq.batch);
+  std::map<ExtentKey, std::vector<double>>& measured =
+      measured_of(p, rq.batch);
+  ExtentPlan* ep = nullptr;
+  if (int rc = extent_plan(plan, &extents, ext, &ep, rq.batch)) return rc;
+  if (rq.force_pass >= 0) {
+    if (rq.force_pass >= plan.num_passes ||
+        iterate % plan.passes[rq.force_pass].fused_iters)
+      return fail(SODA_HIP_ERR_INVALID, "run_core: bad forced pass");
+    for (int i = 0; i < plan.num_passes; ++i) s->count[i] = 0;
+    s->count[rq.force_pass] = s->total =
+        iterate / plan.passes[rq.force_pass].fused_iters;
+    return SODA_HIP_OK;   // (never a residual run: run_core checks)
+  }
+  ExtentKey key;
+  for (int d = 0; d < SODA_HIP_MAX_DIM; ++d) key[d] = ext[d];
+  auto known = measured.find(key);
+  // Never next to a halo exchange (the caller's events say other streams
+  // are live: a calibration allocates, frees and synchronises -- it would
+  // stall the neighbours and make every rank's schedule depend on who ran
+  // beside it), never on a capturing stream (synchronising is illegal
+  // there): such runs are scheduled by the model unless the caller
+  // calibrated the extent beforehand (soda_hip_program_calibrate).
+  const bool beside_exchange =
+      rq.slab && (rq.slab->ghosts_ready || rq.slab->sendable);
+  const bool may_calibrate =
+      p->auto_calibrate && !p->calibrating && !beside_exchange;
+  hipStreamCaptureStatus capture = hipStreamCaptureStatusNone;
+  if (may_calibrate &&
+      hipStreamIsCapturing(static_cast<hipStream_t>(rq.stream), &capture) !=
+          hipSuccess) {
+    (void)hipGetLastError();
+    capture = hipStreamCaptureStatusNone;
+  }
+  if (may_calibrate && capture == hipStreamCaptureStatusNone && iterate > 1 &&
+      plan.num_passes > 1 && plan.num_inputs == plan.num_outputs &&
+      known == measured.end()) {
+    // first run on this extent: let the clock rank the passes
+    p->calibrating = true;
+    int rc = soda_hip_program_calibrate_batch(p, ext, rq.batch, 4, rq.stream);
+    p->calibrating = false;
+    if (rc) return rc;
+    if (int rc2 = extent_plan(plan, &extents, ext, &ep, rq.batch)) return rc2;
+    known = measured.find(key);
+  }
+  // measured launch times of this very extent (soda_hip_program_calibrate)
+  // outrank the model
+  const std::vector<double>& pass_ns =
+      known != measured.end() ? known->second : ep->model_ns;
+  auto& memo = ep->sched;
+  auto hit = memo.find(iterate);
+  if (hit == memo.end()) {
+    if (int rc = schedule(plan, pass_ns, iterate, s->count, &s->total))
+      return rc;
+    std::vector<int32_t> row(s->count, s->count + plan.num_passes);
+    row.push_back(s->total);
+    if (memo.size() > 256) memo.clear();
+    hit = memo.emplace(iterate, std::move(row)).first;
+  }
+  for (int i = 0; i < plan.num_passes; ++i) s->count[i] = hit->second[i];
+  s->total = hit->second[plan.num_passes];
   // A residual run keeps the multiset of passes and changes their order: the
   // pass that takes the residual goes last.  That is the deepest scheduled
   // pass whose kernel has a twin (the residual costs a launch the same work
@@ -1475,18 +1475,164 @@ int run_core(soda_hip_program_t* p, void* const* outputs,
   // behind which `<app>_residual` compares the outputs with that pass's
   // inputs -- taken out of a deeper pass's count where the schedule had none
   // (iterate - 1 iterations scheduled, one added).
-  int res_last = -1;
-  bool res_twin = false;
-  if (res) {
-    ExtentKey key;
-    for (int d = 0; d < SODA_HIP_MAX_DIM; ++d) key[d] = base.extent[d];
-    auto it = measured.find(key);
-    const std::vector<double>& pass_ns =
-        it != measured.end() ? it->second : ep->model_ns;
-    if (int rc = residual_order(plan, pass_ns, iterate, count, &total,
-                                &res_last, &res_twin, res->norms != nullptr))
+  if (rq.residual)
+    return residual_order(plan, pass_ns, iterate, s->count, &s->total,
+                          &s->res_pass, &s->res_twin,
+                          rq.residual->norms != nullptr);
+  return SODA_HIP_OK;
+}
+
+// Scratch of a run of `s` on `cells` x `batch` cells, ahead of its first
+// launch: the locals (into `base`) and the ping-pong temporaries.
+static int ensure_scratch(soda_hip_program* p, const RunRequest& rq,
+                          const Schedule& s, bool own_pingpong, int64_t cells,
+                          soda_hip_kargs_t* base) {
+  const soda_hip_plan_t& plan = p->plan;
+  const int out0 = plan.num_inputs, loc0 = out0 + plan.num_outputs;
+  // scratch for the local tensors -- only if a scheduled pass keeps them in
+  // memory (marching kernels hold them in registers)
+  const bool need_locals = locals_in_memory(plan, s.count);
+  // Growing scratch allocates and synchronises (ensure): illegal on a stream
+  // that is being captured.  Known here, before the first launch; the stream
+  // is asked only when something must grow.
+  if (scratch_grows(p, need_locals, s.total, own_pingpong, cells, rq.batch))
+    if (int rc = refuse_growth_while_capturing(rq.stream, "run_device"))
       return rc;
+  // (all of it for the whole batch: item i of a local or a temporary lies i
+  // grids behind its start, like the caller's tensors; a larger batch regrows)
+  for (int l = 0; need_locals && l < plan.num_locals; ++l) {
+    int rc = ensure(p->locals[l],
+                    (size_t)cells * rq.batch * plan.elem_size[loc0 + l]);
+    if (rc) return rc;
+    base->buf[loc0 + l] = p->locals[l].ptr;
   }
+  if (s.total > 1)
+    for (int o = 0; o < plan.num_outputs; ++o) {
+      const size_t bytes = (size_t)cells * rq.batch * plan.elem_size[out0 + o];
+      if (int rc = ensure(p->temps[o], bytes)) return rc;
+      if (own_pingpong)
+        if (int rc = ensure(p->temps2[o], bytes)) return rc;
+    }
+  return SODA_HIP_OK;
+}
+
+// The residual of a run, as its last pass takes it: as the pass's twin (both
+// parts of a split pass -- one struct, one box, every chunk in exactly one
+// part), or by `<app>_residual` / the norms kernels behind the pass.  `box`:
+// in the coordinates of the rows that launch addresses.
+struct ResidualTake {
+  const ResidualRun* run;
+  bool twin;
+  soda_hip_resbox_t box;
+};
+
+// One pass of a run on `args`, by the tiles of `use`.  `take`: null for every
+// pass but the last of a residual run.
+static int launch_pass(soda_hip_program* p, const RunRequest& rq,
+                       const PassLaunch& L, const soda_hip_kargs_t& args,
+                       const ExtentPlan& use, const ResidualTake* take) {
+  const soda_hip_plan_t& plan = p->plan;
+  const auto& pass = plan.passes[L.pass];
+  hipStream_t stream = static_cast<hipStream_t>(rq.stream);
+  const SlabRun* slab = rq.slab;
+  const bool twin = take && take->twin;
+  void* const rdev = twin ? take->run->dev : nullptr;
+  const soda_hip_resbox_t* box = take ? &take->box : nullptr;
+  auto kernel_of = [&](int k) {
+    const int kk = pass.kernel[k];
+    return twin ? plan.kernels[kk].twin : kk;
+  };
+  if (L.split) {
+    // (a split pass is one marching kernel: plan_launches)
+    const int k0 = kernel_of(0);
+    const int32_t hole = L.bnd_hi - L.bnd_lo;
+    const TileRange boundary = {plan.dim - 1, L.bnd_lo, hole, L.chunks - hole};
+    const TileRange interior = {plan.dim - 1, 0, L.bnd_lo, hole};
+    auto part = [&](const TileRange& range, hipStream_t on) {
+      return launch(p, k0, args, use.geo[k0].tile, on, &range, 1, rdev, box);
+    };
+    const bool in_order = split_in_order();
+    if (in_order && !L.record) {
+      // both parts on the caller's stream, the part that does not depend on
+      // the exchange first: no hand-over between streams, but the two launches
+      // do not share the GPU.  First pass: interior, wait, boundary
+      if (int rc = part(interior, stream)) return rc;
+      HIP_TRY(hipStreamWaitEvent(stream, slab->ghosts_ready, 0));
+      if (int rc = part(boundary, stream)) return rc;
+    } else if (in_order) {
+      // last pass: (wait,) boundary, signal, interior
+      if (L.wait) HIP_TRY(hipStreamWaitEvent(stream, slab->ghosts_ready, 0));
+      if (int rc = part(boundary, stream)) return rc;
+      HIP_TRY(hipEventRecord(slab->sendable, stream));
+      if (int rc = part(interior, stream)) return rc;
+    } else {
+      // the boundary chunks on the program's side stream, the interior on the
+      // caller's: the two share the GPU, the copies run underneath
+      if (int rc = side_stream(p)) return rc;
+      const int turn = p->ev_turn;
+      p->ev_turn ^= 1;
+      HIP_TRY(hipEventRecord(p->ev_pre[turn], stream));
+      HIP_TRY(hipStreamWaitEvent(p->side, p->ev_pre[turn], 0));
+      if (L.wait) HIP_TRY(hipStreamWaitEvent(p->side, slab->ghosts_ready, 0));
+      if (int rc = part(boundary, p->side)) return rc;
+      if (L.record) HIP_TRY(hipEventRecord(slab->sendable, p->side));
+      HIP_TRY(hipEventRecord(p->ev_bnd[turn], p->side));
+      if (int rc = part(interior, stream)) return rc;
+      HIP_TRY(hipStreamWaitEvent(stream, p->ev_bnd[turn], 0));
+    }
+    ++p->last_split;
+  } else {
+    if (L.wait) HIP_TRY(hipStreamWaitEvent(stream, slab->ghosts_ready, 0));
+    for (int k = 0; k < pass.num_kernels; ++k) {
+      const int kk = kernel_of(k);
+      if (int rc = launch(p, kk, args, use.geo[kk].tile, stream, nullptr,
+                          rq.batch, rdev, box))
+        return rc;
+    }
+  }
+  p->last_launches += L.split ? 2 : pass.num_kernels;
+  if (L.pass == 0) p->last_fused += pass.num_kernels;
+  if (take && !take->twin) {
+    // cur: what the pass just wrote; prev: what it read.  Behind both parts
+    // of a split pass: it reads all of what the pass wrote and writes the
+    // struct only, so `sendable` need not wait for it
+    if (int rc = launch_generic(p, args, stream, *take->run, take->box))
+      return rc;
+    ++p->last_launches;
+  }
+  if (!L.split && L.record) HIP_TRY(hipEventRecord(slab->sendable, stream));
+  return SODA_HIP_OK;
+}
+
+int run_core(soda_hip_program_t* p, const RunRequest& rq) {
+  if (!p || !rq.outputs || !rq.inputs || !rq.extent)
+    return fail(SODA_HIP_ERR_INVALID, "run_device: NULL argument");
+  const soda_hip_plan_t& plan = p->plan;
+  const ResidualRun* res = rq.residual;
+  const int32_t iterate = rq.iterate, batch = rq.batch;
+  if (res && (batch != 1 || rq.force_pass >= 0 || !plan.residual.present ||
+              !res->dev || res->box_iterate < iterate))
+    return fail(SODA_HIP_ERR_INVALID, "run_core: bad residual run");
+  if (batch < 1 || (batch > 1 && (!plan.batched || rq.slab)))
+    return fail(SODA_HIP_ERR_INVALID, "run_core: bad batch");
+  if (iterate < 1) return fail(SODA_HIP_ERR_INVALID, "cannot iterate < 1 times");
+  if (iterate > 1 && plan.num_inputs != plan.num_outputs)
+    return fail(SODA_HIP_ERR_INVALID,
+                "number of input tensors must be the same as output if "
+                "iterate > 1 times");
+  hipStream_t stream = static_cast<hipStream_t>(rq.stream);
+  HIP_TRY(hipSetDevice(p->device));
+  const Cone* cone = rq.slab ? &rq.slab->cone : nullptr;
+
+  soda_hip_kargs_t base;
+  int64_t cells;
+  if (int rc = run_geometry(plan, rq, &base, &cells)) return rc;
+  if (int rc = check_run_tensors(plan, p->bank_tensors, rq.outputs, rq.inputs,
+                                 cells, batch))
+    return rc;
+  Schedule s;
+  if (int rc = choose_schedule(p, rq, base.extent, &s)) return rc;
+  const int32_t total = s.total;
 
   if (p->debug) base.buf[SODA_HIP_MAX_TENSORS - 1] = p->debug;
   // the banked form of a wire stream's program: the stream's length, beyond
@@ -1497,13 +1643,10 @@ int run_core(soda_hip_program_t* p, void* const* outputs,
   // (the marching kernel holds them in registers; its a.buf[] slots end with
   // the output banks) -- stream.py `banked_spec`
   base.reserved[0] = p->stream_elems;
-  const int in0 = 0, out0 = plan.num_inputs, loc0 = out0 + plan.num_outputs;
-  const int prm0 = loc0 + plan.num_locals;
+  const int in0 = 0, out0 = plan.num_inputs;
+  const int prm0 = out0 + plan.num_outputs + plan.num_locals;
   for (int k = 0; k < plan.num_params; ++k)   // the same in every iteration
-    base.buf[prm0 + k] = const_cast<void*>(inputs[plan.num_inputs + k]);
-  // scratch for the local tensors -- only if a scheduled pass keeps them in
-  // memory (marching kernels hold them in registers)
-  const bool need_locals = locals_in_memory(plan, count);
+    base.buf[prm0 + k] = const_cast<void*>(rq.inputs[plan.num_inputs + k]);
   // A run that trims its passes to a cone promises to leave the rows of the
   // caller's outputs beyond the LAST pass's reach as they were (soda_hip.h,
   // soda_hip_run_device_cone).  The earlier passes cover more rows than the
@@ -1512,31 +1655,13 @@ int run_core(soda_hip_program_t* p, void* const* outputs,
   const bool own_pingpong =
       cone && total > 2 &&
       (cone->keep_lo > 0 || cone->keep_hi < base.extent[plan.dim - 1]);
-  // Growing scratch allocates and synchronises (ensure): illegal on a stream
-  // that is being captured.  Known here, before the first launch; the stream
-  // is asked only when something must grow.
-  if (scratch_grows(p, need_locals, total, own_pingpong, cells, batch))
-    if (int rc = refuse_growth_while_capturing(stream_, "run_device"))
-      return rc;
-  // (all of it for the whole batch: item i of a local or a temporary lies i
-  // grids behind its start, like the caller's tensors; a larger batch regrows)
-  for (int l = 0; need_locals && l < plan.num_locals; ++l) {
-    int rc = ensure(p->locals[l],
-                    (size_t)cells * batch * plan.elem_size[loc0 + l]);
-    if (rc) return rc;
-    base.buf[loc0 + l] = p->locals[l].ptr;
-  }
-  if (total > 1)
-    for (int o = 0; o < plan.num_outputs; ++o) {
-      const size_t bytes = (size_t)cells * batch * plan.elem_size[out0 + o];
-      if (int rc = ensure(p->temps[o], bytes)) return rc;
-      if (own_pingpong)
-        if (int rc = ensure(p->temps2[o], bytes)) return rc;
-    }
+  if (int rc = ensure_scratch(p, rq, s, own_pingpong, cells, &base)) return rc;
 
+  std::map<ExtentKey, ExtentPlan>& extents = extents_of(p, batch);
   std::vector<PassLaunch> launches;
-  if (int rc = plan_launches(plan, &extents, base.extent, count, total,
-                             iterate, slab, &launches, res_last, res_twin))
+  if (int rc = plan_launches(plan, &extents, base.extent, s.count, total,
+                             iterate, rq.slab, &launches, s.res_pass,
+                             s.res_twin))
     return rc;
   soda_hip_resbox_t res_box;
   if (res) {
@@ -1564,29 +1689,28 @@ int run_core(soda_hip_program_t* p, void* const* outputs,
       HIP_TRY(hipModuleLaunchKernel(p->functions[zk], 1, 1, 1, 64, 1, 1, 0,
                                     stream, nullptr, extra));
     }
-    p->last_res_mode = res_twin ? 1 : 2;
-    p->last_res_fused = plan.passes[res_last].fused_iters;
+    p->last_res_mode = s.res_twin ? 1 : 2;
+    p->last_res_fused = plan.passes[s.res_pass].fused_iters;
   }
   p->last_launches = 0;
   p->last_fused = 0;
   p->last_split = 0;
   p->last_rows = 0;
-  std::vector<const void*> src(inputs, inputs + plan.num_inputs);
+  std::vector<const void*> src(rq.inputs, rq.inputs + plan.num_inputs);
   const int ax = plan.dim - 1;
   const int32_t rows = base.extent[ax];
   for (size_t done = 0; done < launches.size(); ++done) {
     const PassLaunch& L = launches[done];
-    const int i = L.pass;
     // the last pass writes the caller's outputs; before that alternate
     // between the program's temporaries and the caller's outputs
-    bool to_out = ((total - 1 - (int)done) % 2) == 0;
+    const bool to_out = ((total - 1 - (int)done) % 2) == 0;
+    const bool last_pass = (int)done + 1 == total;
     for (int j = 0; j < plan.num_inputs; ++j)
       base.buf[in0 + j] = const_cast<void*>(src[j]);
-    const bool last_pass = (int)done + 1 == total;
     for (int o = 0; o < plan.num_outputs; ++o)
-      base.buf[out0 + o] = !own_pingpong ? (to_out ? outputs[o]
+      base.buf[out0 + o] = !own_pingpong ? (to_out ? rq.outputs[o]
                                                    : p->temps[o].ptr)
-                           : last_pass   ? outputs[o]
+                           : last_pass   ? rq.outputs[o]
                            : to_out      ? p->temps2[o].ptr
                                          : p->temps[o].ptr;
     soda_hip_kargs_t args = base;
@@ -1597,118 +1721,159 @@ int run_core(soda_hip_program_t* p, void* const* outputs,
         args.buf[t] = static_cast<char*>(base.buf[t]) +
                       (int64_t)L.lo * base.stride[ax] * plan.elem_size[t];
     }
-    const ExtentPlan* use = nullptr;
+    ExtentPlan* use = nullptr;
     if (int rc = extent_plan(plan, &extents, args.extent, &use, batch))
       return rc;
     p->last_rows += L.hi - L.lo;
-    int k0 = plan.passes[i].kernel[0];
-    // The last pass of a residual run: as its twin (both parts of a split
-    // pass -- one struct, one box, every chunk in exactly one part), or
-    // followed by `<app>_residual`.  The box in the coordinates of the rows
-    // this launch addresses.
-    const bool take_twin = res && res_twin && last_pass;
-    const bool take_generic = res && !res_twin && last_pass;
-    void* const rdev = take_twin ? res->dev : nullptr;
-    soda_hip_resbox_t lbox;
-    if (take_twin || take_generic)
-      lbox = shifted_box(plan, res_box, L.lo, L.hi - L.lo);
-    if (take_twin) k0 = plan.kernels[k0].twin;
-    if (L.split && split_in_order()) {
-      // both parts on the caller's stream, the part that does not depend on
-      // the exchange first: no hand-over between streams, but the two launches
-      // do not share the GPU
-      const int32_t hole = L.bnd_hi - L.bnd_lo;
-      const TileRange boundary = {ax, L.bnd_lo, hole, L.chunks - hole};
-      const TileRange interior = {ax, 0, L.bnd_lo, hole};
-      if (!L.record) {       // first pass: interior, wait, boundary
-        if (int rc = launch(p, k0, args, use->geo[k0].tile, stream, &interior, 1,
-                            rdev, &lbox))
-          return rc;
-        HIP_TRY(hipStreamWaitEvent(stream, slab->ghosts_ready, 0));
-        if (int rc = launch(p, k0, args, use->geo[k0].tile, stream, &boundary, 1,
-                            rdev, &lbox))
-          return rc;
-      } else {               // last pass: (wait,) boundary, signal, interior
-        if (L.wait) HIP_TRY(hipStreamWaitEvent(stream, slab->ghosts_ready, 0));
-        if (int rc = launch(p, k0, args, use->geo[k0].tile, stream, &boundary, 1,
-                            rdev, &lbox))
-          return rc;
-        HIP_TRY(hipEventRecord(slab->sendable, stream));
-        if (int rc = launch(p, k0, args, use->geo[k0].tile, stream, &interior, 1,
-                            rdev, &lbox))
-          return rc;
-      }
-      p->last_launches += 2;
-      if (i == 0) ++p->last_fused;
-      ++p->last_split;
-      if (take_generic) {
-        // behind both parts: it reads all of what the pass wrote and writes
-        // the struct only, so `sendable` need not wait for it
-        if (int rc = launch_generic(p, args, stream, *res, lbox)) return rc;
-        ++p->last_launches;
-      }
-    } else if (L.split) {
-      // the boundary chunks on the program's side stream, the interior on the
-      // caller's: the two share the GPU, the copies run underneath
-      if (int rc = side_stream(p)) return rc;
-      const int turn = p->ev_turn;
-      p->ev_turn ^= 1;
-      HIP_TRY(hipEventRecord(p->ev_pre[turn], stream));
-      HIP_TRY(hipStreamWaitEvent(p->side, p->ev_pre[turn], 0));
-      if (L.wait) HIP_TRY(hipStreamWaitEvent(p->side, slab->ghosts_ready, 0));
-      const int32_t hole = L.bnd_hi - L.bnd_lo;
-      const TileRange boundary = {ax, L.bnd_lo, hole, L.chunks - hole};
-      if (int rc = launch(p, k0, args, use->geo[k0].tile, p->side, &boundary, 1,
-                            rdev, &lbox))
-        return rc;
-      if (L.record) HIP_TRY(hipEventRecord(slab->sendable, p->side));
-      HIP_TRY(hipEventRecord(p->ev_bnd[turn], p->side));
-      const TileRange interior = {ax, 0, L.bnd_lo, hole};
-      if (int rc = launch(p, k0, args, use->geo[k0].tile, stream, &interior, 1,
-                            rdev, &lbox))
-        return rc;
-      HIP_TRY(hipStreamWaitEvent(stream, p->ev_bnd[turn], 0));
-      p->last_launches += 2;
-      if (i == 0) ++p->last_fused;
-      ++p->last_split;
-      if (take_generic) {
-        if (int rc = launch_generic(p, args, stream, *res, lbox)) return rc;
-        ++p->last_launches;
-      }
-    } else {
-      if (L.wait) HIP_TRY(hipStreamWaitEvent(stream, slab->ghosts_ready, 0));
-      for (int k = 0; k < plan.passes[i].num_kernels; ++k) {
-        int kk = plan.passes[i].kernel[k];
-        if (take_twin) kk = plan.kernels[kk].twin;
-        int rc = launch(p, kk, args, use->geo[kk].tile, stream, nullptr, batch,
-                        rdev, &lbox);
-        if (rc) return rc;
-        ++p->last_launches;
-        if (i == 0) ++p->last_fused;
-      }
-      if (take_generic) {
-        // cur: what the pass just wrote; prev: what it read
-        if (int rc = launch_generic(p, args, stream, *res, lbox))
-          return rc;
-        ++p->last_launches;
-      }
-      if (L.record) HIP_TRY(hipEventRecord(slab->sendable, stream));
-    }
-    if ((int)done + 1 < total)
+    ResidualTake take;
+    if (res && last_pass)
+      take = {res, s.res_twin,
+              shifted_box(plan, res_box, L.lo, L.hi - L.lo)};
+    if (int rc = launch_pass(p, rq, L, args, *use,
+                             res && last_pass ? &take : nullptr))
+      return rc;
+    if (!last_pass)
       for (int j = 0; j < plan.num_inputs; ++j) src[j] = base.buf[out0 + j];
   }
   return SODA_HIP_OK;
 }
 
+// Runs `check_every` iterations at a time until `converged(&stop)` says so by
+// the struct of the last chunk -- `host_bytes` fetched into `host`; `norms`
+// null: the residual struct -- or `max_iterate` iterations are done.  The
+// chunks ping-pong between the caller's outputs and p->until_tmp: the first
+// reads the caller's inputs, every later one the result before it.
+// Synchronous.
+template <class Converged>
+static int run_until(soda_hip_program* p, const char* who,
+                     void* const* outputs, const void* const* inputs,
+                     const int32_t* extent, int32_t max_iterate,
+                     int32_t check_every, soda_hip_norms_handle* norms,
+                     void* host, size_t host_bytes, Converged converged,
+                     int32_t* iterations_done, void* stream_) {
+  const soda_hip_plan_t& plan = p->plan;
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  HIP_TRY(hipSetDevice(p->device));
+  hipStreamCaptureStatus capture = hipStreamCaptureStatusNone;
+  if (hipStreamIsCapturing(stream, &capture) != hipSuccess) {
+    (void)hipGetLastError();
+    capture = hipStreamCaptureStatusNone;
+  }
+  if (capture != hipStreamCaptureStatusNone)
+    return fail(SODA_HIP_ERR_INVALID,
+                std::string(who) +
+                    ": synchronous, not for a stream that is being captured; "
+                    "nothing was launched");
+  int64_t cells = 1;
+  for (int d = 0; d < plan.dim; ++d) {
+    if (extent[d] < 1)
+      return fail(SODA_HIP_ERR_INVALID, std::string(who) + ": extent < 1");
+    cells *= extent[d];
+  }
+  if (int rc = ensure(p->until_struct, host_bytes)) return rc;
+  const int out0 = plan.num_inputs;
+  std::vector<const void*> in(inputs,
+                              inputs + plan.num_inputs + plan.num_params);
+  std::vector<void*> tmp(plan.num_outputs, nullptr);
+  std::vector<void*> own(outputs, outputs + plan.num_outputs);
+  memset(host, 0, host_bytes);
+  int32_t done = 0;
+  bool in_tmp = false;
+  for (int32_t chunk = 0; done < max_iterate; ++chunk) {
+    const int32_t n =
+        max_iterate - done < check_every ? max_iterate - done : check_every;
+    in_tmp = chunk % 2 == 1;
+    if (in_tmp && !tmp[0])
+      for (int o = 0; o < plan.num_outputs; ++o) {
+        if (int rc = ensure(p->until_tmp[o],
+                            (size_t)cells * plan.elem_size[out0 + o]))
+          return rc;
+        tmp[o] = p->until_tmp[o].ptr;
+      }
+    void* const* dst = in_tmp ? tmp.data() : own.data();
+    const ResidualRun run = {p->until_struct.ptr, done + n, norms};
+    RunRequest rq = {dst, in.data(), extent, n, stream_};
+    rq.residual = &run;
+    if (int rc = run_core(p, rq)) return rc;
+    HIP_TRY(hipMemcpyAsync(host, p->until_struct.ptr, host_bytes,
+                           hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    done += n;
+    // the next chunk continues from this one's result; the caller's inputs
+    // were read by the first chunk only
+    for (int j = 0; j < plan.num_inputs; ++j) in[j] = dst[j];
+    bool stop = false;
+    if (int rc = converged(&stop)) return rc;
+    if (stop) break;
+  }
+  if (in_tmp) {
+    for (int o = 0; o < plan.num_outputs; ++o)
+      HIP_TRY(hipMemcpyAsync(outputs[o], tmp[o],
+                             (size_t)cells * plan.elem_size[out0 + o],
+                             hipMemcpyDeviceToDevice, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+  }
+  if (iterations_done) *iterations_done = done;
+  return SODA_HIP_OK;
+}
+
 }  // namespace soda_detail
+
+// a call that may be refused before run_core reads as zero launches
+static void reset_last_run(soda_hip_program* p) {
+  p->last_res_mode = 0;
+  p->last_res_fused = 0;
+  p->last_launches = 0;
+  p->last_fused = 0;
+}
+
+// a box per output as the C entries hand it out: lo[o * dim + d], hi likewise
+static void flatten_box(const soda_hip_plan_t& plan,
+                        const soda_hip_resbox_t& box, int32_t* lo,
+                        int32_t* hi) {
+  for (int o = 0; o < plan.num_outputs; ++o)
+    for (int d = 0; d < plan.dim; ++d) {
+      lo[o * plan.dim + d] = box.lo[o][d];
+      hi[o * plan.dim + d] = box.hi[o][d];
+    }
+}
+
+static int check_struct_aligned(const void* dev, const char* what,
+                                const char* who) {
+  if (reinterpret_cast<uintptr_t>(dev) % 8)
+    return fail(SODA_HIP_ERR_INVALID,
+                std::string(who) + ": the " + what +
+                    " struct is not 8-byte aligned; nothing was launched");
+  return SODA_HIP_OK;
+}
+
+// The struct of `bytes` a run fills (`what`: "residual" / "norms"): 8-byte
+// aligned, and no byte of it in an output of `extent`.
+static int check_run_struct(const soda_hip_plan_t& plan, void* const* outputs,
+                            const int32_t* extent, const void* dev,
+                            size_t bytes, const char* what, const char* who) {
+  if (int rc = check_struct_aligned(dev, what, who)) return rc;
+  uint64_t cells = 1;
+  for (int d = 0; d < plan.dim; ++d)
+    cells *= (uint64_t)(extent[d] > 0 ? extent[d] : 0);
+  const uintptr_t r0 = reinterpret_cast<uintptr_t>(dev);
+  for (int o = 0; o < plan.num_outputs; ++o) {
+    const uintptr_t o0 = reinterpret_cast<uintptr_t>(outputs[o]);
+    if (outputs[o] && r0 < o0 + cells * plan.elem_size[plan.num_inputs + o] &&
+        o0 < r0 + bytes)
+      return fail(SODA_HIP_ERR_INVALID,
+                  std::string(who) + ": the " + what +
+                      " struct overlaps an output; nothing was launched");
+  }
+  return SODA_HIP_OK;
+}
 
 extern "C" {
 
 int soda_hip_run_device(soda_hip_program_t* p, void* const* outputs,
                         const void* const* inputs, const int32_t* extent,
                         int32_t iterate, void* stream_) {
-  return run_core(p, outputs, inputs, extent, nullptr, nullptr, iterate,
-                  stream_, -1, nullptr);
+  return run_core(p, {outputs, inputs, extent, iterate, stream_});
 }
 
 int soda_hip_plan_residual_box(const soda_hip_plan_t* plan,
@@ -1727,42 +1892,24 @@ int soda_hip_plan_residual_box(const soda_hip_plan_t* plan,
       return fail(SODA_HIP_ERR_INVALID, "plan_residual_box: extent < 1");
   soda_hip_resbox_t box;
   residual_box(*plan, extent, iterate, &box);
-  for (int o = 0; o < plan->num_outputs; ++o)
-    for (int d = 0; d < plan->dim; ++d) {
-      lo[o * plan->dim + d] = box.lo[o][d];
-      hi[o * plan->dim + d] = box.hi[o][d];
-    }
+  flatten_box(*plan, box, lo, hi);
   return SODA_HIP_OK;
 }
 
-// what both residual entries ask of a program and of the 32 bytes
+// what the residual entries ask of a program and of the 32 bytes
+// (residual_dev null: of the program only)
 static int check_residual(const soda_hip_program* p, void* const* outputs,
                           const int32_t* extent, const void* residual_dev,
                           const char* who) {
-  const soda_hip_plan_t& plan = p->plan;
-  if (!plan.residual.present)
+  if (!p->plan.residual.present)
     return fail(SODA_HIP_ERR_UNSUPPORTED,
                 std::string(who) +
                     ": the program has no residual kernels (build it with "
                     "LowerOptions.residual / sodac --hip-residual); nothing "
                     "was launched");
   if (!residual_dev) return SODA_HIP_OK;
-  if (reinterpret_cast<uintptr_t>(residual_dev) % 8)
-    return fail(SODA_HIP_ERR_INVALID,
-                std::string(who) + ": the residual struct is not 8-byte "
-                                   "aligned; nothing was launched");
-  uint64_t cells = 1;
-  for (int d = 0; d < plan.dim; ++d) cells *= (uint64_t)(extent[d] > 0 ? extent[d] : 0);
-  const uintptr_t r0 = reinterpret_cast<uintptr_t>(residual_dev);
-  for (int o = 0; o < plan.num_outputs; ++o) {
-    const uintptr_t o0 = reinterpret_cast<uintptr_t>(outputs[o]);
-    if (outputs[o] && r0 < o0 + cells * plan.elem_size[plan.num_inputs + o] &&
-        o0 < r0 + sizeof(soda_hip_residual_t))
-      return fail(SODA_HIP_ERR_INVALID,
-                  std::string(who) + ": the residual struct overlaps an "
-                                     "output; nothing was launched");
-  }
-  return SODA_HIP_OK;
+  return check_run_struct(p->plan, outputs, extent, residual_dev,
+                          sizeof(soda_hip_residual_t), "residual", who);
 }
 
 int soda_hip_run_device_residual(soda_hip_program_t* p, void* const* outputs,
@@ -1771,16 +1918,14 @@ int soda_hip_run_device_residual(soda_hip_program_t* p, void* const* outputs,
                                  void* residual_dev, void* stream_) {
   if (!p || !outputs || !inputs || !extent || !residual_dev)
     return fail(SODA_HIP_ERR_INVALID, "run_device_residual: NULL argument");
-  p->last_res_mode = 0;
-  p->last_res_fused = 0;
-  p->last_launches = 0;
-  p->last_fused = 0;
+  reset_last_run(p);
   if (int rc = check_residual(p, outputs, extent, residual_dev,
                               "run_device_residual"))
     return rc;
   const ResidualRun run = {residual_dev, iterate};
-  return run_core(p, outputs, inputs, extent, nullptr, nullptr, iterate,
-                  stream_, -1, nullptr, 1, &run);
+  RunRequest rq = {outputs, inputs, extent, iterate, stream_};
+  rq.residual = &run;
+  return run_core(p, rq);
 }
 
 int soda_hip_run_device_until(soda_hip_program_t* p, void* const* outputs,
@@ -1796,71 +1941,16 @@ int soda_hip_run_device_until(soda_hip_program_t* p, void* const* outputs,
                 "run_device_until: max_iterate and check_every must be >= 1");
   if (int rc = check_residual(p, outputs, extent, nullptr, "run_device_until"))
     return rc;
-  const soda_hip_plan_t& plan = p->plan;
-  hipStream_t stream = static_cast<hipStream_t>(stream_);
-  HIP_TRY(hipSetDevice(p->device));
-  hipStreamCaptureStatus capture = hipStreamCaptureStatusNone;
-  if (hipStreamIsCapturing(stream, &capture) != hipSuccess) {
-    (void)hipGetLastError();
-    capture = hipStreamCaptureStatusNone;
-  }
-  if (capture != hipStreamCaptureStatusNone)
-    return fail(SODA_HIP_ERR_INVALID,
-                "run_device_until: synchronous, not for a stream that is "
-                "being captured; nothing was launched");
-  int64_t cells = 1;
-  for (int d = 0; d < plan.dim; ++d) {
-    if (extent[d] < 1)
-      return fail(SODA_HIP_ERR_INVALID, "run_device_until: extent < 1");
-    cells *= extent[d];
-  }
-  if (int rc = ensure(p->until_res, sizeof(soda_hip_residual_t))) return rc;
-  const int out0 = plan.num_inputs;
-  std::vector<const void*> in(inputs,
-                              inputs + plan.num_inputs + plan.num_params);
-  std::vector<void*> tmp(plan.num_outputs, nullptr);
-  std::vector<void*> own(outputs, outputs + plan.num_outputs);
   soda_hip_residual_t host;
-  memset(&host, 0, sizeof host);
-  int32_t done = 0;
-  bool in_tmp = false;
-  for (int32_t chunk = 0; done < max_iterate; ++chunk) {
-    const int32_t n =
-        max_iterate - done < check_every ? max_iterate - done : check_every;
-    in_tmp = chunk % 2 == 1;
-    if (in_tmp && !tmp[0])
-      for (int o = 0; o < plan.num_outputs; ++o) {
-        if (int rc = ensure(p->until_tmp[o],
-                            (size_t)cells * plan.elem_size[out0 + o]))
-          return rc;
-        tmp[o] = p->until_tmp[o].ptr;
-      }
-    void* const* dst = in_tmp ? tmp.data() : own.data();
-    const ResidualRun run = {p->until_res.ptr, done + n};
-    if (int rc = run_core(p, dst, in.data(), extent, nullptr, nullptr, n,
-                          stream_, -1, nullptr, 1, &run))
-      return rc;
-    HIP_TRY(hipMemcpyAsync(&host, p->until_res.ptr, sizeof host,
-                           hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
-    done += n;
-    // the next chunk continues from this one's result; the caller's inputs
-    // were read by the first chunk only
-    for (int j = 0; j < plan.num_inputs; ++j) in[j] = dst[j];
-    double max_float;
-    memcpy(&max_float, &host.max_float_bits, sizeof max_float);
-    if (host.unordered == 0 && max_float <= tol && host.max_int <= int_tol)
-      break;
-  }
-  if (in_tmp) {
-    for (int o = 0; o < plan.num_outputs; ++o)
-      HIP_TRY(hipMemcpyAsync(outputs[o], tmp[o],
-                             (size_t)cells * plan.elem_size[out0 + o],
-                             hipMemcpyDeviceToDevice, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
-  }
+  auto converged = [&](bool* stop) {
+    *stop = residual_converged(host, tol, int_tol);
+    return SODA_HIP_OK;
+  };
+  if (int rc = run_until(p, "run_device_until", outputs, inputs, extent,
+                         max_iterate, check_every, nullptr, &host, sizeof host,
+                         converged, iterations_done, stream_))
+    return rc;
   if (result_host) *result_host = host;
-  if (iterations_done) *iterations_done = done;
   return SODA_HIP_OK;
 }
 
@@ -1930,19 +2020,12 @@ int soda_hip_norms_destroy(soda_hip_norms_handle_t* h) {
   return SODA_HIP_OK;
 }
 
-static int check_norms_struct(const void* acc_dev, const char* who) {
-  if (reinterpret_cast<uintptr_t>(acc_dev) % 8)
-    return fail(SODA_HIP_ERR_INVALID,
-                std::string(who) + ": the norms struct is not 8-byte aligned; "
-                                   "nothing was launched");
-  return SODA_HIP_OK;
-}
-
 int soda_hip_norms_zero(soda_hip_norms_handle_t* h, void* acc_dev,
                         void* stream) {
   if (!h || !acc_dev)
     return fail(SODA_HIP_ERR_INVALID, "norms_zero: NULL argument");
-  if (int rc = check_norms_struct(acc_dev, "norms_zero")) return rc;
+  if (int rc = check_struct_aligned(acc_dev, "norms", "norms_zero"))
+    return rc;
   HIP_TRY(hipSetDevice(h->device));
   return norms_zero(h, acc_dev, static_cast<hipStream_t>(stream));
 }
@@ -1953,13 +2036,15 @@ int soda_hip_norms_accumulate(soda_hip_norms_handle_t* h, const void* cur,
                               void* acc_dev, void* stream) {
   if (!h || !cur || !prev || !extent || !lo || !hi || !acc_dev)
     return fail(SODA_HIP_ERR_INVALID, "norms_accumulate: NULL argument");
-  if (int rc = check_norms_struct(acc_dev, "norms_accumulate")) return rc;
+  if (int rc = check_struct_aligned(acc_dev, "norms", "norms_accumulate"))
+    return rc;
   HIP_TRY(hipSetDevice(h->device));
   return norms_accumulate(h, cur, prev, extent, lo, hi, acc_dev,
                           static_cast<hipStream_t>(stream));
 }
 
 // what both norms runs ask of a program, a handle and the struct
+// (acc_dev null: of the program and the handle only)
 static int check_norms_run(const soda_hip_program* p,
                            const soda_hip_norms_handle* h,
                            void* const* outputs, const int32_t* extent,
@@ -1978,20 +2063,8 @@ static int check_norms_run(const soda_hip_program* p,
                                      "type (one struct holds one kind of "
                                      "units); nothing was launched");
   if (!acc_dev) return SODA_HIP_OK;
-  if (int rc = check_norms_struct(acc_dev, who)) return rc;
-  uint64_t cells = 1;
-  for (int d = 0; d < plan.dim; ++d)
-    cells *= (uint64_t)(extent[d] > 0 ? extent[d] : 0);
-  const uintptr_t r0 = reinterpret_cast<uintptr_t>(acc_dev);
-  for (int o = 0; o < plan.num_outputs; ++o) {
-    const uintptr_t o0 = reinterpret_cast<uintptr_t>(outputs[o]);
-    if (outputs[o] && r0 < o0 + cells * plan.elem_size[plan.num_inputs + o] &&
-        o0 < r0 + sizeof(soda_hip_norms_t))
-      return fail(SODA_HIP_ERR_INVALID,
-                  std::string(who) + ": the norms struct overlaps an output; "
-                                     "nothing was launched");
-  }
-  return SODA_HIP_OK;
+  return check_run_struct(plan, outputs, extent, acc_dev,
+                          sizeof(soda_hip_norms_t), "norms", who);
 }
 
 int soda_hip_run_device_norms(soda_hip_program_t* p,
@@ -2000,17 +2073,14 @@ int soda_hip_run_device_norms(soda_hip_program_t* p,
                               int32_t iterate, void* acc_dev, void* stream_) {
   if (!p || !h || !outputs || !inputs || !extent || !acc_dev)
     return fail(SODA_HIP_ERR_INVALID, "run_device_norms: NULL argument");
-  p->last_res_mode = 0;
-  p->last_res_fused = 0;
-  p->last_launches = 0;
-  p->last_fused = 0;
+  reset_last_run(p);
   if (int rc = check_norms_run(p, h, outputs, extent, acc_dev,
                                "run_device_norms"))
     return rc;
-  ResidualRun run = {acc_dev, iterate};
-  run.norms = h;
-  return run_core(p, outputs, inputs, extent, nullptr, nullptr, iterate,
-                  stream_, -1, nullptr, 1, &run);
+  const ResidualRun run = {acc_dev, iterate, h};
+  RunRequest rq = {outputs, inputs, extent, iterate, stream_};
+  rq.residual = &run;
+  return run_core(p, rq);
 }
 
 int soda_hip_run_device_until_norm(soda_hip_program_t* p,
@@ -2032,74 +2102,21 @@ int soda_hip_run_device_until_norm(soda_hip_program_t* p,
   if (int rc = check_norms_run(p, h, outputs, extent, nullptr,
                                "run_device_until_norm"))
     return rc;
-  const soda_hip_plan_t& plan = p->plan;
-  hipStream_t stream = static_cast<hipStream_t>(stream_);
-  HIP_TRY(hipSetDevice(p->device));
-  hipStreamCaptureStatus capture = hipStreamCaptureStatusNone;
-  if (hipStreamIsCapturing(stream, &capture) != hipSuccess) {
-    (void)hipGetLastError();
-    capture = hipStreamCaptureStatusNone;
-  }
-  if (capture != hipStreamCaptureStatusNone)
-    return fail(SODA_HIP_ERR_INVALID,
-                "run_device_until_norm: synchronous, not for a stream that is "
-                "being captured; nothing was launched");
-  int64_t cells = 1;
-  for (int d = 0; d < plan.dim; ++d) {
-    if (extent[d] < 1)
-      return fail(SODA_HIP_ERR_INVALID, "run_device_until_norm: extent < 1");
-    cells *= extent[d];
-  }
-  if (int rc = ensure(p->until_norms, sizeof(soda_hip_norms_t))) return rc;
-  const int out0 = plan.num_inputs;
-  std::vector<const void*> in(inputs,
-                              inputs + plan.num_inputs + plan.num_params);
-  std::vector<void*> tmp(plan.num_outputs, nullptr);
-  std::vector<void*> own(outputs, outputs + plan.num_outputs);
   soda_hip_norms_t host;
-  memset(&host, 0, sizeof host);
-  int32_t done = 0;
-  bool in_tmp = false;
-  for (int32_t chunk = 0; done < max_iterate; ++chunk) {
-    const int32_t n =
-        max_iterate - done < check_every ? max_iterate - done : check_every;
-    in_tmp = chunk % 2 == 1;
-    if (in_tmp && !tmp[0])
-      for (int o = 0; o < plan.num_outputs; ++o) {
-        if (int rc = ensure(p->until_tmp[o],
-                            (size_t)cells * plan.elem_size[out0 + o]))
-          return rc;
-        tmp[o] = p->until_tmp[o].ptr;
-      }
-    void* const* dst = in_tmp ? tmp.data() : own.data();
-    ResidualRun run = {p->until_norms.ptr, done + n};
-    run.norms = h;
-    if (int rc = run_core(p, dst, in.data(), extent, nullptr, nullptr, n,
-                          stream_, -1, nullptr, 1, &run))
-      return rc;
-    HIP_TRY(hipMemcpyAsync(&host, p->until_norms.ptr, sizeof host,
-                           hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
-    done += n;
-    // the next chunk continues from this one's result; the caller's inputs
-    // were read by the first chunk only
-    for (int j = 0; j < plan.num_inputs; ++j) in[j] = dst[j];
+  auto converged = [&](bool* stop) {
     double norm = 0.0;
     if (soda_hip_norms_value(&host, which, &norm))
       return fail(SODA_HIP_ERR_RUNTIME,
                   "run_device_until_norm: the struct fetched is of no kind");
     if (which == SODA_HIP_NORMS_WHICH_L2) norm = sqrt(norm);
-    if (host.unordered == 0 && host.infinite == 0 && norm <= tol) break;
-  }
-  if (in_tmp) {
-    for (int o = 0; o < plan.num_outputs; ++o)
-      HIP_TRY(hipMemcpyAsync(outputs[o], tmp[o],
-                             (size_t)cells * plan.elem_size[out0 + o],
-                             hipMemcpyDeviceToDevice, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
-  }
+    *stop = host.unordered == 0 && host.infinite == 0 && norm <= tol;
+    return (int)SODA_HIP_OK;
+  };
+  if (int rc = run_until(p, "run_device_until_norm", outputs, inputs, extent,
+                         max_iterate, check_every, h, &host, sizeof host,
+                         converged, iterations_done, stream_))
+    return rc;
   if (result_host) *result_host = host;
-  if (iterations_done) *iterations_done = done;
   return SODA_HIP_OK;
 }
 
@@ -2109,44 +2126,15 @@ int soda_hip_run_device_batch(soda_hip_program_t* p, void* const* outputs,
   if (!p || !outputs || !inputs || !extent)
     return fail(SODA_HIP_ERR_INVALID, "run_device_batch: NULL argument");
   if (int rc = check_batch(batch, "run_device_batch")) return rc;
-  const soda_hip_plan_t& plan = p->plan;
-  if (!plan.batched)
+  if (!p->plan.batched)
     return fail(SODA_HIP_ERR_INVALID,
                 "run_device_batch: the program's kernels are not batched "
                 "(build it with LowerOptions.batch / sodac --hip-batch); "
                 "nothing was launched");
-  // no tensor may overlap another, each `batch` items long (inputs may share:
-  // they are only read)
-  int64_t cells = batch;
-  for (int d = 0; d < plan.dim; ++d) {
-    if (extent[d] < 1)
-      return fail(SODA_HIP_ERR_INVALID, "run_device_batch: extent < 1");
-    cells *= extent[d];
-  }
-  const int out0 = plan.num_inputs;
-  auto overlap = [&](const void* a, int sa, const void* b, int sb) {
-    const uintptr_t a0 = reinterpret_cast<uintptr_t>(a);
-    const uintptr_t b0 = reinterpret_cast<uintptr_t>(b);
-    return a0 < b0 + (uint64_t)cells * plan.elem_size[sb] &&
-           b0 < a0 + (uint64_t)cells * plan.elem_size[sa];
-  };
-  for (int o = 0; o < plan.num_outputs; ++o) {
-    if (!outputs[o])
-      return fail(SODA_HIP_ERR_INVALID, "run_device_batch: NULL output");
-    for (int i = 0; i < plan.num_inputs; ++i)
-      if (inputs[i] && overlap(outputs[o], out0 + o, inputs[i], i))
-        return fail(SODA_HIP_ERR_INVALID,
-                    "run_device_batch: an output overlaps an input (each "
-                    "tensor is `batch` items long; in-place runs are not "
-                    "supported)");
-    for (int q = 0; q < o; ++q)
-      if (overlap(outputs[o], out0 + o, outputs[q], out0 + q))
-        return fail(SODA_HIP_ERR_INVALID,
-                    "run_device_batch: two outputs overlap (each tensor is "
-                    "`batch` items long)");
-  }
-  return run_core(p, outputs, inputs, extent, nullptr, nullptr, iterate,
-                  stream_, -1, nullptr, batch);
+  // (no tensor may overlap another, each `batch` items long: run_core checks)
+  RunRequest rq = {outputs, inputs, extent, iterate, stream_};
+  rq.batch = batch;
+  return run_core(p, rq);
 }
 
 int soda_hip_run_device_window(soda_hip_program_t* p, void* const* outputs,
@@ -2154,8 +2142,34 @@ int soda_hip_run_device_window(soda_hip_program_t* p, void* const* outputs,
                                const int32_t* extent, const int32_t* origin,
                                const int32_t* global_extent, int32_t iterate,
                                void* stream_) {
-  return run_core(p, outputs, inputs, extent, origin, global_extent, iterate,
-                  stream_, -1, nullptr);
+  RunRequest rq = {outputs, inputs, extent, iterate, stream_};
+  rq.origin = origin;
+  rq.global_extent = global_extent;
+  return run_core(p, rq);
+}
+
+static int slab_run(const soda_hip_slab_run_t* run, const int32_t* extent,
+                    int ax, SlabRun* out) {
+  if (run->keep_lo < 0 || run->keep_hi > extent[ax] ||
+      run->keep_lo >= run->keep_hi || run->reach_lo < 0 || run->reach_hi < 0)
+    return fail(SODA_HIP_ERR_INVALID,
+                "run_device_slab: [keep_lo, keep_hi) must be a non-empty range "
+                "of the last dimension, the reaches non-negative");
+  if (run->ghost_lo < 0 || run->ghost_hi < 0 || run->send_lo < 0 ||
+      run->send_hi < 0 || run->ghost_lo + run->ghost_hi > extent[ax] ||
+      run->send_lo > run->keep_hi - run->keep_lo ||
+      run->send_hi > run->keep_hi - run->keep_lo)
+    return fail(SODA_HIP_ERR_INVALID,
+                "run_device_slab: ghost / send rows out of range");
+  SlabRun& s = *out;
+  s.cone = {run->keep_lo, run->keep_hi, run->reach_lo, run->reach_hi};
+  s.ghost_lo = run->ghost_lo;
+  s.ghost_hi = run->ghost_hi;
+  s.send_lo = run->send_lo;
+  s.send_hi = run->send_hi;
+  s.ghosts_ready = static_cast<hipEvent_t>(run->ghosts_ready);
+  s.sendable = static_cast<hipEvent_t>(run->sendable);
+  return SODA_HIP_OK;
 }
 
 int soda_hip_run_device_cone(soda_hip_program_t* p, void* const* outputs,
@@ -2175,9 +2189,6 @@ int soda_hip_run_device_cone(soda_hip_program_t* p, void* const* outputs,
                                   global_extent, iterate, &run, stream_);
 }
 
-static int slab_run(const soda_hip_slab_run_t* run, const int32_t* extent,
-                    int ax, SlabRun* out);
-
 int soda_hip_run_device_slab(soda_hip_program_t* p, void* const* outputs,
                              const void* const* inputs, const int32_t* extent,
                              const int32_t* origin,
@@ -2187,8 +2198,11 @@ int soda_hip_run_device_slab(soda_hip_program_t* p, void* const* outputs,
     return fail(SODA_HIP_ERR_INVALID, "run_device_slab: NULL argument");
   SlabRun s;
   if (int rc = slab_run(run, extent, p->plan.dim - 1, &s)) return rc;
-  return run_core(p, outputs, inputs, extent, origin, global_extent, iterate,
-                  stream_, -1, &s);
+  RunRequest rq = {outputs, inputs, extent, iterate, stream_};
+  rq.origin = origin;
+  rq.global_extent = global_extent;
+  rq.slab = &s;
+  return run_core(p, rq);
 }
 
 int soda_hip_run_device_slab_residual(
@@ -2198,10 +2212,7 @@ int soda_hip_run_device_slab_residual(
     void* residual_dev, void* stream_) {
   if (!p || !outputs || !inputs || !extent || !run || !residual_dev)
     return fail(SODA_HIP_ERR_INVALID, "run_device_slab_residual: NULL argument");
-  p->last_res_mode = 0;
-  p->last_res_fused = 0;
-  p->last_launches = 0;
-  p->last_fused = 0;
+  reset_last_run(p);
   if (int rc = check_residual(p, outputs, extent, residual_dev,
                               "run_device_slab_residual"))
     return rc;
@@ -2213,8 +2224,12 @@ int soda_hip_run_device_slab_residual(
   SlabRun s;
   if (int rc = slab_run(run, extent, p->plan.dim - 1, &s)) return rc;
   const ResidualRun res = {residual_dev, box_iterate};
-  return run_core(p, outputs, inputs, extent, origin, global_extent, iterate,
-                  stream_, -1, &s, 1, &res);
+  RunRequest rq = {outputs, inputs, extent, iterate, stream_};
+  rq.origin = origin;
+  rq.global_extent = global_extent;
+  rq.slab = &s;
+  rq.residual = &res;
+  return run_core(p, rq);
 }
 
 int soda_hip_plan_residual_slab_box(const soda_hip_plan_t* plan,
@@ -2244,39 +2259,8 @@ int soda_hip_plan_residual_slab_box(const soda_hip_plan_t* plan,
   soda_hip_resbox_t box;
   residual_slab_box(*plan, global_extent, origin, extent, keep_lo, keep_hi,
                     iterate, &box);
-  for (int o = 0; o < plan->num_outputs; ++o)
-    for (int d = 0; d < plan->dim; ++d) {
-      lo[o * plan->dim + d] = box.lo[o][d];
-      hi[o * plan->dim + d] = box.hi[o][d];
-    }
+  flatten_box(*plan, box, lo, hi);
   return SODA_HIP_OK;
-}
-
-static int plan_launches_c(const soda_hip_plan_t* plan, const int32_t* extent,
-                           int32_t iterate, const soda_hip_slab_run_t* run,
-                           int32_t capacity, soda_hip_launch_info_t* launches,
-                           int32_t* count, int32_t* residual_mode);
-
-int soda_hip_plan_launches(const soda_hip_plan_t* plan, const int32_t* extent,
-                           int32_t iterate, const soda_hip_slab_run_t* run,
-                           int32_t capacity, soda_hip_launch_info_t* launches,
-                           int32_t* count) {
-  return plan_launches_c(plan, extent, iterate, run, capacity, launches, count,
-                         nullptr);
-}
-
-int soda_hip_plan_launches_residual(const soda_hip_plan_t* plan,
-                                    const int32_t* extent, int32_t iterate,
-                                    const soda_hip_slab_run_t* run,
-                                    int32_t capacity,
-                                    soda_hip_launch_info_t* launches,
-                                    int32_t* count, int32_t* mode) {
-  if (!mode) return fail(SODA_HIP_ERR_INVALID, "plan_launches: bad argument");
-  if (plan && !plan->residual.present)
-    return fail(SODA_HIP_ERR_UNSUPPORTED,
-                "plan_launches_residual: the plan has no residual");
-  return plan_launches_c(plan, extent, iterate, run, capacity, launches, count,
-                         mode);
 }
 
 // residual_mode != NULL: the launches of a run that takes a residual
@@ -2297,7 +2281,7 @@ static int plan_launches_c(const soda_hip_plan_t* plan, const int32_t* extent,
   if (run)
     if (int rc = slab_run(run, ext, plan->dim - 1, &s)) return rc;
   std::map<ExtentKey, ExtentPlan> cache;
-  const ExtentPlan* ep = nullptr;
+  ExtentPlan* ep = nullptr;
   if (int rc = extent_plan(*plan, &cache, ext, &ep)) return rc;
   int32_t per_pass[SODA_HIP_MAX_PASSES], total = 0;
   if (int rc = schedule(*plan, ep->model_ns, iterate, per_pass, &total)) return rc;
@@ -2322,28 +2306,26 @@ static int plan_launches_c(const soda_hip_plan_t* plan, const int32_t* extent,
   return SODA_HIP_OK;
 }
 
-static int slab_run(const soda_hip_slab_run_t* run, const int32_t* extent,
-                    int ax, SlabRun* out) {
-  if (run->keep_lo < 0 || run->keep_hi > extent[ax] ||
-      run->keep_lo >= run->keep_hi || run->reach_lo < 0 || run->reach_hi < 0)
-    return fail(SODA_HIP_ERR_INVALID,
-                "run_device_slab: [keep_lo, keep_hi) must be a non-empty range "
-                "of the last dimension, the reaches non-negative");
-  if (run->ghost_lo < 0 || run->ghost_hi < 0 || run->send_lo < 0 ||
-      run->send_hi < 0 || run->ghost_lo + run->ghost_hi > extent[ax] ||
-      run->send_lo > run->keep_hi - run->keep_lo ||
-      run->send_hi > run->keep_hi - run->keep_lo)
-    return fail(SODA_HIP_ERR_INVALID,
-                "run_device_slab: ghost / send rows out of range");
-  SlabRun& s = *out;
-  s.cone = {run->keep_lo, run->keep_hi, run->reach_lo, run->reach_hi};
-  s.ghost_lo = run->ghost_lo;
-  s.ghost_hi = run->ghost_hi;
-  s.send_lo = run->send_lo;
-  s.send_hi = run->send_hi;
-  s.ghosts_ready = static_cast<hipEvent_t>(run->ghosts_ready);
-  s.sendable = static_cast<hipEvent_t>(run->sendable);
-  return SODA_HIP_OK;
+int soda_hip_plan_launches(const soda_hip_plan_t* plan, const int32_t* extent,
+                           int32_t iterate, const soda_hip_slab_run_t* run,
+                           int32_t capacity, soda_hip_launch_info_t* launches,
+                           int32_t* count) {
+  return plan_launches_c(plan, extent, iterate, run, capacity, launches, count,
+                         nullptr);
+}
+
+int soda_hip_plan_launches_residual(const soda_hip_plan_t* plan,
+                                    const int32_t* extent, int32_t iterate,
+                                    const soda_hip_slab_run_t* run,
+                                    int32_t capacity,
+                                    soda_hip_launch_info_t* launches,
+                                    int32_t* count, int32_t* mode) {
+  if (!mode) return fail(SODA_HIP_ERR_INVALID, "plan_launches: bad argument");
+  if (plan && !plan->residual.present)
+    return fail(SODA_HIP_ERR_UNSUPPORTED,
+                "plan_launches_residual: the plan has no residual");
+  return plan_launches_c(plan, extent, iterate, run, capacity, launches, count,
+                         mode);
 }
 
 int soda_hip_program_calibrate(soda_hip_program_t* p, const int32_t* extent,
@@ -2429,23 +2411,26 @@ int soda_hip_program_calibrate_batch(soda_hip_program_t* p,
       ins.push_back(bufs[plan.num_inputs + plan.num_outputs + k].ptr);
     for (int o = 0; o < plan.num_outputs; ++o)
       outs.push_back(bufs[plan.num_inputs + o].ptr);
+    // `n` iterations by launches of pass i alone
+    auto run_pass = [&](int i, int32_t n) {
+      RunRequest rq = {outs.data(), ins.data(), key.data(), n, stream_};
+      rq.force_pass = i;
+      rq.batch = batch;
+      return run_core(p, rq);
+    };
     for (int round = 0; round < 2 && rc == SODA_HIP_OK; ++round)
       for (int i = 0; i < plan.num_passes && rc == SODA_HIP_OK; ++i)
-        rc = run_core(p, outs.data(), ins.data(), key.data(), nullptr, nullptr,
-                      plan.passes[i].fused_iters * launches, stream_, i,
-                      nullptr, batch);
+        rc = run_pass(i, plan.passes[i].fused_iters * launches);
     for (int round = 0; round < kTimedRounds && rc == SODA_HIP_OK; ++round)
       for (int i = 0; i < plan.num_passes && rc == SODA_HIP_OK; ++i) {
         const int32_t one = plan.passes[i].fused_iters;
         hipEvent_t* pair = &ev[2 * (round * plan.num_passes + i)];
-        rc = run_core(p, outs.data(), ins.data(), key.data(), nullptr, nullptr,
-                      one, stream_, i, nullptr, batch);
+        rc = run_pass(i, one);
         if (rc != SODA_HIP_OK) break;
         if (hipEventRecord(pair[0], stream) != hipSuccess)
           rc = fail(SODA_HIP_ERR_RUNTIME, "calibrate: hipEventRecord");
         if (rc != SODA_HIP_OK) break;
-        rc = run_core(p, outs.data(), ins.data(), key.data(), nullptr, nullptr,
-                      one * launches, stream_, i, nullptr, batch);
+        rc = run_pass(i, one * launches);
         if (rc == SODA_HIP_OK && hipEventRecord(pair[1], stream) != hipSuccess)
           rc = fail(SODA_HIP_ERR_RUNTIME, "calibrate: hipEventRecord");
       }

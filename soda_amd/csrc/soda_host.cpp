@@ -855,8 +855,11 @@ int run_banded(HostCall& c, int64_t band_rows, int64_t g_lo, int64_t g_hi) {
     // than the bands save, and synchronise in the middle of the pipeline)
     const bool was = p->calibrating;
     p->calibrating = true;
-    const int rc = run_core(p, outs.data(), ins.data(), lext, origin, gext,
-                            c.iterate, s_run, -1, &slab);
+    RunRequest rq = {outs.data(), ins.data(), lext, c.iterate, s_run};
+    rq.origin = origin;
+    rq.global_extent = gext;
+    rq.slab = &slab;
+    const int rc = run_core(p, rq);
     p->calibrating = was;
     if (rc) return rc;
     HIP_TRY(hipEventRecord(ev_run[buf], s_run));
@@ -968,7 +971,7 @@ int64_t choose_bands(HostCall& c, int64_t g_lo, int64_t g_hi) {
     ext[d] = d < c.dim ? c.extent[d] : 1;
     key[d] = ext[d];
   }
-  const ExtentPlan* ep = nullptr;
+  ExtentPlan* ep = nullptr;
   if (extent_plan(plan, &p->extents, ext, &ep)) return -1;
   auto it = p->measured.find(key);
   const std::vector<double>& pass_ns =

@@ -10,6 +10,7 @@
 
 #include <array>
 #include <cstdio>
+#include <cstring>
 #include <map>
 #include <string>
 #include <vector>
@@ -102,12 +103,11 @@ struct soda_hip_program {
   // ... and its partner in runs trimmed to a cone, which keep their
   // intermediate passes out of the caller's outputs (run_core)
   std::vector<soda_detail::DeviceBuffer> temps2;
-  // soda_hip_run_device_until: the arrays its chunks ping-pong through beside
-  // the caller's outputs (one per output), and the 32 bytes it fetches
+  // soda_hip_run_device_until[_norm]: the arrays its chunks ping-pong through
+  // beside the caller's outputs (one per output), and the struct it fetches
+  // (32 bytes of residual or a soda_hip_norms_t, whichever was asked for)
   std::vector<soda_detail::DeviceBuffer> until_tmp;
-  soda_detail::DeviceBuffer until_res;
-  // ... and the soda_hip_norms_t soda_hip_run_device_until_norm fetches
-  soda_detail::DeviceBuffer until_norms;
+  soda_detail::DeviceBuffer until_struct;
   // how the last soda_hip_run_device_residual took its residual (0 none,
   // 1 twin, 2 `<app>_residual`) and the fusion depth of its last pass
   int32_t last_res_mode = 0;
@@ -178,7 +178,7 @@ namespace soda_detail {
 // the counted box is that of (soda_hip_run_device_until runs chunk after
 // chunk: the box is the one after all iterations done so far; a slab run
 // between two exchanges: the iterations since the state was the caller's).
-// On a slab (run_core's `slab`, `origin`, `global_extent`) the box is the
+// On a slab (RunRequest's `slab`, `origin`, `global_extent`) the box is the
 // global grid's, cut to the slab's kept rows (soda_hip_plan_residual_slab_box)
 // `norms` != nullptr (soda_hip_run_device_norms): `dev` is a soda_hip_norms_t,
 // the run always ends in the one-iteration pass, and the handle's kernels run
@@ -189,15 +189,45 @@ struct ResidualRun {
   soda_hip_norms_handle* norms = nullptr;
 };
 
-// force_pass >= 0: use only that pass (calibration).  batch > 1: every
-// tensor holds that many grids of `extent`, one launch runs them all (a
-// batched plan, no slab: soda_hip_run_device_batch checks)
-int run_core(soda_hip_program* p, void* const* outputs,
-             const void* const* inputs, const int32_t* extent,
-             const int32_t* origin, const int32_t* global_extent,
-             int32_t iterate, void* stream, int force_pass,
-             const SlabRun* slab, int32_t batch = 1,
-             const ResidualRun* res = nullptr);
+// One run of a program on device arrays: `RunRequest rq = {outputs, inputs,
+// extent, iterate, stream};`, then whatever else the caller sets, by name.
+// origin / global_extent: the window's place in a larger grid (null: the
+// window is the grid).  force_pass >= 0: use only that pass (calibration).
+// batch > 1: every tensor holds that many grids of `extent`, one launch runs
+// them all (a batched plan, no slab: soda_hip_run_device_batch checks)
+struct RunRequest {
+  void* const* outputs;
+  const void* const* inputs;
+  const int32_t* extent;
+  int32_t iterate;
+  void* stream;
+  const int32_t* origin = nullptr;
+  const int32_t* global_extent = nullptr;
+  int force_pass = -1;
+  const SlabRun* slab = nullptr;
+  int32_t batch = 1;
+  const ResidualRun* residual = nullptr;
+};
+int run_core(soda_hip_program* p, const RunRequest& rq);
+
+// What run_core asks of the caller's addresses before anything is launched,
+// each tensor taken as the dense array of `cells` x `batch` cells the kernels
+// address: no output shares a byte with an input, a param array or another
+// output, and every tensor is aligned to min(16, vec x its cell size) for the
+// widest `vec` of the plan's kernels (a param array to one cell).  Looks at
+// the addresses only, never behind them.  bank_tensors: nothing is asked
+// (soda_hip_program::bank_tensors).
+int check_run_tensors(const soda_hip_plan_t& plan, bool bank_tensors,
+                      void* const* outputs, const void* const* inputs,
+                      int64_t cells, int32_t batch);
+
+// Has a run that stops on its residual converged?
+inline bool residual_converged(const soda_hip_residual_t& r, double tol,
+                               uint64_t int_tol) {
+  double max_float;
+  memcpy(&max_float, &r.max_float_bits, sizeof max_float);
+  return r.unordered == 0 && max_float <= tol && r.max_int <= int_tol;
+}
 
 inline std::map<ExtentKey, std::vector<double>>& measured_of(
     soda_hip_program* p, int32_t batch) {
@@ -245,7 +275,7 @@ int residual_order(const soda_hip_plan_t& plan,
 // remembered in `cache` (which holds one batch size's: extents_of)
 int extent_plan(const soda_hip_plan_t& plan,
                 std::map<ExtentKey, ExtentPlan>* cache, const int32_t* ext,
-                const ExtentPlan** out, int32_t batch = 1);
+                ExtentPlan** out, int32_t batch = 1);
 
 // launches of every pass for `iterate` iterations by the given pass times
 int schedule(const soda_hip_plan_t& plan, const std::vector<double>& pass_ns,

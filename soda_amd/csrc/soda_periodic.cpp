@@ -257,8 +257,7 @@ int run_chunks(soda_hip_periodic* h, void* const* outputs,
     const bool to_out = ((chunks - 1 - c) % 2) == 0;
     for (int o = 0; o < nout; ++o)
       dst[o] = to_out ? outputs[o] : h->pong[o].ptr;
-    if (int rc = run_core(p, dst.data(), src.data(), h->t.p, nullptr, nullptr,
-                          n, stream, -1, nullptr))
+    if (int rc = run_core(p, {dst.data(), src.data(), h->t.p, n, stream}))
       return rc;
     if (int rc = wrap_launch(h, kFill, dst.data(), dst.data(), elem.data(),
                              nout, static_cast<hipStream_t>(stream)))

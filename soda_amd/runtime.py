@@ -10,6 +10,7 @@ the loaded code object and runs it on host or device arrays.
 There is no CPU fallback: a missing library, a failed JIT or a missing GPU
 raises `util.BackendError`.
 """
+import contextlib
 import ctypes
 import dataclasses
 import hashlib
@@ -1704,98 +1705,72 @@ class Program:
     if len(outputs) != len(st.output_names) or len(inputs) != len(
         st.input_names) + len(st.param_stmts):
       raise util.InputError('wrong number of tensors')
+    exchange = ghosts is not None or sends is not None or bool(
+        ghosts_ready or sendable)
+    slab = exchange or keep is not None or origin is not None or \
+        global_extent is not None
+    if norms is not None and (residual is not None or batch is not None or
+                              slab or box_iterate is not None):
+      raise util.InputError(
+          'run_device: norms are taken on whole grids: not together with '
+          'residual / batch / keep / ghosts / sends / origin')
+    if residual is not None and batch is not None:
+      raise util.InputError(
+          'run_device: no residual of a batch (a residual per item is a '
+          'reduction of its own)')
+    if batch is not None and slab:
+      raise util.InputError(
+          'run_device: a batched run is a run on whole grids: no keep / '
+          'ghosts / sends / origin')
+    if residual is not None and not slab and box_iterate is not None and \
+        int(box_iterate) != iterate:
+      raise util.InputError(
+          'run_device: box_iterate is for a slab run (origin / keep / '
+          'ghosts / sends)')
+    lib = self._lib
     outs = (ctypes.c_void_p * len(outputs))(*outputs)
     ins = (ctypes.c_void_p * len(inputs))(*inputs)
     ext = (ctypes.c_int32 * len(extent))(*extent)
-    if norms is not None:
-      if residual is not None or batch is not None or keep is not None or \
-          ghosts is not None or sends is not None or origin is not None or \
-          global_extent is not None or ghosts_ready or sendable or \
-          box_iterate is not None:
-        raise util.InputError(
-            'run_device: norms are taken on whole grids: not together with '
-            'residual / batch / keep / ghosts / sends / origin')
-      check(
-          self._lib.soda_hip_run_device_norms(
-              self._handle, self.norms()._handle, outs, ins, ext, iterate,
-              ctypes.c_void_p(norms), ctypes.c_void_p(stream)),
-          'running `%s` with norms' % st.app_name)
-      return
-    if residual is not None:
-      if batch is not None:
-        raise util.InputError(
-            'run_device: no residual of a batch (a residual per item is a '
-            'reduction of its own)')
-      if keep is not None or ghosts is not None or sends is not None or \
-          origin is not None or global_extent is not None or ghosts_ready or \
-          sendable:
-        keep = keep if keep is not None else (0, extent[-1])
-        reach_lo, reach_hi = st.reach_along(st.dim - 1)
-        run = SlabRun(int(keep[0]), int(keep[1]), reach_lo, reach_hi,
-                      *(int(v) for v in (ghosts or (0, 0))),
-                      *(int(v) for v in (sends or (0, 0))),
-                      ghosts_ready or None, sendable or None)
-        org = (ctypes.c_int32 * len(extent))(*(origin or [0] * len(extent)))
-        gext = (ctypes.c_int32 * len(extent))(*(global_extent or extent))
-        check(
-            self._lib.soda_hip_run_device_slab_residual(
-                self._handle, outs, ins, ext, org, gext, iterate,
-                iterate if box_iterate is None else int(box_iterate),
-                ctypes.byref(run), ctypes.c_void_p(residual),
-                ctypes.c_void_p(stream)),
-            'running `%s` on a slab with a residual' % st.app_name)
-        return
-      if box_iterate is not None and int(box_iterate) != iterate:
-        raise util.InputError(
-            'run_device: box_iterate is for a slab run (origin / keep / '
-            'ghosts / sends)')
-      check(
-          self._lib.soda_hip_run_device_residual(
-              self._handle, outs, ins, ext, iterate, ctypes.c_void_p(residual),
-              ctypes.c_void_p(stream)),
-          'running `%s` with a residual' % st.app_name)
-      return
-    if batch is not None:
-      if keep is not None or ghosts is not None or sends is not None or \
-          origin is not None or global_extent is not None or ghosts_ready or \
-          sendable:
-        raise util.InputError(
-            'run_device: a batched run is a run on whole grids: no keep / '
-            'ghosts / sends / origin')
-      check(
-          self._lib.soda_hip_run_device_batch(self._handle, outs, ins, ext,
-                                              int(batch), iterate,
-                                              ctypes.c_void_p(stream)),
-          'running `%s` on a batch of %d' % (st.app_name, batch))
-      return
     org = (ctypes.c_int32 * len(extent))(*(origin or [0] * len(extent)))
     gext = (ctypes.c_int32 * len(extent))(*(global_extent or extent))
-    if ghosts is not None or sends is not None or ghosts_ready or sendable:
-      keep = keep if keep is not None else (0, extent[-1])
+    whole = (0, extent[-1])
+    if slab:
       reach_lo, reach_hi = st.reach_along(st.dim - 1)
-      run = SlabRun(int(keep[0]), int(keep[1]), reach_lo, reach_hi,
+      keep_lo, keep_hi = keep if keep is not None else whole
+      run = SlabRun(int(keep_lo), int(keep_hi), reach_lo, reach_hi,
                     *(int(v) for v in (ghosts or (0, 0))),
                     *(int(v) for v in (sends or (0, 0))),
                     ghosts_ready or None, sendable or None)
-      check(
-          self._lib.soda_hip_run_device_slab(
-              self._handle, outs, ins, ext, org, gext, iterate,
-              ctypes.byref(run), ctypes.c_void_p(stream)),
-          'running `%s`' % st.app_name)
-      return
-    if keep is not None and tuple(keep) != (0, extent[-1]):
-      reach_lo, reach_hi = st.reach_along(st.dim - 1)
-      check(
-          self._lib.soda_hip_run_device_cone(
-              self._handle, outs, ins, ext, org, gext, iterate, int(keep[0]),
-              int(keep[1]), reach_lo, reach_hi, ctypes.c_void_p(stream)),
-          'running `%s`' % st.app_name)
-      return
-    check(
-        self._lib.soda_hip_run_device_window(self._handle, outs, ins, ext, org,
-                                             gext, iterate,
-                                             ctypes.c_void_p(stream)),
-        'running `%s`' % st.app_name)
+    window = (self._handle, outs, ins, ext, org, gext, iterate)
+    on = ctypes.c_void_p(stream)
+    what = 'running `%s`' % st.app_name
+    # the entry of the C ABI the arguments ask for
+    if norms is not None:
+      entry, what = lib.soda_hip_run_device_norms, what + ' with norms'
+      args = (self._handle, self.norms()._handle, outs, ins, ext, iterate,
+              ctypes.c_void_p(norms), on)
+    elif residual is not None and slab:
+      entry = lib.soda_hip_run_device_slab_residual
+      what += ' on a slab with a residual'
+      args = window + (iterate if box_iterate is None else int(box_iterate),
+                       ctypes.byref(run), ctypes.c_void_p(residual), on)
+    elif residual is not None:
+      entry, what = lib.soda_hip_run_device_residual, what + ' with a residual'
+      args = (self._handle, outs, ins, ext, iterate,
+              ctypes.c_void_p(residual), on)
+    elif batch is not None:
+      entry = lib.soda_hip_run_device_batch
+      what += ' on a batch of %d' % batch
+      args = (self._handle, outs, ins, ext, int(batch), iterate, on)
+    elif exchange:
+      entry = lib.soda_hip_run_device_slab
+      args = window + (ctypes.byref(run), on)
+    elif keep is not None and tuple(keep) != whole:
+      entry = lib.soda_hip_run_device_cone
+      args = window + (run.keep_lo, run.keep_hi, reach_lo, reach_hi, on)
+    else:
+      entry, args = lib.soda_hip_run_device_window, window + (on,)
+    check(entry(*args), what)
 
   def residual(self, ptr: int, stream: int = 0) -> Residual:
     """The struct a `run_device(..., residual=ptr)` left at device address
@@ -1873,42 +1848,15 @@ class Program:
     first = np.asarray(inputs[st.input_names[0]])
     extent = tuple(first.shape[::-1])
     self._check_extent(extent)
-    host_in = []
-    for n, t in zip(st.input_names, st.input_types):
-      arr = np.ascontiguousarray(inputs[n])
-      if arr.dtype != np.dtype(t.np_name):
-        raise util.InputError('expected dtype %s, got %s' % (t.np_name,
-                                                             arr.dtype))
-      if arr.shape != first.shape:
-        raise util.InputError('all tensors must share one shape')
-      host_in.append(arr)
-    for pstmt in st.param_stmts:        # param arrays follow, C order
-      arr = np.ascontiguousarray(inputs[pstmt.name]).reshape(-1)
-      if arr.dtype != np.dtype(pstmt.haoda_type.np_name) or \
-          arr.size != st.param_elems(pstmt):
-        raise util.InputError('param %s must be %d x %s' % (
-            pstmt.name, st.param_elems(pstmt), pstmt.haoda_type.np_name))
-      host_in.append(arr)
+    host_in = _host_inputs(st, inputs, first.shape)
     dense = [np.empty(first.shape, dtype=np.dtype(t.np_name))
              for t in st.output_types]
-    dev_in, dev_out = [], []
     raw = ResidualStruct() if norm is None else NormsStruct()
     done = ctypes.c_int32(0)
-    try:
-      for arr in host_in:
-        ptr = ctypes.c_void_p()
-        check(lib.soda_hip_malloc(self.device, arr.nbytes, ctypes.byref(ptr)),
-              'run_until: allocating an input')
-        dev_in.append(ptr)
-        check(lib.soda_hip_memcpy_h2d(ptr, arr.ctypes.data, arr.nbytes, None),
-              'run_until: copy in')
-      for arr in dense:
-        ptr = ctypes.c_void_p()
-        check(lib.soda_hip_malloc(self.device, arr.nbytes, ctypes.byref(ptr)),
-              'run_until: allocating an output')
-        dev_out.append(ptr)
-      outs = (ctypes.c_void_p * len(dev_out))(*[p.value for p in dev_out])
-      ins = (ctypes.c_void_p * len(dev_in))(*[p.value for p in dev_in])
+    with _staged(lib, self.device, host_in, dense, 'run_until') as (dev_in,
+                                                                     dev_out):
+      outs = (ctypes.c_void_p * len(dev_out))(*dev_out)
+      ins = (ctypes.c_void_p * len(dev_in))(*dev_in)
       ext = (ctypes.c_int32 * len(extent))(*extent)
       if norm is None:
         check(
@@ -1925,21 +1873,10 @@ class Program:
                 int(check_every), {'l1': NORMS_L1, 'l2': NORMS_L2}[norm],
                 float(tol), ctypes.byref(raw), ctypes.byref(done), None),
             'running `%s` until its %s norm is small' % (st.app_name, norm))
-      for arr, ptr in zip(dense, dev_out):
-        check(lib.soda_hip_memcpy_d2h(arr.ctypes.data, ptr, arr.nbytes, None),
-              'run_until: copy out')
+      _copy_out(lib, dense, dev_out, 'run_until')
       check(lib.soda_hip_stream_synchronize(None), 'run_until: synchronize')
-    finally:
-      for ptr in dev_in + dev_out:
-        lib.soda_hip_free(self.device, ptr)
-    result = {}
-    for n, arr in zip(st.output_names, dense):
-      lo, hi = clipped_box(st.valid_box(extent, n, done.value), extent)
-      box = tuple(slice(l, h) for l, h in zip(lo, hi))[::-1]
-      result[n] = np.zeros_like(arr)
-      result[n][box] = arr[box]
-    return result, done.value, (Residual.from_struct(raw) if norm is None
-                                else raw)
+    return (_valid_boxes(st, extent, done.value, dense), done.value,
+            Residual.from_struct(raw) if norm is None else raw)
 
   def last_split(self) -> int:
     """Passes of the last run launched in two parts around a halo exchange."""
@@ -1992,30 +1929,11 @@ class Program:
     self._check_extent(extent)
     dim = st.dim
     keep = []
-
-    def describe(arr, np_name):
-      if arr.dtype != np.dtype(np_name):
-        raise util.InputError('expected dtype %s, got %s' % (np_name, arr.dtype))
-      if arr.shape != first.shape:
-        raise util.InputError('all tensors must share one shape')
-      item = arr.dtype.itemsize
-      strides = [s // item for s in arr.strides[::-1]]
-      if any(s * item != b for s, b in zip(strides, arr.strides[::-1])):
-        raise util.InputError('strides must be whole elements')
-      ext = (ctypes.c_int32 * dim)(*extent)
-      strd = (ctypes.c_int32 * dim)(*strides)
-      mn = (ctypes.c_int32 * dim)(*([0] * dim))
-      keep.extend((ext, strd, mn, arr))
-      return HostTensor(arr.ctypes.data, ext, strd, mn)
-
-    in_list = [describe(np.asarray(inputs[n]), t.np_name)
+    in_list = [_host_tensor(np.asarray(inputs[n]), t.np_name, first.shape, dim,
+                            keep)
                for n, t in zip(st.input_names, st.input_types)]
     for pstmt in st.param_stmts:        # param arrays follow, C order
-      arr = np.ascontiguousarray(inputs[pstmt.name]).reshape(-1)
-      if arr.dtype != np.dtype(pstmt.haoda_type.np_name) or \
-          arr.size != st.param_elems(pstmt):
-        raise util.InputError('param %s must be %d x %s' % (
-            pstmt.name, st.param_elems(pstmt), pstmt.haoda_type.np_name))
+      arr = _host_param(st, inputs, pstmt)
       keep.append(arr)
       in_list.append(HostTensor(arr.ctypes.data, None, None, None))
     ins = (HostTensor * len(in_list))(*in_list)
@@ -2026,7 +1944,7 @@ class Program:
       else:
         result[n] = np.zeros(first.shape, dtype=np.dtype(t.np_name))
     outs = (HostTensor * len(st.output_names))(*[
-        describe(result[n], t.np_name)
+        _host_tensor(result[n], t.np_name, first.shape, dim, keep)
         for n, t in zip(st.output_names, st.output_types)
     ])
     lo, hi = [], []
@@ -2063,50 +1981,15 @@ class Program:
     first = np.asarray(inputs[st.input_names[0]])
     extent = tuple(first.shape[::-1])
     self._check_extent(extent)
-    host_in = []
-    for n, t in zip(st.input_names, st.input_types):
-      arr = np.ascontiguousarray(inputs[n])
-      if arr.dtype != np.dtype(t.np_name):
-        raise util.InputError('expected dtype %s, got %s' % (t.np_name,
-                                                             arr.dtype))
-      if arr.shape != first.shape:
-        raise util.InputError('all tensors must share one shape')
-      host_in.append(arr)
-    for pstmt in st.param_stmts:        # param arrays follow, C order
-      arr = np.ascontiguousarray(inputs[pstmt.name]).reshape(-1)
-      if arr.dtype != np.dtype(pstmt.haoda_type.np_name) or \
-          arr.size != st.param_elems(pstmt):
-        raise util.InputError('param %s must be %d x %s' % (
-            pstmt.name, st.param_elems(pstmt), pstmt.haoda_type.np_name))
-      host_in.append(arr)
+    host_in = _host_inputs(st, inputs, first.shape)
     result = {n: np.empty(first.shape, dtype=np.dtype(t.np_name))
               for n, t in zip(st.output_names, st.output_types)}
-    dev_in, dev_out = [], []
-    with self.periodic(extent, refill_every) as per:
-      try:
-        for arr in host_in:
-          ptr = ctypes.c_void_p()
-          check(lib.soda_hip_malloc(self.device, arr.nbytes,
-                                    ctypes.byref(ptr)),
-                'run_periodic: allocating an input')
-          dev_in.append(ptr)
-          check(lib.soda_hip_memcpy_h2d(ptr, arr.ctypes.data, arr.nbytes,
-                                        None), 'run_periodic: copy in')
-        for arr in result.values():
-          ptr = ctypes.c_void_p()
-          check(lib.soda_hip_malloc(self.device, arr.nbytes,
-                                    ctypes.byref(ptr)),
-                'run_periodic: allocating an output')
-          dev_out.append(ptr)
-        per.run_device([p.value for p in dev_out], [p.value for p in dev_in],
-                       iterate)
-        for arr, ptr in zip(result.values(), dev_out):
-          check(lib.soda_hip_memcpy_d2h(arr.ctypes.data, ptr, arr.nbytes,
-                                        None), 'run_periodic: copy out')
-      finally:
-        lib.soda_hip_stream_synchronize(None)
-        for ptr in dev_in + dev_out:
-          lib.soda_hip_free(self.device, ptr)
+    dense = list(result.values())
+    with self.periodic(extent, refill_every) as per, \
+        _staged(lib, self.device, host_in, dense, 'run_periodic',
+                synchronize=True) as (dev_in, dev_out):
+      per.run_device(dev_out, dev_in, iterate)
+      _copy_out(lib, dense, dev_out, 'run_periodic')
     return result
 
   def run_batch(self, inputs: Dict[str, 'numpy.ndarray'],
@@ -2127,53 +2010,93 @@ class Program:
     batch = int(first.shape[0])
     extent = tuple(first.shape[:0:-1])
     self._check_extent(extent)
-    host_in = []
-    for n, t in zip(st.input_names, st.input_types):
-      arr = np.ascontiguousarray(inputs[n])
-      if arr.dtype != np.dtype(t.np_name):
-        raise util.InputError('expected dtype %s, got %s' % (t.np_name,
-                                                             arr.dtype))
-      if arr.shape != first.shape:
-        raise util.InputError('all tensors must share one shape')
-      host_in.append(arr)
-    for pstmt in st.param_stmts:        # param arrays follow, C order
-      arr = np.ascontiguousarray(inputs[pstmt.name]).reshape(-1)
-      if arr.dtype != np.dtype(pstmt.haoda_type.np_name) or \
-          arr.size != st.param_elems(pstmt):
-        raise util.InputError('param %s must be %d x %s' % (
-            pstmt.name, st.param_elems(pstmt), pstmt.haoda_type.np_name))
-      host_in.append(arr)
+    host_in = _host_inputs(st, inputs, first.shape)
     dense = [np.empty(first.shape, dtype=np.dtype(t.np_name))
              for t in st.output_types]
-    dev_in, dev_out = [], []
-    try:
-      for arr in host_in:
-        ptr = ctypes.c_void_p()
-        check(lib.soda_hip_malloc(self.device, arr.nbytes, ctypes.byref(ptr)),
-              'run_batch: allocating an input')
-        dev_in.append(ptr)
-        check(lib.soda_hip_memcpy_h2d(ptr, arr.ctypes.data, arr.nbytes, None),
-              'run_batch: copy in')
-      for arr in dense:
-        ptr = ctypes.c_void_p()
-        check(lib.soda_hip_malloc(self.device, arr.nbytes, ctypes.byref(ptr)),
-              'run_batch: allocating an output')
-        dev_out.append(ptr)
-      self.run_device([p.value for p in dev_out], [p.value for p in dev_in],
-                      extent, iterate, batch=batch)
-      for arr, ptr in zip(dense, dev_out):
-        check(lib.soda_hip_memcpy_d2h(arr.ctypes.data, ptr, arr.nbytes, None),
-              'run_batch: copy out')
-    finally:
-      for ptr in dev_in + dev_out:
-        lib.soda_hip_free(self.device, ptr)
-    result = {}
-    for n, arr in zip(st.output_names, dense):
-      lo, hi = clipped_box(st.valid_box(extent, n, iterate), extent)
-      box = (slice(None),) + tuple(slice(l, h) for l, h in zip(lo, hi))[::-1]
-      result[n] = np.zeros_like(arr)
-      result[n][box] = arr[box]
-    return result
+    with _staged(lib, self.device, host_in, dense, 'run_batch') as (dev_in,
+                                                                     dev_out):
+      self.run_device(dev_out, dev_in, extent, iterate, batch=batch)
+      _copy_out(lib, dense, dev_out, 'run_batch')
+    return _valid_boxes(st, extent, iterate, dense, batched=True)
+
+
+def _host_param(st, inputs, pstmt):
+  """The param array of `pstmt` among `inputs`, contiguous and flat (C
+  order)."""
+  import numpy as np
+  arr = np.ascontiguousarray(inputs[pstmt.name]).reshape(-1)
+  if arr.dtype != np.dtype(pstmt.haoda_type.np_name) or \
+      arr.size != st.param_elems(pstmt):
+    raise util.InputError('param %s must be %d x %s' % (
+        pstmt.name, st.param_elems(pstmt), pstmt.haoda_type.np_name))
+  return arr
+
+
+def _host_inputs(st, inputs, shape):
+  """What a staged run copies in, contiguous: the input tensors of `inputs`,
+  each of `shape`, then the param arrays (C order)."""
+  import numpy as np
+  host_in = []
+  for n, t in zip(st.input_names, st.input_types):
+    arr = np.ascontiguousarray(inputs[n])
+    if arr.dtype != np.dtype(t.np_name):
+      raise util.InputError('expected dtype %s, got %s' % (t.np_name,
+                                                           arr.dtype))
+    if arr.shape != shape:
+      raise util.InputError('all tensors must share one shape')
+    host_in.append(arr)
+  return host_in + [_host_param(st, inputs, p) for p in st.param_stmts]
+
+
+@contextlib.contextmanager
+def _staged(lib, device: int, host_in, host_out, what: str,
+            synchronize: bool = False):
+  """Device arrays for the numpy arrays `host_in` (copied in) and `host_out`
+  (not touched): yields (input addresses, output addresses) and frees them all
+  on the way out -- `synchronize`: behind a wait for the null stream.  `what`
+  names the caller in the error texts."""
+  dev_in, dev_out = [], []
+  try:
+    for arr in host_in:
+      ptr = ctypes.c_void_p()
+      check(lib.soda_hip_malloc(device, arr.nbytes, ctypes.byref(ptr)),
+            what + ': allocating an input')
+      dev_in.append(ptr)
+      check(lib.soda_hip_memcpy_h2d(ptr, arr.ctypes.data, arr.nbytes, None),
+            what + ': copy in')
+    for arr in host_out:
+      ptr = ctypes.c_void_p()
+      check(lib.soda_hip_malloc(device, arr.nbytes, ctypes.byref(ptr)),
+            what + ': allocating an output')
+      dev_out.append(ptr)
+    yield [p.value for p in dev_in], [p.value for p in dev_out]
+  finally:
+    if synchronize:
+      lib.soda_hip_stream_synchronize(None)
+    for ptr in dev_in + dev_out:
+      lib.soda_hip_free(device, ptr)
+
+
+def _copy_out(lib, host_out, dev_out, what: str) -> None:
+  for arr, ptr in zip(host_out, dev_out):
+    check(lib.soda_hip_memcpy_d2h(arr.ctypes.data, ctypes.c_void_p(ptr),
+                                  arr.nbytes, None), what + ': copy out')
+
+
+def _valid_boxes(st, extent, iterate: int, dense, batched: bool = False):
+  """{output name: zeros, but for the output's valid box after `iterate`
+  iterations, which is taken from its array in `dense`}.  `batched`: the
+  arrays have a leading axis of items, each cut alike."""
+  import numpy as np
+  result = {}
+  for n, arr in zip(st.output_names, dense):
+    lo, hi = clipped_box(st.valid_box(extent, n, iterate), extent)
+    box = tuple(slice(l, h) for l, h in zip(lo, hi))[::-1]
+    if batched:
+      box = (slice(None),) + box
+    result[n] = np.zeros_like(arr)
+    result[n][box] = arr[box]
+  return result
 
 
 def _host_tensor(arr, np_name: str, shape, dim: int, keep: list):
@@ -2311,11 +2234,7 @@ class Group:
                             keep)
                for n, t in zip(st.input_names, st.input_types)]
     for pstmt in st.param_stmts:
-      arr = np.ascontiguousarray(inputs[pstmt.name]).reshape(-1)
-      if arr.dtype != np.dtype(pstmt.haoda_type.np_name) or \
-          arr.size != st.param_elems(pstmt):
-        raise util.InputError('param %s must be %d x %s' % (
-            pstmt.name, st.param_elems(pstmt), pstmt.haoda_type.np_name))
+      arr = _host_param(st, inputs, pstmt)
       keep.append(arr)
       tensors.append(HostTensor(arr.ctypes.data, None, None, None))
     arr_t = (HostTensor * len(tensors))(*tensors)

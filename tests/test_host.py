@@ -242,6 +242,24 @@ def test_independent_wire_hosts_against_the_kernel_contract(tmp_path, main,
       run.stdout + run.stderr)
 
 
+def test_run_tensor_checks_under_a_sanitizer(tmp_path):
+  """tests/host/run_checks_main.cpp: the overlap and alignment rules every
+  device entry applies before it launches (check_run_tensors, soda_internal.h)
+  on made-up addresses -- tensors back to back, an output on an input, one byte
+  into an input, a param array or another output, layouts that collide only as
+  a batch, every alignment the rule distinguishes, bank tensors -- status and
+  text of each.  Its own main, the library's sources, ASan + UBSan (`make
+  run_checks_asan`); no GPU, nothing loaded into Python."""
+  out = str(tmp_path)
+  subprocess.run(['make', '-C', os.path.join(ROOT, 'soda_amd', 'csrc'),
+                  'run_checks_asan', 'OUT=' + out], check=True,
+                 capture_output=True)
+  run = subprocess.run([os.path.join(out, 'run_checks_asan')],
+                       capture_output=True, text=True, timeout=300)
+  assert run.returncode == 0 and run.stdout.startswith(
+      'run tensor checks: clean'), run.stdout + run.stderr
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize('main,soda', WIRE_HOSTS)
 def test_wire_kernels_under_independent_hosts(built, tmp_path, main, soda):
