@@ -44,9 +44,12 @@ compile the same C expression text with -ffp-contract=off.
 Layout of the package: module.py (Module, descriptors, the device runtime
 text), march.py (`march2d` / `march3d`), ldswin.py, tile3d.py, direct.py; this
 file holds the options and `lower()`, which picks the family and the shape
-(DESIGN.md section 4.3).
+ in named steps: check_options, _lower_ldswin, _derive,
+_add_march_passes (the shape from _one_iteration_shape, every kernel a
+march_config added by _add_march) or `direct`, _add_tile3d_passes.
 """
 import dataclasses
+import itertools
 import os
 from typing import Dict, Optional, Sequence, Union
 
@@ -120,7 +123,7 @@ class LowerOptions:
   # default_pipe(fusion depth)
   pipe: Optional[int] = None
   pipe_rows: int = 2
-  # estimated VGPRs a marching shape may need before the ladder in lower()
+  # estimated VGPRs a marching shape may need before _one_iteration_shape
   # moves on to a leaner one (None: REG_BUDGET)
   reg_budget: Optional[int] = None
   stamps: bool = False
@@ -229,6 +232,16 @@ class LowerOptions:
 NARROW_STRIP_OPS = (48, 128)
 
 
+def ops_per_cell(stencil: core.Stencil) -> int:
+  """Arithmetic per cell of one iteration AS WRITTEN (the rewrites of _derive
+  fold and split statements; what the shape choice wants to know is how much
+  the program computes)."""
+  from soda_amd import ir as _ir
+  return sum(_ir.op_count(s.stmt.expr) +
+             sum(_ir.op_count(l.expr) for l in s.stmt.let)
+             for s in stencil.ordered_stages)
+
+
 def prefers_narrow_strips(stencil: core.Stencil) -> bool:
   """One iteration per launch of a 2-D program that computes for 50-130
   operations per fp32 cell (denoise2d: 55): the kernel is bound by neither
@@ -240,20 +253,16 @@ def prefers_narrow_strips(stencil: core.Stencil) -> bool:
   profiles/r05_denoise_shapes.jsonl, one process; sustained over 900 launches
   each, alternating: 163.6 against 151.8 us, r05_denoise_sustained.json).
   Above the band a program goes through `ldswin` or takes 2 rows in flight
-  (lower()); below it the loads are what a wave waits for.  fp32 cells only:
-  that is what was measured.  runtime.resolve_options applies it where the
-  caller fixed neither the cells per lane nor the prefetch depth."""
+  (_one_iteration_shape); below it the loads are what a wave waits for.  fp32
+  cells only: that is what was measured.  runtime.resolve_options applies it
+  where the caller fixed neither the cells per lane nor the prefetch depth."""
   if os.environ.get('SODA_HIP_NARROW', '1') == '0':
     return False
   if stencil.dim != 2 or stencil.iterate != 1:
     return False
   if any(str(t) != 'float' for t in stencil.symbol_table.values()):
     return False
-  from soda_amd import ir as _ir
-  work = sum(_ir.op_count(s.stmt.expr) +
-             sum(_ir.op_count(l.expr) for l in s.stmt.let)
-             for s in stencil.ordered_stages)
-  return NARROW_STRIP_OPS[0] <= work < NARROW_STRIP_OPS[1]
+  return NARROW_STRIP_OPS[0] <= ops_per_cell(stencil) < NARROW_STRIP_OPS[1]
 
 
 def default_pipe(fused_iters: int) -> int:
@@ -297,11 +306,13 @@ def default_prefetch(fused_iters: int, lane_shift: str = 'dpp') -> int:
   return 2
 
 
-def lower(stencil: core.Stencil, opts: Optional[LowerOptions] = None) -> Module:
-  """Builds the module: passes for every requested fusion depth plus a
-  1-iteration pass (always present: the scheduler needs it for remainders)."""
-  opts = (opts or LowerOptions()).resolved(
-      stencil.dim, iterated=stencil.iterate > 1)
+# ---------------------------------------------------------------------------
+# the steps of lower(), in the order it takes them
+# ---------------------------------------------------------------------------
+
+def check_options(stencil: core.Stencil, opts: LowerOptions) -> None:
+  """Refuses what no family can build, before anything is built; `opts` are
+  resolved.  A call that breaks two rules hears the first one here."""
   if opts.strategy not in STRATEGIES:
     raise util.SemanticError('strategy %r: one of %s' %
                              (opts.strategy, ', '.join(STRATEGIES)))
@@ -315,8 +326,8 @@ def lower(stencil: core.Stencil, opts: Optional[LowerOptions] = None) -> Module:
       not isinstance(opts.pipe_rows, int) or opts.pipe_rows < 1 or
       opts.pipe_rows & (opts.pipe_rows - 1)):
     # (refused here, whatever the strategy: the marching generator's own
-    # refusal is caught by the ladder below, which would drop the fused depth
-    # and hand back the one-iteration kernel without a word)
+    # refusal is caught by _add_march, and _add_march_passes would drop the
+    # fused depth and hand back the one-iteration kernel without a word)
     raise util.SemanticError(
         'pipe_rows %r: the row steps per barrier of a stage-pipelined block '
         '(pipe %d) are a power of two' % (opts.pipe_rows, opts.pipe))
@@ -333,30 +344,27 @@ def lower(stencil: core.Stencil, opts: Optional[LowerOptions] = None) -> Module:
                              % opts.strategy)
   if opts.strategy == 'tile3d' and tile3d_supported(stencil):
     raise util.SemanticError('tile3d: %s' % tile3d_supported(stencil))
-  # arithmetic per cell of one iteration AS WRITTEN (the rewrites below fold
-  # and split statements; what the shape ladder wants to know is how much the
-  # program computes)
-  from soda_amd import ir as _ir
-  work = sum(_ir.op_count(s.stmt.expr) +
-             sum(_ir.op_count(l.expr) for l in s.stmt.let)
-             for s in stencil.ordered_stages)
-  # the module's program from here on is a DERIVED one: same tensors the
-  # caller sees (inputs, outputs, their windows and boxes), other locals
-  def same_boxes(other: core.Stencil) -> bool:
-    """A rewrite must leave the outputs' windows alone: they decide the valid
-    box and, under `border: preserve`, which cells an iteration computes.  A
-    tensor's window includes the tensor's own cell (core.iteration_boxes), so
-    folding a local that is STORED off-centre can widen what its consumer may
-    compute (`loc(0, -1) = in(1, 0); out(0, 0) = loc(0, -1)`: row 0 of `out`
-    needs row -1 of `loc`; folded, it needs nothing outside the grid -- found
-    by tools/fuzz_scan.py options, a preserved row computed instead)."""
-    mine, theirs = stencil.iteration_boxes(), other.iteration_boxes()
-    return all(mine[o] == theirs[o] for o in stencil.output_names)
 
-  # wide 2-D windows through an LDS row ring (ldswin.py): a whole stage per
-  # thread, so every pointwise local -- the groups of a rebalanced sum included
-  # -- is a sub-expression there.  On request, and by itself where it pays
-  # (contrast: one input, 17 x 17 taps, 393 operations per cell)
+
+def same_boxes(a: core.Stencil, b: core.Stencil) -> bool:
+  """A rewrite must leave the outputs' windows alone: they decide the valid
+  box and, under `border: preserve`, which cells an iteration computes.  A
+  tensor's window includes the tensor's own cell (core.iteration_boxes), so
+  folding a local that is STORED off-centre can widen what its consumer may
+  compute (`loc(0, -1) = in(1, 0); out(0, 0) = loc(0, -1)`: row 0 of `out`
+  needs row -1 of `loc`; folded, it needs nothing outside the grid -- found
+  by tools/fuzz_scan.py options, a preserved row computed instead)."""
+  mine, theirs = a.iteration_boxes(), b.iteration_boxes()
+  return all(mine[o] == theirs[o] for o in a.output_names)
+
+
+def _lower_ldswin(stencil: core.Stencil,
+                  opts: LowerOptions) -> Optional[Module]:
+  """Wide 2-D windows through an LDS row ring (ldswin.py): a whole stage per
+  thread, so every pointwise local -- the groups of a rebalanced sum included
+  -- is a sub-expression there.  On request, and by itself where it pays
+  (contrast: one input, 17 x 17 taps, 393 operations per cell).  None where
+  `auto` does not take the family; an explicit `ldswin` hears why not."""
   if opts.strategy in ('auto', 'ldswin') and stencil.dim == 2 and \
       os.environ.get('SODA_HIP_LDSWIN', '1') != '0' and \
       (opts.strategy == 'ldswin' or ldswin_candidate(stencil)):
@@ -366,7 +374,7 @@ def lower(stencil: core.Stencil, opts: Optional[LowerOptions] = None) -> Module:
     whole = pointwise.inline_pointwise(
         stencil, fold_groups=True,
         max_ops=1 << 20 if opts.strategy == 'ldswin' else 1 << 13)
-    if same_boxes(whole) and (
+    if same_boxes(stencil, whole) and (
         (opts.strategy == 'ldswin' and ldswin_supported(whole) is None) or
         (opts.strategy == 'auto' and ldswin_pays(whole) and
          (opts.vec is None or opts.vec % 4 == 0))):
@@ -383,16 +391,23 @@ def lower(stencil: core.Stencil, opts: Optional[LowerOptions] = None) -> Module:
       except util.SemanticError:
         # the ring does not fit LDS (window too tall / too wide): only an
         # explicit `ldswin` request hears about it, `auto` moves on to the
-        # marching / direct ladder with the program as written
+        # marching / direct kernels with the program as written
         if opts.strategy == 'ldswin':
           raise
   if opts.strategy == 'ldswin':
     raise util.SemanticError('ldswin: %s' % (
         ldswin_supported(stencil) or 'the program does not fold to one stage'))
+  return None
+
+
+def _derive(stencil: core.Stencil, opts: LowerOptions) -> core.Stencil:
+  """The program the marching / direct / tile3d kernels are built from, a
+  DERIVED one: same tensors the caller sees (inputs, outputs, their windows
+  and boxes), other locals."""
   if opts.inline:
     from soda_amd.optimization import pointwise
     folded = pointwise.inline_pointwise(stencil)
-    if same_boxes(folded):
+    if same_boxes(stencil, folded):
       stencil = folded
   if opts.windows:
     from soda_amd.optimization import windows
@@ -407,221 +422,254 @@ def lower(stencil: core.Stencil, opts: Optional[LowerOptions] = None) -> Module:
     # (the auxiliaries are tensors of the launch plan: a program that would
     # exceed the argument block's slots keeps its windows as written)
     if len(derived.symbol_table) + len(derived.param_stmts) <= MAX_TENSORS \
-        and same_boxes(derived):
+        and same_boxes(stencil, derived):
       stencil = derived
   # operations whose operand ranges the text proves: cheaper sequences with
   # the same bits (exact.py; the program as written unless one is enabled)
   from soda_amd.codegen.hip import exact
-  stencil = exact.specialize(stencil)
+  return exact.specialize(stencil)
+
+
+def peel_for(opts: LowerOptions, t: int) -> int:
+  """Trips of the warm-up the kernel of fusion depth `t` peels."""
+  if opts.peel is None:
+    return -1
+  if isinstance(opts.peel, dict):
+    return int(opts.peel.get(t, -1))
+  return int(opts.peel)
+
+
+def pipe_for(opts: LowerOptions, t: int) -> int:
+  """Waves that share the `t` fused iterations: what was asked for (else
+  default_pipe) where it divides them and the block is one wave otherwise,
+  else quietly 1."""
+  want = default_pipe(t) if opts.pipe is None else opts.pipe
+  ok = (want > 1 and t > 1 and t % want == 0 and
+        opts.waves_x * opts.waves_y == 1)
+  return want if ok else 1
+
+
+def shift_for(opts: LowerOptions, dim: int, t: int, xshare: int = 0) -> str:
+  """The lane shifts of the kernel of depth `t`: as asked, else DPP for blocks
+  of several waves (x-halo sharing, stage pipelines, waves_x / waves_y), else
+  default_lane_shift."""
+  if opts.lane_shift is not None:
+    return opts.lane_shift
+  if xshare or pipe_for(opts, t) > 1 or opts.waves_x * opts.waves_y != 1:
+    return 'dpp'
+  return default_lane_shift(t, dim)
+
+
+def march_config(opts: LowerOptions, stencil: core.Stencil, t: int, vec: int,
+                 pf: Optional[int], rows: Optional[int] = None,
+                 xshare: int = 0, xshare_block: int = 0) -> MarchConfig:
+  """The marching kernel of `t` fused iterations at `vec` cells per lane, `pf`
+  rows in flight (None: default_prefetch) and `rows` rows per 3-D tile."""
+  shift = shift_for(opts, stencil.dim, t, xshare or xshare_block)
+  if pf is None:
+    pf = default_prefetch(t, shift)
+  align = opts.align_lanes
+  if align is None:
+    out_bytes = min(o.size_in_bytes for o in stencil.output_types)
+    align = max(1, 64 // (vec * out_bytes)) if opts.nt_store else 1
+  cfg = MarchConfig(
+      fused_iters=t, vec=vec, chunk_rows=opts.chunk_rows or 64,
+      prefetch=pf, waves_x=opts.waves_x, waves_y=opts.waves_y,
+      nt_store=opts.nt_store, nt_load=opts.nt_load,
+      xcd_swizzle=opts.xcd_swizzle, edge_loads=opts.edge_loads,
+      tile_rows=rows or opts.tile_rows, lane_shift=shift,
+      min_waves=opts.min_waves, occupancy=opts.occupancy,
+      pipe=pipe_for(opts, t), pipe_rows=opts.pipe_rows, stamps=opts.stamps,
+      peel=peel_for(opts, t), align_lanes=align, xshare=xshare,
+      xshare_block=xshare_block,
+      xwindow=bool(opts.windows),
+      slide=bool(opts.windows) and SLIDING_SUMS,
+      banks=opts.banks, bank_lead=opts.bank_lead)
+  cfg.chunk_fixed = opts.chunk_rows is not None
+  return cfg
+
+
+def _fuse_depths(stencil: core.Stencil, opts: LowerOptions):
+  """Fusion depths of the marching kernels, deepest first: each requested
+  depth, clipped to the iteration count the program asks for (a 2-iteration
+  program gets a T=2 kernel, not T=4) and, in 3-D, to MAX_FUSE_3D: a tile of
+  rows x planes per tensor per fused iteration; two iterations still fit
+  (heat3d 512^3: 118-125 us per iteration at T=2, 260 VGPRs, against 194 us at
+  T=1; T=3 with 2 cells per lane: 129 us)."""
+  if opts.strategy == 'tile3d':
+    # the fused passes are tile3d's (_add_tile3d_passes); the marching family
+    # supplies the one-iteration pass, as under `auto`
+    return []
+  iterable = (len(stencil.input_names) == len(stencil.output_names) and
+              stencil.input_types == stencil.output_types)
+  cap = stencil.iterate
+  if stencil.dim == 3 and opts.strategy != 'march':
+    cap = min(cap, MAX_FUSE_3D)
+  if stencil.preserve_border and opts.strategy != 'march':
+    # every fused iteration also keeps the window of the tensor it preserves
+    # the border from: jacobi2d T=12 needs 186 VGPRs (2 waves per SIMD) and
+    # runs 96 iterations in 2.51 ms, T=8 in 2.04 ms (1.54 / 1.61 ms without
+    # preserve)
+    cap = min(cap, MAX_FUSE_PRESERVE)
+  return sorted({min(t, cap) for t in opts.fuse if iterable} - {0, 1},
+                reverse=True)
+
+
+def _one_iteration_shape(stencil: core.Stencil, opts: LowerOptions, work: int,
+                         budget: int):
+  """((cells per lane, prefetch depth, rows per tile) or None, the last
+  refusal or None) of the one-iteration kernel, which is mandatory.  Tall
+  windows (erosion and xcorr read 19 rows) or many live tensors may not fit
+  the register budget at the preferred shape: try shallower prefetch, then
+  fewer cells per lane, and take the first shape whose estimate stays within
+  `budget` (else the leanest, the earlier of two alike); None if the
+  generator refuses them all -- lower() then falls back to `direct` kernels,
+  or raises the refusal where `march` was asked for."""
+  # arithmetic per cell of one iteration (`work`): a program that computes
+  # for hundreds of instructions per cell has nothing to hide behind a deep
+  # prefetch queue and pays for its registers in resident waves (contrast,
+  # 393 operations per cell: 703 us at 8 rows in flight, 660 at 2)
+  first = default_prefetch(1) if stencil.dim == 2 and work < 128 else \
+      (2 if stencil.dim == 2 else 1)
+  pfs = [opts.prefetch] if opts.prefetch else [first, 2, 1]
+  pfs = sorted(set(pfs), reverse=True)
+  # (3-D: fewer rows per tile never paid -- denoise3d 512^3: 651 / 691 / 910
+  # us at 4 / 2 / 1 rows, 1 cell per lane -- so the tile height stays)
+  rows = opts.tile_rows
+  vecs = []
+  v = opts.vec or default_vec(stencil)
+  while v >= 1:
+    vecs.append(v)
+    v //= 2
+  leanest = None
+  last_error = None
+  for v, pf in itertools.product(vecs, pfs):
+    trial = Module(stencil, opts.banks, opts.batch)
+    try:
+      est = add_march_pass(
+          trial, march_config(opts, stencil, 1, v, pf, rows)).traffic_model[
+              'est_window_regs']
+    except util.SemanticError as e:
+      last_error = e
+      continue
+    if est <= budget:
+      return (v, pf, rows), last_error
+    if leanest is None or est < leanest[0]:
+      leanest = (est, v, pf, rows)
+  return (leanest[1:] if leanest else None), last_error
+
+
+def _append_march(mod: Module, cfg: MarchConfig, residual: bool) -> None:
+  add_march_pass(mod, cfg)
+  if residual:
+    # (a form or depth whose twin does not fit has none: the library then
+    # ends such a run in `<app>_residual`)
+    add_march_twin(mod, cfg)
+
+
+def _add_march(mod: Module, cfg: MarchConfig, residual: bool) -> bool:
+  """The marching pass of `cfg`, and its residual twin if asked for, or
+  nothing at all: False, with `mod` as it was, if the generator refuses."""
+  keep = (len(mod.kernels), len(mod.passes), len(mod.chunks))
+  try:
+    _append_march(mod, cfg, residual)
+  except util.SemanticError:
+    del mod.kernels[keep[0]:], mod.passes[keep[1]:], mod.chunks[keep[2]:]
+    return False
+  return True
+
+
+def _add_march_passes(mod: Module, stencil: core.Stencil, opts: LowerOptions,
+                      work: int) -> bool:
+  """The marching passes of every fusion depth that fits and of the one
+  iteration; False, and nothing added, if no one-iteration shape exists."""
+  shape, refusal = _one_iteration_shape(stencil, opts, work,
+                                        opts.reg_budget or REG_BUDGET)
+  if shape is None:
+    if opts.strategy == 'march':
+      raise refusal
+    return False
+  vec, pf1, rows1 = shape
+  # waves that cover a whole row side by side, sharing x-halos through LDS
+  share = 0
+  if opts.row_cells and opts.xshare is not False and \
+      (stencil.dim == 3 or opts.xshare) and opts.pipe in (None, 1):
+    share = -(-opts.row_cells // (64 * vec))
+    if share > (4 if opts.xshare is None else 16):
+      share = 0
+  # ... or a segment of it, on request (then instead of the whole row)
+  seg = opts.xshare_block or 0
+  if seg:
+    share = 0
+  for t in _fuse_depths(stencil, opts):
+    # (xshare, xshare_block) to try in turn; overlapping strips last
+    shared = [(0, seg)] if seg else ([(share, 0)] if share and t > 1 else [])
+    for xs, xb in shared + [(0, 0)]:
+      # a shape that does not fit: try without sharing; if the depth does not
+      # fit at all the scheduler uses the others
+      if _add_march(mod, march_config(opts, stencil, t, vec,
+                                      opts.prefetch or None, xshare=xs,
+                                      xshare_block=xb), opts.residual):
+        break
+  # (the one-iteration kernel shares x-halos only on request: measured)
+  done1 = bool((share or seg) and opts.xshare) and _add_march(
+      mod, march_config(opts, stencil, 1, vec, pf1, rows1, xshare=share,
+                        xshare_block=seg), opts.residual)
+  if not done1:
+    _append_march(mod, march_config(opts, stencil, 1, vec, pf1, rows1),
+                  opts.residual)
+  return True
+
+
+def _add_tile3d_passes(mod: Module, stencil: core.Stencil,
+                       opts: LowerOptions) -> None:
+  """One tile3d pass per requested depth, clipped to the iteration count only:
+  the planes live in LDS, MAX_FUSE_3D (registers) does not bind.  A depth whose
+  rings do not fit is dropped; an explicit request that ends with no fused
+  pass at all hears why."""
+  depths = sorted({min(t, stencil.iterate) for t in opts.fuse} - {0, 1},
+                  reverse=True)
+  refusal = None
+  built = 0
+  for t in depths:
+    try:
+      add_tile3d_pass(mod, t, tile_w=opts.tile3d_w, tile_h=opts.tile3d_h,
+                      waves=opts.tile3d_waves, chunk=opts.chunk_rows,
+                      nt_load=bool(opts.nt_load),
+                      nt_store=bool(opts.nt_store),
+                      xcd_swizzle=opts.xcd_swizzle)
+      built += 1
+    except util.SemanticError as e:
+      refusal = refusal or e
+  if not built:
+    raise refusal or util.SemanticError(
+        'tile3d: no fusion depth of 2 or more to build (iterate %d, fuse %s)'
+        % (stencil.iterate, list(opts.fuse)))
+
+
+def lower(stencil: core.Stencil, opts: Optional[LowerOptions] = None) -> Module:
+  """Builds the module: passes for every requested fusion depth plus a
+  1-iteration pass (always present: the scheduler needs it for remainders)."""
+  opts = (opts or LowerOptions()).resolved(
+      stencil.dim, iterated=stencil.iterate > 1)
+  check_options(stencil, opts)
+  mod = _lower_ldswin(stencil, opts)
+  if mod is not None:
+    return mod
+  work = ops_per_cell(stencil)       # of the program as written
+  stencil = _derive(stencil, opts)
   mod = Module(stencil, opts.banks, opts.batch, opts.residual)
   use_march = opts.strategy in ('auto', 'march', 'tile3d') and \
       march_supported(stencil) is None
   if opts.strategy == 'march' and not use_march:
     raise util.SemanticError('march: %s' % march_supported(stencil))
-  if use_march:
-    vec0 = opts.vec or default_vec(stencil)
-    iterable = (len(stencil.input_names) == len(stencil.output_names) and
-                stencil.input_types == stencil.output_types)
-    # Fusion depths: each requested depth, clipped to the iteration count the
-    # program asks for (a 2-iteration program gets a T=2 kernel, not T=4) and,
-    # in 3-D, to MAX_FUSE_3D: a tile of rows x planes per tensor per fused
-    # iteration; two iterations still fit (heat3d 512^3: 118-125 us per
-    # iteration at T=2, 260 VGPRs, against 194 us at T=1; T=3 with 2 cells per
-    # lane: 129 us).
-    cap = stencil.iterate
-    if stencil.dim == 3 and opts.strategy != 'march':
-      cap = min(cap, MAX_FUSE_3D)
-    if stencil.preserve_border and opts.strategy != 'march':
-      # every fused iteration also keeps the window of the tensor it preserves
-      # the border from: jacobi2d T=12 needs 186 VGPRs (2 waves per SIMD) and
-      # runs 96 iterations in 2.51 ms, T=8 in 2.04 ms (1.54 / 1.61 ms without
-      # preserve)
-      cap = min(cap, MAX_FUSE_PRESERVE)
-    depths = sorted({min(t, cap) for t in opts.fuse if iterable} - {0, 1},
-                    reverse=True)
-    if opts.strategy == 'tile3d':
-      # the fused passes are tile3d's (below); the marching family supplies
-      # the one-iteration pass, as under `auto`
-      depths = []
-
-    def peel_for(t: int) -> int:
-      if opts.peel is None:
-        return -1
-      if isinstance(opts.peel, dict):
-        return int(opts.peel.get(t, -1))
-      return int(opts.peel)
-
-    def pipe_for(t: int) -> int:
-      want = default_pipe(t) if opts.pipe is None else opts.pipe
-      ok = (want > 1 and t > 1 and t % want == 0 and
-            opts.waves_x * opts.waves_y == 1)
-      return want if ok else 1
-
-    out_bytes = min(t.size_in_bytes for t in stencil.output_types)
-
-    def shift_for(t: int, xshare: int = 0) -> str:
-      if opts.lane_shift is not None:
-        return opts.lane_shift
-      if xshare or pipe_for(t) > 1 or opts.waves_x * opts.waves_y != 1:
-        return 'dpp'
-      return default_lane_shift(t, stencil.dim)
-
-    def config(t: int, vec: int, pf: Optional[int],
-               rows: Optional[int] = None, xshare: int = 0,
-               xshare_block: int = 0) -> MarchConfig:
-      shift = shift_for(t, xshare or xshare_block)
-      if pf is None:
-        pf = default_prefetch(t, shift)
-      if opts.align_lanes is not None:
-        align = opts.align_lanes
-      else:
-        align = max(1, 64 // (vec * out_bytes)) if opts.nt_store else 1
-      cfg = MarchConfig(
-          fused_iters=t, vec=vec, chunk_rows=opts.chunk_rows or 64,
-          prefetch=pf, waves_x=opts.waves_x, waves_y=opts.waves_y,
-          nt_store=opts.nt_store, nt_load=opts.nt_load,
-          xcd_swizzle=opts.xcd_swizzle, edge_loads=opts.edge_loads,
-          tile_rows=rows or opts.tile_rows, lane_shift=shift,
-          min_waves=opts.min_waves, occupancy=opts.occupancy,
-          pipe=pipe_for(t), pipe_rows=opts.pipe_rows, stamps=opts.stamps,
-          peel=peel_for(t), align_lanes=align, xshare=xshare,
-          xshare_block=xshare_block,
-          xwindow=bool(opts.windows),
-          slide=bool(opts.windows) and SLIDING_SUMS,
-          banks=opts.banks, bank_lead=opts.bank_lead)
-      cfg.chunk_fixed = opts.chunk_rows is not None
-      return cfg
-
-    # The one-iteration kernel is mandatory.  Tall windows (erosion and xcorr
-    # read 19 rows) or many live tensors may not fit the register budget at
-    # the preferred shape: try shallower prefetch, then fewer cells per lane,
-    # and take the first shape whose estimate stays
-    # within the register budget (else the leanest); only if none exists fall
-    # back to `direct` kernels.
-    budget = opts.reg_budget or REG_BUDGET
-    # arithmetic per cell of one iteration: a program that computes for
-    # hundreds of instructions per cell has nothing to hide behind a deep
-    # prefetch queue and pays for its registers in resident waves (contrast,
-    # 393 operations per cell: 703 us at 8 rows in flight, 660 at 2)
-    first = default_prefetch(1) if stencil.dim == 2 and work < 128 else \
-        (2 if stencil.dim == 2 else 1)
-    pfs = [opts.prefetch] if opts.prefetch else [first, 2, 1]
-    pfs = sorted(set(pfs), reverse=True)
-    # (3-D: fewer rows per tile never paid -- denoise3d 512^3: 651 / 691 / 910
-    # us at 4 / 2 / 1 rows, 1 cell per lane -- so the tile height stays)
-    rows_list = [opts.tile_rows]
-    vecs = []
-    v = vec0
-    while v >= 1:
-      vecs.append(v)
-      v //= 2
-    chosen = None
-    last_error = None
-    for v in vecs:
-      for rows in rows_list:
-        for pf in pfs:
-          trial = Module(stencil, opts.banks, opts.batch)
-          try:
-            est = add_march_pass(trial, config(1, v, pf, rows)).traffic_model[
-                'est_window_regs']
-          except util.SemanticError as e:
-            last_error = e
-            continue
-          if chosen is None or est < chosen[0]:
-            chosen = (est, v, pf, rows)
-          if est <= budget:
-            break
-        if chosen and chosen[0] <= budget:
-          break
-      if chosen and chosen[0] <= budget:
-        break
-    if chosen is None:
-      if opts.strategy == 'march':
-        raise last_error
-      use_march = False
-    else:
-      _, vec, pf1, rows1 = chosen
-      # waves that cover a whole row side by side, sharing x-halos through LDS
-      share = 0
-      if opts.row_cells and opts.xshare is not False and \
-          (stencil.dim == 3 or opts.xshare) and opts.pipe in (None, 1):
-        share = -(-opts.row_cells // (64 * vec))
-        if share > (4 if opts.xshare is None else 16):
-          share = 0
-      # ... or a segment of it, on request (then instead of the whole row)
-      seg = opts.xshare_block or 0
-      if seg:
-        share = 0
-      for t in depths:
-        keep = (len(mod.kernels), len(mod.passes), len(mod.chunks))
-        # (xshare, xshare_block) to try in turn; overlapping strips last
-        if seg:
-          forms = [(0, seg), (0, 0)]
-        elif share and t > 1:
-          forms = [(share, 0), (0, 0)]
-        else:
-          forms = [(0, 0)]
-        for xs, xb in forms:
-          try:
-            cfg = config(t, vec, opts.prefetch or None, xshare=xs,
-                         xshare_block=xb)
-            add_march_pass(mod, cfg)
-            if opts.residual:
-              # (a form or depth whose twin does not fit has none: the
-              # library then ends such a run in `<app>_residual`)
-              add_march_twin(mod, cfg)
-            break
-          except util.SemanticError:
-            # this shape does not fit: try without sharing; if the depth does
-            # not fit at all the scheduler uses the others
-            del mod.kernels[keep[0]:], mod.passes[keep[1]:], \
-                mod.chunks[keep[2]:]
-      # (the one-iteration kernel shares x-halos only on request: measured)
-      done1 = False
-      if (share or seg) and opts.xshare:
-        keep = (len(mod.kernels), len(mod.passes), len(mod.chunks))
-        try:
-          cfg = config(1, vec, pf1, rows1, xshare=share, xshare_block=seg)
-          add_march_pass(mod, cfg)
-          if opts.residual:
-            add_march_twin(mod, cfg)
-          done1 = True
-        except util.SemanticError:
-          del mod.kernels[keep[0]:], mod.passes[keep[1]:], mod.chunks[keep[2]:]
-      if not done1:
-        cfg = config(1, vec, pf1, rows1)
-        add_march_pass(mod, cfg)
-        if opts.residual:
-          add_march_twin(mod, cfg)
-  if not use_march:
+  if not (use_march and _add_march_passes(mod, stencil, opts, work)):
     if opts.banks:
       raise util.SemanticError(
           'banks: `direct` kernels read and write dense arrays')
     add_direct_pass(mod, opts.vec or 1)
   if opts.strategy == 'tile3d':
-    # one pass per requested depth, clipped to the iteration count only: the
-    # planes live in LDS, MAX_FUSE_3D (registers) does not bind.  A depth whose
-    # rings do not fit is dropped; an explicit request that ends with no fused
-    # pass at all hears why
-    depths = sorted({min(t, stencil.iterate) for t in opts.fuse} - {0, 1},
-                    reverse=True)
-    refusal = None
-    built = 0
-    for t in depths:
-      try:
-        add_tile3d_pass(mod, t, tile_w=opts.tile3d_w, tile_h=opts.tile3d_h,
-                        waves=opts.tile3d_waves, chunk=opts.chunk_rows,
-                        nt_load=bool(opts.nt_load),
-                        nt_store=bool(opts.nt_store),
-                        xcd_swizzle=opts.xcd_swizzle)
-        built += 1
-      except util.SemanticError as e:
-        refusal = refusal or e
-    if not built:
-      raise refusal or util.SemanticError(
-          'tile3d: no fusion depth of 2 or more to build (iterate %d, fuse %s)'
-          % (stencil.iterate, list(opts.fuse)))
+    _add_tile3d_passes(mod, stencil, opts)
   if opts.residual:
     residual.add_residual_kernel(mod)
   return mod
-
