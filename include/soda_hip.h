@@ -73,7 +73,9 @@ extern "C" {
  * _value / _host / _create / _destroy / _zero / _accumulate,
  * soda_hip_run_device_norms and soda_hip_run_device_until_norm; and periodic
  * domains -- soda_hip_wrap_host, soda_hip_periodic_plan / _create / _destroy /
- * _info / _fill / _run_padded / _run_device. */
+ * _info / _fill / _run_padded / _run_device; and bordered domains --
+ * soda_hip_extend_host, soda_hip_border_plan / _create / _destroy / _info /
+ * _fill / _run_padded / _run_device with soda_hip_border_desc_t. */
 #define SODA_HIP_ABI_VERSION 9
 #define SODA_HIP_MAX_DIM 4
 #define SODA_HIP_MAX_TENSORS 16
@@ -305,7 +307,8 @@ int soda_hip_device_count(int* count);
  * check their mirrors: 0 kargs, 1 kernel_desc, 2 pass_desc, 3 plan,
  * 4 host_tensor, 5 stream_desc, 6 slab_run, 7 group_desc, 8 slab_info,
  * 9 group_stats, 10 launch_info, 11 residual, 12 resbox, 14 norms,
- * 15 periodic_desc, 16 periodic_info; 0 for anything else (13 among them). */
+ * 15 periodic_desc, 16 periodic_info, 17 border_desc; 0 for anything else
+ * (13 among them). */
 size_t soda_hip_sizeof(int which);
 
 /* -- JIT: HIP source text -> gfx950 code object (hiprtc; needs no GPU) ---- */
@@ -906,6 +909,114 @@ int soda_hip_periodic_run_device(soda_hip_periodic_t* handle,
                                  void* const* outputs,
                                  const void* const* inputs, int32_t iterate,
                                  void* stream);
+
+/* -- bordered domains: a border mode per dimension --------- */
+/* The padded arrays, handle and entries of the block above with another rule
+ * for the ghost frame.  Each dimension d has a mode; with g = ghost_lo[d] and
+ * j = i - g, padded index i takes interior index g + m(j) along d:
+ *   WRAP       j mod N                                   (numpy `wrap`)
+ *   CLAMP      min(max(j, 0), N - 1)                     (`edge`)
+ *   MIRROR     t = j mod 2N;  t < N ? t : 2N - 1 - t     (`symmetric`)
+ *   MIRROR101  N == 1: 0; else t = j mod (2N - 2);
+ *              t < N ? t : 2N - 2 - t                    (`reflect`)
+ *   CONSTANT   none: a cell with j outside [0, N) takes the tensor's constant
+ * (`mod` the mathematical modulo; a frame wider than the domain bounces more
+ * than once).  The map is separable: a cell outside in ANY constant dimension
+ * takes the constant, every other cell the interior cell given by the maps of
+ * all dimensions at once.  An array whose ghost cells all hold that is
+ * EXTENDED.  A run of `iterate` iterations lets every iteration see its inputs
+ * extended over the window of ONE iteration: only a wrapped ghost evolves into
+ * the wrap of the evolved interior, so with any other mode in any dimension
+ * the frame is refilled after every iteration (refill_every resolves to 1).
+ * With every dimension WRAP the request is the torus above, at its own
+ * refill_every, bit for bit.
+ * Not served on a bordered domain: residuals, norms, run_until, slabs, groups,
+ * ranks, batches, the wire format, `border: preserve`. */
+#define SODA_HIP_BORDER_WRAP 0
+#define SODA_HIP_BORDER_CLAMP 1
+#define SODA_HIP_BORDER_MIRROR 2
+#define SODA_HIP_BORDER_MIRROR101 3
+#define SODA_HIP_BORDER_CONSTANT 4
+typedef struct soda_hip_border_desc {
+  soda_hip_periodic_desc_t domain;     /* extent, refill_every (0 or 1 unless
+                                          every mode is WRAP), the ghosts of
+                                          refill_every iterations, preserve,
+                                          not_iterable: as above */
+  int32_t mode[SODA_HIP_MAX_DIM];      /* SODA_HIP_BORDER_* per dimension */
+  int32_t reserved;
+  uint64_t constant[SODA_HIP_MAX_TENSORS];  /* per INPUT tensor: the cell's bit
+                                          pattern in the low bytes.  Output o's
+                                          ghost takes the constant of input o,
+                                          the input it replaces when the
+                                          program iterates.  Bits are moved,
+                                          never computed with */
+} soda_hip_border_desc_t;
+/* The fill on a host array, in plain C++ (no GPU, no allocation):
+ * soda_hip_wrap_host with a mode per dimension and one constant. */
+int soda_hip_extend_host(void* array, int32_t elem_bytes, int32_t dim,
+                         const int32_t* extent, const int32_t* ghost_lo,
+                         const int32_t* ghost_hi, const int32_t* modes,
+                         uint64_t constant);
+/* soda_hip_periodic_plan for a bordered domain.  Pure function.  With every
+ * mode WRAP it IS soda_hip_periodic_plan on desc->domain.  Otherwise
+ * refill_every resolves to 1, every chunk is 1 iteration, and on top of that
+ * function's refusals:
+ *   SODA_HIP_ERR_INVALID      a mode that is none of SODA_HIP_BORDER_*;
+ *                             refill_every > 1 with a mode other than WRAP. */
+int soda_hip_border_plan(const soda_hip_plan_t* plan,
+                         const soda_hip_border_desc_t* desc, int32_t iterate,
+                         soda_hip_periodic_info_t* info, int32_t capacity,
+                         int32_t* chunks, int32_t* count);
+/* A handle over `program` for ONE bordered domain.  code[i] / code_size[i]:
+ * the code object of the EXTEND module (codegen/hip/extend.py) of 1 << i byte
+ * cells and the program's dimension count, i = 0..3; needed for every cell
+ * size among the program's inputs and outputs, NULL elsewhere.  All scratch of
+ * the handle is allocated here.  A refusal (soda_hip_border_plan's, or a
+ * program on wire-format banks: SODA_HIP_ERR_UNSUPPORTED) launches nothing
+ * and allocates nothing.  The handle must be destroyed before its program. */
+typedef struct soda_hip_periodic soda_hip_border_t;  /* opaque: the handle of
+                                          the block above, which keeps its
+                                          modes */
+int soda_hip_border_create(soda_hip_program_t* program,
+                           const soda_hip_border_desc_t* desc,
+                           const void* const* code, const size_t* code_size,
+                           soda_hip_border_t** handle);
+int soda_hip_border_destroy(soda_hip_border_t* handle);
+int soda_hip_border_info(soda_hip_border_t* handle,
+                         soda_hip_periodic_info_t* info);
+/* The primitive: refills the ghost frame of `count` caller-owned padded device
+ * arrays in place, array i with the cells and the constant of the program's
+ * output i (count <= num_outputs), each aligned to its cell size.  One launch
+ * per cell size among them -- one in all for a program of one cell type.
+ * Reads interior cells only, writes ghost cells only.  Asynchronous on
+ * `stream`, never allocates, capturable as it stands. */
+int soda_hip_border_fill(soda_hip_border_t* handle, void* const* arrays,
+                         int32_t count, void* stream);
+/* `iterate` iterations on PADDED device arrays; the state stays padded and
+ * device-resident across calls.  `inputs` (the num_inputs tensors, then the
+ * param arrays, which pass through unchanged) arrive EXTENDED, `outputs` leave
+ * extended, the inputs are never written.  Chunks of k iterations (the last
+ * may be shorter) go through soda_hip_run_device on P, a fill behind each;
+ * they ping-pong between `outputs` and one scratch set of the handle so that
+ * the last chunk lands in `outputs`.  The device entry contract holds on the
+ * padded arrays.  Under "Streams, scratch, graphs": asynchronous on `stream`,
+ * never allocates in the handle; the PROGRAM's own scratch is sized for P by
+ * the first call like any soda_hip_run_device on P (and that call calibrates,
+ * where the program does), after which the call can be captured.  One queue:
+ * the handle shares its program's.  SODA_HIP_ERR_INVALID, nothing launched:
+ * iterate < 1, iterate > 1 on a program that cannot iterate. */
+int soda_hip_border_run_padded(soda_hip_border_t* handle, void* const* outputs,
+                               const void* const* inputs, int32_t iterate,
+                               void* stream);
+/* The same on DENSE domain arrays of N: the inputs are padded into scratch
+ * (every cell, ghosts included), the loop above runs on scratch, the interior
+ * is cropped into `outputs`.  The device entry contract of soda_hip_run_device
+ * holds on the dense arrays -- overlap, alignment, inputs never written, no
+ * byte outside the outputs -- and so does "Streams, scratch, graphs" as for
+ * the entry above.  Every cell of every output is defined. */
+int soda_hip_border_run_device(soda_hip_border_t* handle, void* const* outputs,
+                               const void* const* inputs, int32_t iterate,
+                               void* stream);
 
 /* Replaces soda::app::<app>(): host arrays described by (ptr, extent, stride,
  * min) per tensor, inputs then outputs; copies in, runs, copies the outputs

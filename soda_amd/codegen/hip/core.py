@@ -13,6 +13,8 @@ opencl.py:55-142).  This module slots into the same place:
                       the GPU with the reference harness's inputs, checking
                       nothing by itself (the oracle lives in tests/); prints
                       one JSON line with timing.  --hip-periodic: on a torus.
+                      --hip-border MODE[,MODE...]: with a border mode per
+                      dimension.
 """
 import argparse
 import json
@@ -117,6 +119,18 @@ def add_arguments(parser) -> None:
                       help='with --hip-periodic: iterations between two '
                       'refills of the ghost frame (default: the deepest '
                       'fusion depth)')
+  parser.add_argument('--hip-border', dest='hip_border', default=None,
+                      metavar='MODE[,MODE...]',
+                      help='--hip-backend: run with borders -- every iteration '
+                      'sees its inputs extended by wrap, clamp, mirror, '
+                      'mirror101 or constant (one mode for all dimensions or '
+                      'one per dimension, dimension 0 first), every cell of '
+                      'the outputs is defined (soda_hip_border_run_device; one '
+                      'GPU, no --hip-until, no --hip-periodic)')
+  parser.add_argument('--hip-border-value', type=float,
+                      dest='hip_border_value', default=0.0, metavar='V',
+                      help='with --hip-border: the value outside the grid in a '
+                      '`constant` dimension (default 0)')
   parser.add_argument('--hip-nt-store', action='store_true',
                       dest='hip_nt_store',
                       help='non-temporal instead of plain output stores')
@@ -245,6 +259,18 @@ def run(stencil: core.Stencil, args: argparse.Namespace) -> None:
     raise util.InputError('--hip-periodic runs on one GPU, without --hip-until '
                           'or --hip-residual (slabs, groups and residuals are '
                           'not served on a torus yet)')
+  border = getattr(args, 'hip_border', None)
+  if border is not None and (
+      periodic or gpus > 1 or getattr(args, 'hip_until', None) is not None
+      or getattr(args, 'hip_residual', False)):
+    raise util.InputError('--hip-border runs on one GPU, without --hip-periodic, '
+                          '--hip-until or --hip-residual (slabs, groups and '
+                          'residuals are not served on a bordered domain yet)')
+  if border is not None:
+    border = [m.strip() for m in border.split(',')]
+    border = border * stencil.dim if len(border) == 1 else border
+    runtime._border_modes(border, stencil.dim)     # an InputError, before any
+                                                   # kernel is built
   if gpus > 1:
     # one host thread, N GPUs: slabs along the streamed dimension
     devices = ([args.hip_device] * gpus if getattr(args, 'hip_virtual', False)
@@ -309,6 +335,10 @@ def run(stencil: core.Stencil, args: argparse.Namespace) -> None:
       outputs = prog.run_periodic(inputs, refill_every=k)
       extra = {'periodic': True, 'refill_every': k or max(
           p.fused_iters for p in prog.module.passes)}
+    elif border is not None:
+      outputs = prog.run_bordered(inputs, border,
+                                  getattr(args, 'hip_border_value', 0.0))
+      extra = {'border': border}
     else:
       outputs = prog.run(inputs)
     seconds = time.time() - t0

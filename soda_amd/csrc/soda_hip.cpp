@@ -144,6 +144,7 @@ size_t soda_hip_sizeof(int which) {
     case 12: return sizeof(soda_hip_resbox_t);
     case 15: return sizeof(soda_hip_periodic_desc_t);
     case 16: return sizeof(soda_hip_periodic_info_t);
+    case 17: return sizeof(soda_hip_border_desc_t);
     default: return 0;
   }
 }

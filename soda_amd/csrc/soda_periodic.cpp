@@ -5,6 +5,12 @@
 // the ghost frame in between with the wrap kernel (soda_rt_wrap.h), which also
 // pads the dense entry's inputs and crops its outputs.  The program, its
 // module and its plan know nothing of this.
+//
+// Bordered domains (soda_hip_border_*) are the same handle
+// with another rule for the ghost frame: a mode per dimension and a constant
+// per tensor, the extend kernel (soda_rt_extend.h) in the wrap kernel's place,
+// one iteration between refills unless every mode wraps.  Everything below is
+// written once for both, told apart by a Kind.
 #include "soda_internal.h"
 
 #include <cstring>
@@ -37,7 +43,24 @@ struct WrapArgs {
   uint64_t total;
 };
 
+// the extend kernel's (soda_rt_extend.h): the same block, then the border
+struct ExtendArgs {
+  WrapArgs w;
+  int32_t mode[4];
+  uint64_t constant[16];
+};
+
 enum WrapJob { kFill, kPad, kCrop };
+
+// what tells a torus from a bordered domain: the names in messages, the kernel
+struct Kind {
+  const char* who;
+  const char* domain;
+  const char* kernel;
+  bool extend;
+};
+const Kind kTorus = {"periodic", "a torus", "soda_wrap", false};
+const Kind kBorder = {"border", "a bordered domain", "soda_extend", true};
 
 struct Torus {
   int dim;
@@ -103,6 +126,9 @@ bool wrap_regions(const Torus& t, WrapJob job, int elem, WrapArgs* a) {
 
 struct soda_hip_periodic {
   soda_hip_program* prog = nullptr;
+  const Kind* kind = &kTorus;
+  int32_t mode[4] = {0, 0, 0, 0};      // kBorder: SODA_HIP_BORDER_* ...
+  uint64_t constant[SODA_HIP_MAX_TENSORS] = {};   // ... and per input
   Torus t;
   int32_t k = 1;
   bool not_iterable = false;
@@ -125,32 +151,38 @@ int64_t cells_of(const int32_t* e, int dim) {
   return c;
 }
 
-// One job on `count` tensors: dst[i] / src[i] with cells of elem[i] bytes; one
-// launch per cell size among them.
+// One job on `count` tensors: dst[i] / src[i] with cells of elem[i] bytes (a
+// bordered domain: and the constant of input i); one launch per cell size
+// among them.
 int wrap_launch(soda_hip_periodic* h, WrapJob job, void* const* dst,
                 const void* const* src, const int32_t* elem, int count,
                 hipStream_t stream) {
+  const std::string who(h->kind->who);
   for (int size = 1; size <= 8; size *= 2) {
-    WrapArgs a;
-    memset(&a, 0, sizeof a);
+    ExtendArgs args;
+    memset(&args, 0, sizeof args);
+    WrapArgs& a = args.w;
     int m = 0;
     for (int i = 0; i < count; ++i)
       if (elem[i] == size) {
         a.dst[m] = dst[i];
         a.src[m] = src[i];
+        args.constant[m] = h->constant[i];
         ++m;
       }
     if (!m) continue;
     if (!wrap_regions(h->t, job, size, &a))
       return fail(SODA_HIP_ERR_INVALID,
-                  "periodic: 2^31 rows or more; nothing was launched");
+                  who + ": 2^31 rows or more; nothing was launched");
     if (!a.total) continue;          // no ghost cells: nothing to fill
     hipFunction_t fn = h->fn[log2_elem(size)];
-    if (!fn) return fail(SODA_HIP_ERR_INVALID, "periodic: no wrap kernel");
+    if (!fn) return fail(SODA_HIP_ERR_INVALID, who + ": no wrap kernel");
     int64_t blocks = (int64_t)((a.total + kWrapBlock - 1) / kWrapBlock);
     if (blocks > kWrapMaxBlocks) blocks = kWrapMaxBlocks;
-    size_t bytes = sizeof a;
-    void* extra[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &a,
+    for (int d = 0; d < 4; ++d) args.mode[d] = h->mode[d];
+    // the wrap kernel takes the block without the border behind it
+    size_t bytes = h->kind->extend ? sizeof args : sizeof a;
+    void* extra[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &args,
                      HIP_LAUNCH_PARAM_BUFFER_SIZE, &bytes,
                      HIP_LAUNCH_PARAM_END};
     HIP_TRY(hipModuleLaunchKernel(fn, (unsigned)blocks, (unsigned)m, 1,
@@ -269,36 +301,34 @@ int run_chunks(soda_hip_periodic* h, void* const* outputs,
   return SODA_HIP_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-int soda_hip_periodic_plan(const soda_hip_plan_t* plan,
-                           const soda_hip_periodic_desc_t* desc,
-                           int32_t iterate, soda_hip_periodic_info_t* info,
-                           int32_t capacity, int32_t* chunks, int32_t* count) {
+// soda_hip_periodic_plan, and soda_hip_border_plan behind its modes
+int plan_core(const Kind& kind, const soda_hip_plan_t* plan,
+              const soda_hip_periodic_desc_t* desc, int32_t iterate,
+              soda_hip_periodic_info_t* info, int32_t capacity,
+              int32_t* chunks, int32_t* count) {
+  const std::string who(kind.who);
   if (!plan || !desc)
-    return fail(SODA_HIP_ERR_INVALID, "periodic_plan: NULL argument");
+    return fail(SODA_HIP_ERR_INVALID, who + "_plan: NULL argument");
   if (plan->abi_version != SODA_HIP_ABI_VERSION || plan->dim < 1 ||
       plan->dim > SODA_HIP_MAX_DIM || plan->num_passes < 1 ||
       plan->num_passes > SODA_HIP_MAX_PASSES)
-    return fail(SODA_HIP_ERR_INVALID, "periodic_plan: bad plan");
+    return fail(SODA_HIP_ERR_INVALID, who + "_plan: bad plan");
   if (desc->preserve || (plan->residual.present && plan->residual.whole))
     return fail(SODA_HIP_ERR_UNSUPPORTED,
-                "periodic: a program with `border: preserve` pins its border, "
-                "and a torus has none; nothing was launched");
+                who + ": a program with `border: preserve` pins its border, "
+                      "and " + kind.domain + " has none; nothing was launched");
   if (plan->batched)
     return fail(SODA_HIP_ERR_UNSUPPORTED,
-                "periodic: batched plans are not served on a torus; nothing "
-                "was launched");
+                who + ": batched plans are not served on " + kind.domain +
+                    "; nothing was launched");
   const int dim = plan->dim;
   int32_t k = desc->refill_every;
   if (k < 0)
-    return fail(SODA_HIP_ERR_INVALID, "periodic: refill_every < 0");
+    return fail(SODA_HIP_ERR_INVALID, who + ": refill_every < 0");
   if (k == 0)
     for (int i = 0; i < plan->num_passes; ++i)
       if (plan->passes[i].fused_iters > k) k = plan->passes[i].fused_iters;
-  if (k < 1) return fail(SODA_HIP_ERR_INVALID, "periodic: bad plan");
+  if (k < 1) return fail(SODA_HIP_ERR_INVALID, who + ": bad plan");
   soda_hip_periodic_info_t out;
   memset(&out, 0, sizeof out);
   out.refill_every = k;
@@ -306,8 +336,8 @@ int soda_hip_periodic_plan(const soda_hip_plan_t* plan,
   for (int d = 0; d < dim; ++d) {
     if (desc->extent[d] < 1 || desc->ghost_lo[d] < 0 || desc->ghost_hi[d] < 0)
       return fail(SODA_HIP_ERR_INVALID,
-                  "periodic: extent < 1 or a negative ghost width; nothing was "
-                  "launched");
+                  who + ": extent < 1 or a negative ghost width; nothing was "
+                        "launched");
     out.ghost_lo[d] = desc->ghost_lo[d];
     out.ghost_hi[d] = desc->ghost_hi[d];
   }
@@ -317,9 +347,9 @@ int soda_hip_periodic_plan(const soda_hip_plan_t* plan,
         (int64_t)out.ghost_hi[ax] < (int64_t)k * plan->reach_hi) {
       char buf[256];
       snprintf(buf, sizeof buf,
-               "periodic: ghosts of %d / %d cells along the last dimension, "
+               "%s: ghosts of %d / %d cells along the last dimension, "
                "%d iterations between refills reach %d / %d; nothing was "
-               "launched", out.ghost_lo[ax], out.ghost_hi[ax], k,
+               "launched", kind.who, out.ghost_lo[ax], out.ghost_hi[ax], k,
                k * plan->reach_lo, k * plan->reach_hi);
       return fail(SODA_HIP_ERR_INVALID, buf);
     }
@@ -333,14 +363,14 @@ int soda_hip_periodic_plan(const soda_hip_plan_t* plan,
       p += vec - p % vec;
     }
     if (p > 0x7fffffffLL)
-      return fail(SODA_HIP_ERR_INVALID, "periodic: padded extent overflows");
+      return fail(SODA_HIP_ERR_INVALID, who + ": padded extent overflows");
     out.padded[d] = (int32_t)p;
     cells *= p;
   }
-  if (iterate < 0) return fail(SODA_HIP_ERR_INVALID, "periodic: iterate < 0");
+  if (iterate < 0) return fail(SODA_HIP_ERR_INVALID, who + ": iterate < 0");
   if (iterate > 1)
     if (int rc = check_iterate(*plan, desc->not_iterable != 0, iterate,
-                               "periodic"))
+                               kind.who))
       return rc;
   // what the kernels ask of the padded extent: row length, max_extent0, the
   // 1 GiB window of a plane
@@ -361,22 +391,19 @@ int soda_hip_periodic_plan(const soda_hip_plan_t* plan,
   return SODA_HIP_OK;
 }
 
-int soda_hip_periodic_create(soda_hip_program_t* p,
-                             const soda_hip_periodic_desc_t* desc,
-                             const void* const* wrap_code,
-                             const size_t* wrap_code_size,
-                             soda_hip_periodic_t** handle) {
-  if (handle) *handle = nullptr;
-  if (!p || !desc || !wrap_code || !wrap_code_size || !handle)
-    return fail(SODA_HIP_ERR_INVALID, "periodic_create: NULL argument");
+
+int create_core(const Kind& kind, soda_hip_program_t* p,
+                const soda_hip_periodic_desc_t* desc, const int32_t* mode,
+                const uint64_t* constant, const void* const* code,
+                const size_t* code_size, soda_hip_periodic** handle) {
+  const std::string who(kind.who);
   const soda_hip_plan_t& plan = p->plan;
   if (p->bank_tensors)
     return fail(SODA_HIP_ERR_UNSUPPORTED,
-                "periodic: programs on wire-format banks are not served on a "
-                "torus; nothing was launched");
+                who + ": programs on wire-format banks are not served on " +
+                    kind.domain + "; nothing was launched");
   soda_hip_periodic_info_t info;
-  if (int rc = soda_hip_periodic_plan(&plan, desc, 0, &info, 0, nullptr,
-                                      nullptr))
+  if (int rc = plan_core(kind, &plan, desc, 0, &info, 0, nullptr, nullptr))
     return rc;
   const int nin = plan.num_inputs, nout = plan.num_outputs;
   bool need[4] = {false, false, false, false};
@@ -384,18 +411,19 @@ int soda_hip_periodic_create(soda_hip_program_t* p,
     const int l = log2_elem(plan.elem_size[s]);
     if (l < 0)
       return fail(SODA_HIP_ERR_UNSUPPORTED,
-                  "periodic: cells of 1, 2, 4 or 8 bytes only");
+                  who + ": cells of 1, 2, 4 or 8 bytes only");
     need[l] = true;
   }
   for (int l = 0; l < 4; ++l)
-    if (need[l] && (!wrap_code[l] || !wrap_code_size[l]))
+    if (need[l] && (!code[l] || !code_size[l]))
       return fail(SODA_HIP_ERR_INVALID,
-                  "periodic_create: the wrap module of a cell size of the "
-                  "program is missing");
+                  who + "_create: the wrap module of a cell size of the "
+                        "program is missing");
   HIP_TRY(hipSetDevice(p->device));
   soda_hip_periodic* h = new (std::nothrow) soda_hip_periodic;
-  if (!h) return fail(SODA_HIP_ERR_NOMEM, "new periodic handle");
+  if (!h) return fail(SODA_HIP_ERR_NOMEM, "new " + who + " handle");
   h->prog = p;
+  h->kind = &kind;
   h->k = info.refill_every;
   h->not_iterable = desc->not_iterable != 0;
   const bool iterates = can_iterate(plan, h->not_iterable);
@@ -405,21 +433,25 @@ int soda_hip_periodic_create(soda_hip_program_t* p,
     h->t.glo[d] = info.ghost_lo[d];
     h->t.ghi[d] = info.ghost_hi[d];
     h->t.p[d] = info.padded[d];
+    if (mode) h->mode[d] = d < plan.dim ? mode[d] : 0;
   }
+  if (constant)
+    for (int i = 0; i < nin; ++i) h->constant[i] = constant[i];
   int rc = SODA_HIP_OK;
   for (int l = 0; l < 4 && !rc; ++l) {
     if (!need[l]) continue;
-    hipError_t e = hipModuleLoadData(&h->module[l], wrap_code[l]);
+    hipError_t e = hipModuleLoadData(&h->module[l], code[l]);
     if (e != hipSuccess) {
-      rc = hip_fail(e, "periodic_create: hipModuleLoadData");
+      rc = hip_fail(e, (who + "_create: hipModuleLoadData").c_str());
       break;
     }
     char name[64];
-    snprintf(name, sizeof name, "soda_wrap_e%d_d%d", 1 << l, plan.dim);
+    snprintf(name, sizeof name, "%s_e%d_d%d", kind.kernel, 1 << l, plan.dim);
     e = hipModuleGetFunction(&h->fn[l], h->module[l], name);
     if (e != hipSuccess)
-      rc = hip_fail(e, "periodic_create: hipModuleGetFunction (is this the "
-                       "wrap module of the cell size and dimension count?)");
+      rc = hip_fail(e, (who + "_create: hipModuleGetFunction (is this the "
+                              "wrap module of the cell size and dimension "
+                              "count?)").c_str());
   }
   const int64_t cells = cells_of(h->t.p, plan.dim);
   h->pad_in.resize(nin);
@@ -441,50 +473,21 @@ int soda_hip_periodic_create(soda_hip_program_t* p,
   return SODA_HIP_OK;
 }
 
-int soda_hip_periodic_destroy(soda_hip_periodic_t* h) {
-  if (!h) return SODA_HIP_OK;
-  (void)hipSetDevice(h->prog->device);
-  for (auto* v : {&h->pad_in, &h->pad_out, &h->pong})
-    for (auto& b : *v)
-      if (b.ptr) (void)hipFree(b.ptr);
-  for (auto& m : h->module)
-    if (m) (void)hipModuleUnload(m);
-  delete h;
-  return SODA_HIP_OK;
-}
-
-int soda_hip_periodic_info(soda_hip_periodic_t* h,
-                           soda_hip_periodic_info_t* info) {
-  if (!h || !info)
-    return fail(SODA_HIP_ERR_INVALID, "periodic_info: NULL argument");
-  memset(info, 0, sizeof *info);
-  info->refill_every = h->k;
-  for (int d = 0; d < 4; ++d) {
-    info->ghost_lo[d] = h->t.glo[d];
-    info->ghost_hi[d] = h->t.ghi[d];
-    info->padded[d] = h->t.p[d];
-  }
-  for (const auto* v : {&h->pad_in, &h->pad_out, &h->pong})
-    for (const auto& b : *v) info->scratch_bytes += (int64_t)b.bytes;
-  return SODA_HIP_OK;
-}
-
-int soda_hip_periodic_fill(soda_hip_periodic_t* h, void* const* arrays,
-                           int32_t count, void* stream) {
-  if (!h || !arrays)
-    return fail(SODA_HIP_ERR_INVALID, "periodic_fill: NULL argument");
+int fill_core(soda_hip_periodic* h, void* const* arrays, int32_t count,
+              void* stream) {
+  const std::string who(h->kind->who);
   const soda_hip_plan_t& plan = h->prog->plan;
   if (count < 0 || count > plan.num_outputs)
     return fail(SODA_HIP_ERR_INVALID,
-                "periodic_fill: one array per output at most; nothing was "
-                "launched");
+                who + "_fill: one array per output at most; nothing was "
+                      "launched");
   int32_t elem[SODA_HIP_MAX_TENSORS];
   for (int i = 0; i < count; ++i) {
     elem[i] = plan.elem_size[plan.num_inputs + i];
     if (!arrays[i] || reinterpret_cast<uintptr_t>(arrays[i]) % elem[i])
       return fail(SODA_HIP_ERR_INVALID,
-                  "periodic_fill: an array is NULL or not aligned to its cell "
-                  "size; nothing was launched");
+                  who + "_fill: an array is NULL or not aligned to its cell "
+                        "size; nothing was launched");
   }
   HIP_TRY(hipSetDevice(h->prog->device));
   return wrap_launch(h, kFill, arrays,
@@ -492,34 +495,29 @@ int soda_hip_periodic_fill(soda_hip_periodic_t* h, void* const* arrays,
                      static_cast<hipStream_t>(stream));
 }
 
-int soda_hip_periodic_run_padded(soda_hip_periodic_t* h, void* const* outputs,
-                                 const void* const* inputs, int32_t iterate,
-                                 void* stream) {
-  if (!h || !outputs || !inputs)
-    return fail(SODA_HIP_ERR_INVALID, "periodic_run_padded: NULL argument");
+int run_padded_core(soda_hip_periodic* h, void* const* outputs,
+                    const void* const* inputs, int32_t iterate, void* stream) {
+  const std::string who = std::string(h->kind->who) + "_run_padded";
   if (int rc = check_iterate(h->prog->plan, h->not_iterable, iterate,
-                             "periodic_run_padded"))
+                             who.c_str()))
     return rc;
   if (int rc = check_contract(h->prog->plan, outputs, inputs, h->t.p,
-                              "periodic_run_padded"))
+                              who.c_str()))
     return rc;
   return run_chunks(h, outputs, inputs, iterate, stream);
 }
 
-int soda_hip_periodic_run_device(soda_hip_periodic_t* h, void* const* outputs,
-                                 const void* const* inputs, int32_t iterate,
-                                 void* stream_) {
-  if (!h || !outputs || !inputs)
-    return fail(SODA_HIP_ERR_INVALID, "periodic_run_device: NULL argument");
+int run_device_core(soda_hip_periodic* h, void* const* outputs,
+                    const void* const* inputs, int32_t iterate,
+                    void* stream_) {
+  const std::string who = std::string(h->kind->who) + "_run_device";
   soda_hip_program* p = h->prog;
   const soda_hip_plan_t& plan = p->plan;
-  if (int rc = check_iterate(plan, h->not_iterable, iterate,
-                             "periodic_run_device"))
+  if (int rc = check_iterate(plan, h->not_iterable, iterate, who.c_str()))
     return rc;
   const int nin = plan.num_inputs, nout = plan.num_outputs;
   // the device entry contract on the caller's dense arrays of N
-  if (int rc = check_contract(plan, outputs, inputs, h->t.n,
-                              "periodic_run_device"))
+  if (int rc = check_contract(plan, outputs, inputs, h->t.n, who.c_str()))
     return rc;
   HIP_TRY(hipSetDevice(p->device));
   hipStream_t stream = static_cast<hipStream_t>(stream_);
@@ -545,6 +543,172 @@ int soda_hip_periodic_run_device(soda_hip_periodic_t* h, void* const* outputs,
   return wrap_launch(h, kCrop, outputs,
                      const_cast<const void* const*>(pout.data()), eout.data(),
                      nout, stream);
+}
+
+// Whether every mode of a bordered request wraps; its modes checked.
+int border_modes(const soda_hip_plan_t* plan,
+                 const soda_hip_border_desc_t* desc, bool* all_wrap) {
+  *all_wrap = true;
+  const int dim = plan->dim < 0                  ? 0
+                  : plan->dim > SODA_HIP_MAX_DIM ? SODA_HIP_MAX_DIM
+                                                 : plan->dim;
+  for (int d = 0; d < dim; ++d) {
+    if (desc->mode[d] < SODA_HIP_BORDER_WRAP ||
+        desc->mode[d] > SODA_HIP_BORDER_CONSTANT)
+      return fail(SODA_HIP_ERR_INVALID,
+                  "border: a mode that is none of SODA_HIP_BORDER_*; nothing "
+                  "was launched");
+    if (desc->mode[d] != SODA_HIP_BORDER_WRAP) *all_wrap = false;
+  }
+  if (!*all_wrap && desc->domain.refill_every > 1)
+    return fail(SODA_HIP_ERR_INVALID,
+                "border: only a wrapped ghost evolves with its interior: with "
+                "any other mode the frame is refilled after every iteration "
+                "(refill_every 0 or 1); nothing was launched");
+  return SODA_HIP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int soda_hip_periodic_plan(const soda_hip_plan_t* plan,
+                           const soda_hip_periodic_desc_t* desc,
+                           int32_t iterate, soda_hip_periodic_info_t* info,
+                           int32_t capacity, int32_t* chunks, int32_t* count) {
+  return plan_core(kTorus, plan, desc, iterate, info, capacity, chunks, count);
+}
+
+int soda_hip_periodic_create(soda_hip_program_t* p,
+                             const soda_hip_periodic_desc_t* desc,
+                             const void* const* wrap_code,
+                             const size_t* wrap_code_size,
+                             soda_hip_periodic_t** handle) {
+  if (handle) *handle = nullptr;
+  if (!p || !desc || !wrap_code || !wrap_code_size || !handle)
+    return fail(SODA_HIP_ERR_INVALID, "periodic_create: NULL argument");
+  return create_core(kTorus, p, desc, nullptr, nullptr, wrap_code,
+                     wrap_code_size, handle);
+}
+
+int soda_hip_periodic_destroy(soda_hip_periodic_t* h) {
+  if (!h) return SODA_HIP_OK;
+  (void)hipSetDevice(h->prog->device);
+  for (auto* v : {&h->pad_in, &h->pad_out, &h->pong})
+    for (auto& b : *v)
+      if (b.ptr) (void)hipFree(b.ptr);
+  for (auto& m : h->module)
+    if (m) (void)hipModuleUnload(m);
+  delete h;
+  return SODA_HIP_OK;
+}
+
+int soda_hip_periodic_info(soda_hip_periodic_t* h,
+                           soda_hip_periodic_info_t* info) {
+  if (!h || !info)
+    return fail(SODA_HIP_ERR_INVALID,
+                std::string(h ? h->kind->who : "periodic") +
+                    "_info: NULL argument");
+  memset(info, 0, sizeof *info);
+  info->refill_every = h->k;
+  for (int d = 0; d < 4; ++d) {
+    info->ghost_lo[d] = h->t.glo[d];
+    info->ghost_hi[d] = h->t.ghi[d];
+    info->padded[d] = h->t.p[d];
+  }
+  for (const auto* v : {&h->pad_in, &h->pad_out, &h->pong})
+    for (const auto& b : *v) info->scratch_bytes += (int64_t)b.bytes;
+  return SODA_HIP_OK;
+}
+
+int soda_hip_periodic_fill(soda_hip_periodic_t* h, void* const* arrays,
+                           int32_t count, void* stream) {
+  if (!h || !arrays)
+    return fail(SODA_HIP_ERR_INVALID, "periodic_fill: NULL argument");
+  return fill_core(h, arrays, count, stream);
+}
+
+int soda_hip_periodic_run_padded(soda_hip_periodic_t* h, void* const* outputs,
+                                 const void* const* inputs, int32_t iterate,
+                                 void* stream) {
+  if (!h || !outputs || !inputs)
+    return fail(SODA_HIP_ERR_INVALID, "periodic_run_padded: NULL argument");
+  return run_padded_core(h, outputs, inputs, iterate, stream);
+}
+
+int soda_hip_periodic_run_device(soda_hip_periodic_t* h, void* const* outputs,
+                                 const void* const* inputs, int32_t iterate,
+                                 void* stream) {
+  if (!h || !outputs || !inputs)
+    return fail(SODA_HIP_ERR_INVALID, "periodic_run_device: NULL argument");
+  return run_device_core(h, outputs, inputs, iterate, stream);
+}
+
+// -- bordered domains: the same handle behind its modes ----
+
+int soda_hip_border_plan(const soda_hip_plan_t* plan,
+                         const soda_hip_border_desc_t* desc, int32_t iterate,
+                         soda_hip_periodic_info_t* info, int32_t capacity,
+                         int32_t* chunks, int32_t* count) {
+  if (!plan || !desc)
+    return fail(SODA_HIP_ERR_INVALID, "border_plan: NULL argument");
+  bool all_wrap;
+  if (int rc = border_modes(plan, desc, &all_wrap)) return rc;
+  if (all_wrap)
+    return soda_hip_periodic_plan(plan, &desc->domain, iterate, info, capacity,
+                                  chunks, count);
+  soda_hip_periodic_desc_t domain = desc->domain;
+  if (domain.refill_every == 0) domain.refill_every = 1;
+  return plan_core(kBorder, plan, &domain, iterate, info, capacity, chunks,
+                   count);
+}
+
+int soda_hip_border_create(soda_hip_program_t* p,
+                           const soda_hip_border_desc_t* desc,
+                           const void* const* code, const size_t* code_size,
+                           soda_hip_border_t** handle) {
+  if (handle) *handle = nullptr;
+  if (!p || !desc || !code || !code_size || !handle)
+    return fail(SODA_HIP_ERR_INVALID, "border_create: NULL argument");
+  bool all_wrap;
+  if (int rc = border_modes(&p->plan, desc, &all_wrap)) return rc;
+  soda_hip_periodic_desc_t domain = desc->domain;
+  if (!all_wrap && domain.refill_every == 0) domain.refill_every = 1;
+  return create_core(kBorder, p, &domain, desc->mode, desc->constant, code,
+                     code_size, handle);
+}
+
+int soda_hip_border_destroy(soda_hip_border_t* h) {
+  return soda_hip_periodic_destroy(h);
+}
+
+int soda_hip_border_info(soda_hip_border_t* h,
+                         soda_hip_periodic_info_t* info) {
+  if (!h) return fail(SODA_HIP_ERR_INVALID, "border_info: NULL argument");
+  return soda_hip_periodic_info(h, info);
+}
+
+int soda_hip_border_fill(soda_hip_border_t* h, void* const* arrays,
+                         int32_t count, void* stream) {
+  if (!h || !arrays)
+    return fail(SODA_HIP_ERR_INVALID, "border_fill: NULL argument");
+  return fill_core(h, arrays, count, stream);
+}
+
+int soda_hip_border_run_padded(soda_hip_border_t* h, void* const* outputs,
+                               const void* const* inputs, int32_t iterate,
+                               void* stream) {
+  if (!h || !outputs || !inputs)
+    return fail(SODA_HIP_ERR_INVALID, "border_run_padded: NULL argument");
+  return run_padded_core(h, outputs, inputs, iterate, stream);
+}
+
+int soda_hip_border_run_device(soda_hip_border_t* h, void* const* outputs,
+                               const void* const* inputs, int32_t iterate,
+                               void* stream) {
+  if (!h || !outputs || !inputs)
+    return fail(SODA_HIP_ERR_INVALID, "border_run_device: NULL argument");
+  return run_device_core(h, outputs, inputs, iterate, stream);
 }
 
 }  // extern "C"

@@ -15,6 +15,7 @@ import ctypes
 import dataclasses
 import hashlib
 import os
+import sys
 from typing import Dict, Optional, Sequence
 
 from soda_amd import core, util
@@ -257,6 +258,15 @@ class PeriodicInfo(ctypes.Structure):
               ('scratch_bytes', ctypes.c_int64)]
 
 
+class BorderDesc(ctypes.Structure):
+  """Mirror of soda_hip_border_desc_t: a domain, a mode per dimension, a
+  constant per input tensor."""
+  _fields_ = [('domain', PeriodicDesc),
+              ('mode', ctypes.c_int32 * MAX_DIM),
+              ('reserved', ctypes.c_int32),
+              ('constant', ctypes.c_uint64 * MAX_TENSORS)]
+
+
 # every symbol include/soda_hip.h declares: name -> (restype, argtypes)
 _vp = ctypes.c_void_p
 _i32 = ctypes.c_int32
@@ -360,6 +370,22 @@ API = {
     'soda_hip_periodic_fill': (ctypes.c_int, [_vp, _pvp, _i32, _vp]),
     'soda_hip_periodic_run_padded': (ctypes.c_int, [_vp, _pvp, _pvp, _i32,
                                                     _vp]),
+    'soda_hip_extend_host': (ctypes.c_int, [_vp, _i32, _i32, _pi32, _pi32,
+                                            _pi32, _pi32, ctypes.c_uint64]),
+    'soda_hip_border_plan': (ctypes.c_int, [
+        ctypes.POINTER(Plan), ctypes.POINTER(BorderDesc), _i32,
+        ctypes.POINTER(PeriodicInfo), _i32, _pi32, _pi32
+    ]),
+    'soda_hip_border_create': (ctypes.c_int, [
+        _vp, ctypes.POINTER(BorderDesc), _pvp,
+        ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(_vp)
+    ]),
+    'soda_hip_border_destroy': (ctypes.c_int, [_vp]),
+    'soda_hip_border_info': (ctypes.c_int, [_vp,
+                                            ctypes.POINTER(PeriodicInfo)]),
+    'soda_hip_border_fill': (ctypes.c_int, [_vp, _pvp, _i32, _vp]),
+    'soda_hip_border_run_padded': (ctypes.c_int, [_vp, _pvp, _pvp, _i32, _vp]),
+    'soda_hip_border_run_device': (ctypes.c_int, [_vp, _pvp, _pvp, _i32, _vp]),
     'soda_hip_periodic_run_device': (ctypes.c_int, [_vp, _pvp, _pvp, _i32,
                                                     _vp]),
     'soda_hip_run_device_window': (ctypes.c_int, [_vp, _pvp, _pvp, _pi32, _pi32,
@@ -499,7 +525,8 @@ def library() -> ctypes.CDLL:
                           (7, GroupDesc), (8, SlabInfo), (9, GroupStats),
                           (10, LaunchInfo), (11, ResidualStruct),
                           (12, ResBox), (14, NormsStruct),
-                          (15, PeriodicDesc), (16, PeriodicInfo)):
+                          (15, PeriodicDesc), (16, PeriodicInfo),
+                          (17, BorderDesc)):
       if lib.soda_hip_sizeof(which) != ctypes.sizeof(mirror):
         raise util.BackendError(
             'struct layout mismatch between libsoda_hip.so and runtime.py '
@@ -1410,6 +1437,31 @@ class Periodic:
   of the program's ordinary kernels and is refilled on the GPU in between.
   Made by `Program.periodic`; close it before its program."""
 
+  _entry = 'soda_hip_periodic_'    # the library's entries of this handle
+  _what = 'periodic'
+
+  def _fn(self, name):
+    return getattr(self._lib, self._entry + name)
+
+  def _codes_of(self, resources):
+    """(codes, sizes) for the create entry: the code object `resources(elem,
+    dim)` gives for every cell size among the inputs and outputs."""
+    st = self.prog.stencil
+    codes = (ctypes.c_void_p * 4)()
+    sizes = (ctypes.c_size_t * 4)()
+    self._codes = []
+    if not st.preserve_border:      # (refused by create: nothing to build for)
+      sizes_needed = {t.size_in_bytes
+                      for t in list(st.input_types) + list(st.output_types)}
+      for elem in sorted(sizes_needed & {1, 2, 4, 8}):
+        code, _ = resources(elem, st.dim)
+        buf = ctypes.create_string_buffer(code, len(code))
+        self._codes.append(buf)
+        i = elem.bit_length() - 1
+        codes[i] = ctypes.cast(buf, ctypes.c_void_p)
+        sizes[i] = len(code)
+    return codes, sizes
+
   def __init__(self, prog: 'Program', extent: Sequence[int],
                refill_every: Optional[int] = None,
                ghosts: Optional[Sequence[Sequence[int]]] = None):
@@ -1429,19 +1481,7 @@ class Periodic:
     desc = _periodic_desc(
         st.dim, self.extent, k, lo, hi, st.preserve_border,
         not_iterable=list(st.input_types) != list(st.output_types))
-    codes = (ctypes.c_void_p * 4)()
-    sizes = (ctypes.c_size_t * 4)()
-    self._codes = []
-    if not st.preserve_border:      # (refused below: nothing to build for)
-      sizes_needed = {t.size_in_bytes
-                      for t in list(st.input_types) + list(st.output_types)}
-      for elem in sorted(sizes_needed & {1, 2, 4, 8}):
-        code, _ = wrap_resources(elem, st.dim)
-        buf = ctypes.create_string_buffer(code, len(code))
-        self._codes.append(buf)
-        i = elem.bit_length() - 1
-        codes[i] = ctypes.cast(buf, ctypes.c_void_p)
-        sizes[i] = len(code)
+    codes, sizes = self._codes_of(wrap_resources)
     self._lib = library()
     self._handle = ctypes.c_void_p()
     check(self._lib.soda_hip_periodic_create(prog._handle, ctypes.byref(desc),
@@ -1453,7 +1493,7 @@ class Periodic:
 
   def close(self) -> None:
     if getattr(self, '_handle', None):
-      self._lib.soda_hip_periodic_destroy(self._handle)
+      self._fn('destroy')(self._handle)
       self._handle = None
       if self in self.prog._periodic:
         self.prog._periodic.remove(self)
@@ -1475,17 +1515,16 @@ class Periodic:
     what the library chose (ghost_hi[0] rounded up until padded[0] is a
     multiple of the program's vector width) and holds."""
     raw = PeriodicInfo()
-    check(self._lib.soda_hip_periodic_info(self._handle, ctypes.byref(raw)),
-          'periodic: info')
+    check(self._fn('info')(self._handle, ctypes.byref(raw)),
+          '%s: info' % self._what)
     return _periodic_info(raw, self.prog.stencil.dim)
 
   def fill(self, arrays: Sequence[int], stream: int = 0) -> None:
     """Refills the ghost frame of padded device arrays in place (array i: the
     cells of output i); asynchronous on `stream`."""
     arr = (ctypes.c_void_p * max(1, len(arrays)))(*arrays)
-    check(self._lib.soda_hip_periodic_fill(self._handle, arr, len(arrays),
-                                           ctypes.c_void_p(stream)),
-          'periodic: fill')
+    check(self._fn('fill')(self._handle, arr, len(arrays),
+                           ctypes.c_void_p(stream)), '%s: fill' % self._what)
 
   def _run(self, fn, what, outputs, inputs, iterate, stream):
     st = self.prog.stencil
@@ -1505,15 +1544,182 @@ class Periodic:
     """`iterate` iterations on PADDED device arrays of info()['padded']: the
     inputs (then the param arrays) arrive wrapped, the outputs leave wrapped,
     the inputs are never written (soda_hip_periodic_run_padded)."""
-    self._run(self._lib.soda_hip_periodic_run_padded, 'periodic run_padded',
+    self._run(self._fn('run_padded'), '%s run_padded' % self._what,
               outputs, inputs, iterate, stream)
 
   def run_device(self, outputs: Sequence[int], inputs: Sequence[int],
                  iterate: Optional[int] = None, stream: int = 0) -> None:
     """The same on DENSE device arrays of the torus's extent: padded into the
     handle's scratch, run, cropped (soda_hip_periodic_run_device)."""
-    self._run(self._lib.soda_hip_periodic_run_device, 'periodic run_device',
+    self._run(self._fn('run_device'), '%s run_device' % self._what,
               outputs, inputs, iterate, stream)
+
+
+# -- bordered domains: a border mode per dimension (DESIGN.md 4.12) -----------
+def _border_modes(modes, dim: int):
+  """SODA_HIP_BORDER_* per dimension of `modes`: one name for all dimensions
+  or one per dimension, dimension 0 first."""
+  from soda_amd.codegen.hip import extend as _extend
+  names = [modes] * dim if isinstance(modes, str) else list(modes)
+  if len(names) != dim:
+    raise util.InputError('border: one mode, or one per dimension (%d)' % dim)
+  for m in names:
+    if m not in _extend.MODES:
+      raise util.InputError('border: unknown mode %r (one of %s)' % (
+          m, ', '.join(sorted(_extend.MODES))))
+  return [_extend.MODES[m] for m in names]
+
+
+def _cell_bits(value, np_name: str) -> int:
+  """The bit pattern of `value` as a cell of a numpy type, in a uint64."""
+  import numpy as np
+  cell = np.asarray(value).astype(np.dtype(np_name)).reshape(1)
+  return int.from_bytes(cell.tobytes(), sys.byteorder)
+
+
+def _border_constants(stencil: core.Stencil, constants):
+  """One uint64 per input of `stencil`: `constants` is None (zero), a scalar
+  for every input or {input: scalar}."""
+  if constants is None:
+    constants = {}
+  if not isinstance(constants, dict):
+    constants = {n: constants for n in stencil.input_names}
+  unknown = sorted(set(constants) - set(stencil.input_names))
+  if unknown:
+    raise util.InputError('border: constants for %s, which are no inputs' %
+                          ', '.join(unknown))
+  return [_cell_bits(constants.get(n, 0), t.np_name)
+          for n, t in zip(stencil.input_names, stencil.input_types)]
+
+
+def extend_host(arr, ghost_lo: Sequence[int], ghost_hi: Sequence[int], modes,
+                constant=0):
+  """wrap_host with a border mode per dimension: refills the ghost frame of the
+  padded numpy array `arr` IN PLACE from its interior (soda_hip_extend_host,
+  plain C++; no GPU needed).  `modes`: one name or one per dimension,
+  dimension 0 (the LAST numpy axis) first; `constant`: the value of a ghost
+  cell outside in a `constant` dimension, converted to the cell type.  Returns
+  `arr`."""
+  import numpy as np
+  if not isinstance(arr, np.ndarray) or not arr.flags['C_CONTIGUOUS'] or \
+      not arr.flags['WRITEABLE']:
+    raise util.InputError('extend_host: a writable C-contiguous numpy array')
+  dim = arr.ndim
+  if len(ghost_lo) != dim or len(ghost_hi) != dim:
+    raise util.InputError('extend_host: %d ghost widths per side' % dim)
+  padded = arr.shape[::-1]
+  extent = [p - l - h for p, l, h in zip(padded, ghost_lo, ghost_hi)]
+  if arr.dtype.itemsize not in (1, 2, 4, 8) or not 1 <= dim <= MAX_DIM or \
+      min(extent) < 1 or min(ghost_lo) < 0 or min(ghost_hi) < 0:
+    raise util.InputError(
+        'extend_host: cells of 1, 2, 4 or 8 bytes, 1 to %d dimensions, ghosts '
+        '>= 0 that leave a domain of at least one cell' % MAX_DIM)
+  bits = constant if isinstance(constant, (bytes, bytearray)) else \
+      np.asarray(constant).astype(arr.dtype).tobytes()
+  if len(bits) != arr.dtype.itemsize:
+    raise util.InputError('extend_host: a constant of one cell')
+  check(library().soda_hip_extend_host(
+      arr.ctypes.data, arr.dtype.itemsize, dim, (ctypes.c_int32 * dim)(*extent),
+      (ctypes.c_int32 * dim)(*ghost_lo), (ctypes.c_int32 * dim)(*ghost_hi),
+      (ctypes.c_int32 * dim)(*_border_modes(modes, dim)),
+      int.from_bytes(bits, sys.byteorder)), 'extend_host')
+  return arr
+
+
+def border_ghosts(stencil: core.Stencil, modes):
+  """(ghost_lo, ghost_hi) of a bordered domain: with a mode other than `wrap`
+  the frame of ONE iteration (periodic_ghosts(stencil, 1): the most
+  window_bounds(1) reaches over all outputs, along the last dimension at
+  least the plan's reach) -- it is refilled after every iteration."""
+  _border_modes(modes, stencil.dim)
+  return periodic_ghosts(stencil, 1)
+
+
+def _border_desc(domain: PeriodicDesc, modes,
+                 constants: Sequence[int]) -> BorderDesc:
+  desc = BorderDesc()
+  desc.domain = domain
+  for d, m in enumerate(modes):
+    desc.mode[d] = m
+  for i, c in enumerate(constants):
+    desc.constant[i] = c
+  return desc
+
+
+def border_plan(plan: Plan, extent: Sequence[int], modes,
+                ghost_lo: Sequence[int], ghost_hi: Sequence[int],
+                iterate: int = 0, refill_every: int = 0,
+                preserve: bool = False, not_iterable: bool = False):
+  """periodic_plan for a bordered domain (soda_hip_border_plan; no GPU
+  needed): (info, chunks).  `modes`: names, or raw SODA_HIP_BORDER_* numbers
+  (which reach the library unchecked).  With a mode other than `wrap`,
+  `refill_every` must be 0 or 1 and every chunk is one iteration; with all
+  `wrap` this is periodic_plan."""
+  raw_modes = list(modes) if not isinstance(modes, str) and all(
+      isinstance(m, int) for m in modes) else _border_modes(modes, plan.dim)
+  if len(raw_modes) != plan.dim:
+    raise util.InputError('border: one mode per dimension (%d)' % plan.dim)
+  desc = _border_desc(_periodic_desc(
+      plan.dim, extent, refill_every, ghost_lo, ghost_hi, preserve,
+      not_iterable), raw_modes, ())
+  raw = PeriodicInfo()
+  cap = max(1, iterate)
+  chunks = (ctypes.c_int32 * cap)()
+  n = ctypes.c_int32()
+  check(library().soda_hip_border_plan(ctypes.byref(plan), ctypes.byref(desc),
+                                       iterate, ctypes.byref(raw), cap, chunks,
+                                       ctypes.byref(n)), 'border_plan')
+  return _periodic_info(raw, plan.dim), list(chunks[:n.value])
+
+
+def extend_resources(elem: int, dim: int):
+  """(code object, kernel_resources of it) of the extend module of a cell size
+  and dimension count: JIT-built like every module, cached like them; needs
+  no GPU."""
+  from soda_amd.codegen.hip import extend as _extend
+  code = compile_source(_extend.source(elem, dim),
+                        'extend_e%d_%dd.hip' % (elem, dim))
+  return code, kernel_resources(code)
+
+
+class Bordered(Periodic):
+  """A program on a domain of ONE extent with a border mode per dimension
+  (soda_hip_border_create): Periodic's padded arrays and entries, the ghost
+  frame refilled under the modes after every iteration -- or, with every
+  dimension `wrap`, the torus of Periodic at its default refill interval.
+  Made by `Program.bordered`; close it before its program."""
+
+  _entry = 'soda_hip_border_'
+  _what = 'border'
+
+  def __init__(self, prog: 'Program', extent: Sequence[int], modes,
+               constants=None):
+    """`modes`: one name for all dimensions or one per dimension, dimension 0
+    first, of wrap / clamp / mirror / mirror101 / constant.  `constants`: a
+    scalar or {input: scalar}, converted to the cell type's bits (default
+    zero); an output's ghost takes the constant of the input it replaces."""
+    st = prog.stencil
+    self.prog, self.extent = prog, tuple(int(e) for e in extent)
+    prog._check_extent(self.extent)
+    self.modes = tuple([modes] * st.dim if isinstance(modes, str) else modes)
+    raw_modes = _border_modes(modes, st.dim)
+    k = 1
+    if not any(raw_modes):          # a torus: Periodic's default
+      k = max(p.fused_iters for p in prog.module.passes)
+    lo, hi = periodic_ghosts(st, k)
+    desc = _border_desc(_periodic_desc(
+        st.dim, self.extent, k, lo, hi, st.preserve_border,
+        not_iterable=list(st.input_types) != list(st.output_types)),
+                        raw_modes, _border_constants(st, constants))
+    codes, sizes = self._codes_of(extend_resources)
+    self._lib = library()
+    self._handle = ctypes.c_void_p()
+    check(self._lib.soda_hip_border_create(prog._handle, ctypes.byref(desc),
+                                           codes, sizes,
+                                           ctypes.byref(self._handle)),
+          '`%s` on %s with borders %s' % (st.app_name, 'x'.join(
+              map(str, self.extent)), ', '.join(self.modes)))
+    prog._periodic.append(self)
 
 
 class Program:
@@ -2018,6 +2224,39 @@ class Program:
                 synchronize=True) as (dev_in, dev_out):
       per.run_device(dev_out, dev_in, iterate)
       _copy_out(lib, dense, dev_out, 'run_periodic')
+    return result
+
+  # -- bordered domains ------------------------------------------------------
+  def bordered(self, extent: Sequence[int], modes, constants=None) -> Bordered:
+    """This program on a domain of `extent` with a border mode per dimension
+    (runtime.Bordered).  The handle is closed with the program
+    at the latest."""
+    return Bordered(self, extent, modes, constants)
+
+  def run_bordered(self, inputs: Dict[str, 'numpy.ndarray'], modes,
+                   constants=None, iterate: Optional[int] = None
+                   ) -> Dict[str, 'numpy.ndarray']:
+    """`run` with borders: numpy arrays of the domain in, the outputs out,
+    EVERY cell of them defined -- each iteration sees its inputs extended by
+    `modes` (one name, or one per dimension, dimension 0 first) and
+    `constants` (a scalar or {input: scalar}; default zero).  A plain allocate
+    / copy in / Bordered.run_device / copy out."""
+    import numpy as np
+    st = self.stencil
+    lib = self._lib
+    iterate = st.iterate if iterate is None else iterate
+    first = np.asarray(inputs[st.input_names[0]])
+    extent = tuple(first.shape[::-1])
+    self._check_extent(extent)
+    host_in = _host_inputs(st, inputs, first.shape)
+    result = {n: np.empty(first.shape, dtype=np.dtype(t.np_name))
+              for n, t in zip(st.output_names, st.output_types)}
+    dense = list(result.values())
+    with self.bordered(extent, modes, constants) as bor, \
+        _staged(lib, self.device, host_in, dense, 'run_bordered',
+                synchronize=True) as (dev_in, dev_out):
+      bor.run_device(dev_out, dev_in, iterate)
+      _copy_out(lib, dense, dev_out, 'run_bordered')
     return result
 
   def run_batch(self, inputs: Dict[str, 'numpy.ndarray'],
