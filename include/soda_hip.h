@@ -75,7 +75,10 @@ extern "C" {
  * domains -- soda_hip_wrap_host, soda_hip_periodic_plan / _create / _destroy /
  * _info / _fill / _run_padded / _run_device; and bordered domains --
  * soda_hip_extend_host, soda_hip_border_plan / _create / _destroy / _info /
- * _fill / _run_padded / _run_device with soda_hip_border_desc_t. */
+ * _fill / _run_padded / _run_device with soda_hip_border_desc_t; and their
+ * fused form -- soda_hip_box_host, soda_hip_border_fused_plan / _create /
+ * _destroy / _info / _move / _run_padded / _run_device with
+ * soda_hip_border_fused_desc_t. */
 #define SODA_HIP_ABI_VERSION 9
 #define SODA_HIP_MAX_DIM 4
 #define SODA_HIP_MAX_TENSORS 16
@@ -307,8 +310,9 @@ int soda_hip_device_count(int* count);
  * check their mirrors: 0 kargs, 1 kernel_desc, 2 pass_desc, 3 plan,
  * 4 host_tensor, 5 stream_desc, 6 slab_run, 7 group_desc, 8 slab_info,
  * 9 group_stats, 10 launch_info, 11 residual, 12 resbox, 14 norms,
- * 15 periodic_desc, 16 periodic_info, 17 border_desc; 0 for anything else
- * (13 among them). */
+ * 15 periodic_desc, 16 periodic_info, 17 border_desc, 18 border_fused_desc,
+ * 19 border_strip, 20 border_fused_info; 0 for anything else (13 among
+ * them). */
 size_t soda_hip_sizeof(int which);
 
 /* -- JIT: HIP source text -> gfx950 code object (hiprtc; needs no GPU) ---- */
@@ -1017,6 +1021,143 @@ int soda_hip_border_run_padded(soda_hip_border_t* handle, void* const* outputs,
 int soda_hip_border_run_device(soda_hip_border_t* handle, void* const* outputs,
                                const void* const* inputs, int32_t iterate,
                                void* stream);
+
+/* -- bordered domains, fused away from the walls ----------- */
+/* The block above advances one iteration per launch.  Here a chunk of n <= T
+ * iterations (T: the depth) takes an extended state S to the extended S':
+ *   interior  n iterations of the ordinary kernels on P, fused as deep as the
+ *             plan allows.  With a frame of ONE iteration's reach in a wall
+ *             dimension every domain cell at least (n - 1) x reach_lo from a
+ *             low wall and (n - 1) x reach_hi from a high wall comes out right;
+ *             a WRAP dimension, whose frame carries T iterations, is right
+ *             over its whole width.
+ *   strips    per wall dimension d whose reach is not zero ONE strip: a
+ *             bordered domain of the block above, with the request's modes and
+ *             constants, of extent N with N[d] replaced by L + H -- the
+ *             domain's cells [0, L) and [N[d] - H, N[d]) side by side,
+ *             L = H = T x (reach_lo[d] + reach_hi[d]).  It is gathered from S,
+ *             advanced n iterations one at a time, and its cells
+ *             [0, take_lo) and [L + H - take_hi, L + H) along d,
+ *             take = (T - 1) x reach, are scattered into the interior's
+ *             result; they are clear of the false neighbours in the strip's
+ *             middle for every n <= T.
+ *   fill      one ordinary fill of the frame of P.
+ * All on the one stream, in that order.  Every cell is computed by the same
+ * expression from the same values as in the block above: the result equals
+ * soda_hip_border_run_* bit for bit, whatever the depth.
+ * The depth resolves to 1 -- and the handle is the block above's -- when it is
+ * given as 1, when the program cannot iterate, or when some wall dimension
+ * has N[d] < L + H.  With every mode WRAP the handle is the torus at
+ * refill_every = depth. */
+typedef struct soda_hip_border_fused_desc {
+  soda_hip_border_desc_t border;       /* as above; domain.refill_every 0 or 1
+                                          (the depth takes its place);
+                                          ghost_lo / ghost_hi: at least reach in
+                                          a wall dimension, depth x reach in a
+                                          WRAP dimension */
+  int32_t depth;                       /* T; 0: the largest fused_iters of the
+                                          plan's passes */
+  int32_t reach_lo[SODA_HIP_MAX_DIM];  /* cells ONE iteration reaches below ... */
+  int32_t reach_hi[SODA_HIP_MAX_DIM];  /* ... and above a cell, the most over
+                                          all outputs (the caller's to compute:
+                                          Stencil.window_bounds(1)); with
+                                          plan->has_reach, along the last
+                                          dimension at least the plan's reach */
+  int32_t reserved;
+} soda_hip_border_fused_desc_t;
+typedef struct soda_hip_border_strip {
+  int32_t dim;                         /* the wall dimension d */
+  int32_t lo, hi;                      /* L, H */
+  int32_t take_lo, take_hi;            /* cells along d the scatter takes at
+                                          the low / the high wall */
+  int32_t reserved;
+  int32_t extent[SODA_HIP_MAX_DIM];    /* N with N[d] = L + H */
+  soda_hip_periodic_info_t info;       /* the strip's own handle: ghosts (the
+                                          request's; [0] as rounded for this
+                                          extent), padded extent, scratch */
+} soda_hip_border_strip_t;
+typedef struct soda_hip_border_fused_info {
+  soda_hip_periodic_info_t main;       /* the handle on N; refill_every: 1, or
+                                          the depth on a torus */
+  int32_t depth;                       /* T as resolved */
+  int32_t num_strips;                  /* 0 at depth 1 and on a torus */
+  soda_hip_border_strip_t strip[SODA_HIP_MAX_DIM];  /* by rising dimension */
+  int64_t scratch_bytes;               /* main and strips together */
+} soda_hip_border_fused_info_t;
+/* The box mover on host arrays, in plain C++ (no GPU, no allocation): box b
+ * copies size[b * dim + d] cells per dimension from `src` (dense,
+ * dim-0-fastest, of src_extent) at src_origin[b * dim + d] to `dst` (of
+ * dst_extent) at dst_origin[b * dim + d].  A box with a size of 0 is empty.
+ * The arrays must not overlap.  SODA_HIP_ERR_INVALID, nothing written: a cell
+ * size other than 1, 2, 4 or 8 bytes, dim outside 1..4, a negative size or
+ * origin, a box that leaves either array. */
+int soda_hip_box_host(void* dst, const int32_t* dst_extent, const void* src,
+                      const int32_t* src_extent, int32_t elem_bytes,
+                      int32_t dim, int32_t num_boxes,
+                      const int32_t* dst_origin, const int32_t* src_origin,
+                      const int32_t* size);
+/* soda_hip_border_plan for the fused form: *info, and the iterations of every
+ * chunk -- the depth each, the last may be shorter -- in chunks[0, *count).
+ * Pure function.  Refuses what soda_hip_border_plan refuses, on N and on every
+ * strip's extent, and:
+ *   SODA_HIP_ERR_INVALID      depth < 0; a negative reach; with
+ *                             plan->has_reach, a reach along the last
+ *                             dimension below the plan's; a frame narrower than
+ *                             reach in a wall dimension or than depth x reach
+ *                             in a WRAP dimension. */
+int soda_hip_border_fused_plan(const soda_hip_plan_t* plan,
+                               const soda_hip_border_fused_desc_t* desc,
+                               int32_t iterate,
+                               soda_hip_border_fused_info_t* info,
+                               int32_t capacity, int32_t* chunks,
+                               int32_t* count);
+/* A handle over `program` for ONE bordered domain, fused.  code / code_size:
+ * the EXTEND modules as for soda_hip_border_create; box_code / box_code_size:
+ * the BOX modules (codegen/hip/box.py) likewise, needed where the plan has
+ * strips.  All scratch is allocated here, the strips' included.  A refusal
+ * launches nothing and allocates nothing.  The handle must be destroyed before
+ * its program. */
+typedef struct soda_hip_border_fused soda_hip_border_fused_t;   /* opaque */
+int soda_hip_border_fused_create(soda_hip_program_t* program,
+                                 const soda_hip_border_fused_desc_t* desc,
+                                 const void* const* code,
+                                 const size_t* code_size,
+                                 const void* const* box_code,
+                                 const size_t* box_code_size,
+                                 soda_hip_border_fused_t** handle);
+int soda_hip_border_fused_destroy(soda_hip_border_fused_t* handle);
+int soda_hip_border_fused_info(soda_hip_border_fused_t* handle,
+                               soda_hip_border_fused_info_t* info);
+/* The primitive: the two boxes of strip `strip` (0 .. num_strips - 1) between
+ * `count` caller-owned padded device arrays on either side, pair i with the
+ * cells of the program's output i (count <= num_outputs), each aligned to its
+ * cell size: main_arrays of P, strip_arrays of the strip's padded extent.
+ * gather != 0: the domain's cells [0, L) and [N[d] - H, N[d]) along the
+ * strip's dimension, over the whole domain elsewhere, from main_arrays into
+ * the strip's domain; gather == 0, the scatter: the strip's cells
+ * [0, take_lo) and [L + H - take_hi, L + H) into the domain's two rims in
+ * main_arrays.  Frames are neither read nor written.  One launch per cell
+ * size among the arrays.  Asynchronous on `stream`, never allocates,
+ * capturable as it stands. */
+int soda_hip_border_fused_move(soda_hip_border_fused_t* handle, int32_t strip,
+                               int32_t gather, void* const* main_arrays,
+                               void* const* strip_arrays, int32_t count,
+                               void* stream);
+/* soda_hip_border_run_padded / _run_device in chunks of the depth, under the
+ * same contracts: asynchronous on `stream`, the inputs never written, the
+ * device entry contract on the caller's arrays, param arrays passed through,
+ * never allocating in the handle.  The PROGRAM's scratch is sized by the first
+ * call for P and for every strip's extent (and that call calibrates, where the
+ * program does), after which the call can be captured.  One queue, no side
+ * streams. */
+int soda_hip_border_fused_run_padded(soda_hip_border_fused_t* handle,
+                                     void* const* outputs,
+                                     const void* const* inputs,
+                                     int32_t iterate, void* stream);
+int soda_hip_border_fused_run_device(soda_hip_border_fused_t* handle,
+                                     void* const* outputs,
+                                     const void* const* inputs,
+                                     int32_t iterate, void* stream);
 
 /* Replaces soda::app::<app>(): host arrays described by (ptr, extent, stride,
  * min) per tensor, inputs then outputs; copies in, runs, copies the outputs

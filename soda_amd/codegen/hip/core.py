@@ -14,7 +14,8 @@ opencl.py:55-142).  This module slots into the same place:
                       nothing by itself (the oracle lives in tests/); prints
                       one JSON line with timing.  --hip-periodic: on a torus.
                       --hip-border MODE[,MODE...]: with a border mode per
-                      dimension.
+                      dimension; --hip-border-depth T: fused away from the
+                      walls.
 """
 import argparse
 import json
@@ -131,6 +132,12 @@ def add_arguments(parser) -> None:
                       dest='hip_border_value', default=0.0, metavar='V',
                       help='with --hip-border: the value outside the grid in a '
                       '`constant` dimension (default 0)')
+  parser.add_argument('--hip-border-depth', type=int,
+                      dest='hip_border_depth', default=None, metavar='T',
+                      help='with --hip-border: fuse away from the walls in '
+                      'chunks of T iterations, 0 for the deepest fusion depth '
+                      '(soda_hip_border_fused_run_device; the same bits; '
+                      'default 1: one iteration per launch)')
   parser.add_argument('--hip-nt-store', action='store_true',
                       dest='hip_nt_store',
                       help='non-temporal instead of plain output stores')
@@ -266,6 +273,8 @@ def run(stencil: core.Stencil, args: argparse.Namespace) -> None:
     raise util.InputError('--hip-border runs on one GPU, without --hip-periodic, '
                           '--hip-until or --hip-residual (slabs, groups and '
                           'residuals are not served on a bordered domain yet)')
+  if border is None and getattr(args, 'hip_border_depth', None) is not None:
+    raise util.InputError('--hip-border-depth needs --hip-border')
   if border is not None:
     border = [m.strip() for m in border.split(',')]
     border = border * stencil.dim if len(border) == 1 else border
@@ -336,9 +345,11 @@ def run(stencil: core.Stencil, args: argparse.Namespace) -> None:
       extra = {'periodic': True, 'refill_every': k or max(
           p.fused_iters for p in prog.module.passes)}
     elif border is not None:
+      depth = getattr(args, 'hip_border_depth', None)
       outputs = prog.run_bordered(inputs, border,
-                                  getattr(args, 'hip_border_value', 0.0))
-      extra = {'border': border}
+                                  getattr(args, 'hip_border_value', 0.0),
+                                  depth=1 if depth is None else depth)
+      extra = {'border': border, 'border_depth': 1 if depth is None else depth}
     else:
       outputs = prog.run(inputs)
     seconds = time.time() - t0

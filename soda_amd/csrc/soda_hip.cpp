@@ -145,6 +145,9 @@ size_t soda_hip_sizeof(int which) {
     case 15: return sizeof(soda_hip_periodic_desc_t);
     case 16: return sizeof(soda_hip_periodic_info_t);
     case 17: return sizeof(soda_hip_border_desc_t);
+    case 18: return sizeof(soda_hip_border_fused_desc_t);
+    case 19: return sizeof(soda_hip_border_strip_t);
+    case 20: return sizeof(soda_hip_border_fused_info_t);
     default: return 0;
   }
 }

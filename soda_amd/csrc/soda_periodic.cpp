@@ -11,6 +11,11 @@
 // per tensor, the extend kernel (soda_rt_extend.h) in the wrap kernel's place,
 // one iteration between refills unless every mode wraps.  Everything below is
 // written once for both, told apart by a Kind.
+//
+// Fused bordered domains (soda_hip_border_fused_*) put such
+// handles together: one on the domain, whose chunks run fused, and one per
+// wall dimension on a narrow strip, which runs the loop above and mends the
+// rim; the box kernel (soda_rt_box.h) carries cells between them.
 #include "soda_internal.h"
 
 #include <cstring>
@@ -123,6 +128,8 @@ bool wrap_regions(const Torus& t, WrapJob job, int elem, WrapArgs* a) {
 }
 
 }  // namespace
+
+struct soda_hip_border_fused;
 
 struct soda_hip_periodic {
   soda_hip_program* prog = nullptr;
@@ -495,8 +502,14 @@ int fill_core(soda_hip_periodic* h, void* const* arrays, int32_t count,
                      static_cast<hipStream_t>(stream));
 }
 
+// (a fused bordered handle's chunks, below)
+int fused_chunks(soda_hip_border_fused* f, void* const* outputs,
+                 const void* const* inputs, int32_t iterate, void* stream);
+
+// `fused`: the handle whose chunks these are, if not h's own
 int run_padded_core(soda_hip_periodic* h, void* const* outputs,
-                    const void* const* inputs, int32_t iterate, void* stream) {
+                    const void* const* inputs, int32_t iterate, void* stream,
+                    soda_hip_border_fused* fused = nullptr) {
   const std::string who = std::string(h->kind->who) + "_run_padded";
   if (int rc = check_iterate(h->prog->plan, h->not_iterable, iterate,
                              who.c_str()))
@@ -504,12 +517,13 @@ int run_padded_core(soda_hip_periodic* h, void* const* outputs,
   if (int rc = check_contract(h->prog->plan, outputs, inputs, h->t.p,
                               who.c_str()))
     return rc;
+  if (fused) return fused_chunks(fused, outputs, inputs, iterate, stream);
   return run_chunks(h, outputs, inputs, iterate, stream);
 }
 
 int run_device_core(soda_hip_periodic* h, void* const* outputs,
                     const void* const* inputs, int32_t iterate,
-                    void* stream_) {
+                    void* stream_, soda_hip_border_fused* fused = nullptr) {
   const std::string who = std::string(h->kind->who) + "_run_device";
   soda_hip_program* p = h->prog;
   const soda_hip_plan_t& plan = p->plan;
@@ -538,7 +552,10 @@ int run_device_core(soda_hip_periodic* h, void* const* outputs,
   if (int rc = wrap_launch(h, kPad, pin.data(), inputs, ein.data(), nin,
                            stream))
     return rc;
-  if (int rc = run_chunks(h, pout.data(), src.data(), iterate, stream_))
+  if (int rc = fused ? fused_chunks(fused, pout.data(), src.data(), iterate,
+                                    stream_)
+                     : run_chunks(h, pout.data(), src.data(), iterate,
+                                  stream_))
     return rc;
   return wrap_launch(h, kCrop, outputs,
                      const_cast<const void* const*>(pout.data()), eout.data(),
@@ -709,6 +726,500 @@ int soda_hip_border_run_device(soda_hip_border_t* h, void* const* outputs,
   if (!h || !outputs || !inputs)
     return fail(SODA_HIP_ERR_INVALID, "border_run_device: NULL argument");
   return run_device_core(h, outputs, inputs, iterate, stream);
+}
+
+}  // extern "C"
+
+// -- bordered domains, fused away from the walls -----------
+// A handle on the domain whose chunks run fused on P, and per wall dimension a
+// handle of the same kind on a narrow strip that advances the cells near the
+// two walls one iteration at a time.  The box kernel gathers the strips from
+// the chunk's inputs and scatters their rims into its outputs.
+
+namespace {
+
+const int kBoxBlock = 256;
+const int kBoxMax = 4;
+const int64_t kBoxMaxBlocks = 1 << 15;    // the lanes stride over the items
+
+// the box kernel's one argument, as soda_rt_box.h declares it
+struct BoxArgs {
+  void* dst[16];
+  const void* src[16];
+  int32_t dext[4];
+  int32_t sext[4];
+  int32_t nbox;
+  uint32_t reserved;
+  int32_t dorg[kBoxMax][4];
+  int32_t sorg[kBoxMax][4];
+  int32_t size[kBoxMax][4];
+  uint32_t per_row[kBoxMax];
+  uint64_t start[kBoxMax];
+  uint64_t total;
+};
+
+struct Box {
+  int32_t to[4], from[4], size[4];
+};
+
+}  // namespace
+
+struct soda_hip_border_fused {
+  soda_hip_periodic* main = nullptr;
+  int32_t depth = 1;
+  int nstrips = 0;
+  struct Strip {
+    soda_hip_periodic* h = nullptr;
+    int32_t d = 0, lo = 0, hi = 0, take_lo = 0, take_hi = 0;
+  } strip[SODA_HIP_MAX_DIM];
+  hipModule_t box_module[4] = {nullptr, nullptr, nullptr, nullptr};
+  hipFunction_t box_fn[4] = {nullptr, nullptr, nullptr, nullptr};  // log2(elem)
+};
+
+namespace {
+
+// soda_hip_border_fused_plan; *all_wrap: the request is a torus
+int fused_plan_core(const soda_hip_plan_t* plan,
+                    const soda_hip_border_fused_desc_t* desc, int32_t iterate,
+                    soda_hip_border_fused_info_t* info, int32_t capacity,
+                    int32_t* chunks, int32_t* count, bool* all_wrap) {
+  if (!plan || !desc)
+    return fail(SODA_HIP_ERR_INVALID, "border_fused_plan: NULL argument");
+  if (int rc = border_modes(plan, &desc->border, all_wrap)) return rc;
+  if (desc->border.domain.refill_every > 1)
+    return fail(SODA_HIP_ERR_INVALID,
+                "border_fused: refill_every is 0 or 1 here, the depth takes "
+                "its place; nothing was launched");
+  if (desc->depth < 0)
+    return fail(SODA_HIP_ERR_INVALID,
+                "border_fused: depth < 0; nothing was launched");
+  soda_hip_border_fused_info_t out;
+  memset(&out, 0, sizeof out);
+  // everything soda_hip_border_plan asks of the plan, of N and of the frame
+  soda_hip_periodic_desc_t domain = desc->border.domain;
+  domain.refill_every = 1;
+  const Kind& kind = *all_wrap ? kTorus : kBorder;
+  if (int rc = plan_core(kind, plan, &domain, iterate, &out.main, capacity,
+                         chunks, count))
+    return rc;
+  const int dim = plan->dim;
+  int32_t depth = desc->depth;
+  if (depth == 0)
+    for (int i = 0; i < plan->num_passes; ++i)
+      if (plan->passes[i].fused_iters > depth)
+        depth = plan->passes[i].fused_iters;
+  if (depth < 1) return fail(SODA_HIP_ERR_INVALID, "border_fused: bad plan");
+  const int32_t* rlo = desc->reach_lo;
+  const int32_t* rhi = desc->reach_hi;
+  for (int d = 0; d < dim; ++d)
+    if (rlo[d] < 0 || rhi[d] < 0)
+      return fail(SODA_HIP_ERR_INVALID,
+                  "border_fused: a negative reach; nothing was launched");
+  if (plan->has_reach &&
+      (rlo[dim - 1] < plan->reach_lo || rhi[dim - 1] < plan->reach_hi))
+    return fail(SODA_HIP_ERR_INVALID,
+                "border_fused: a reach along the last dimension below the "
+                "plan's; nothing was launched");
+  // the fallbacks: a program that cannot iterate, a wall dimension too narrow
+  // for the two parts of its strip
+  const int32_t* n = domain.extent;
+  if (!*all_wrap) {
+    if (!can_iterate(*plan, domain.not_iterable != 0)) depth = 1;
+    for (int d = 0; d < dim; ++d)
+      if (desc->border.mode[d] != SODA_HIP_BORDER_WRAP &&
+          (int64_t)n[d] < 2 * (int64_t)depth * ((int64_t)rlo[d] + rhi[d]))
+        depth = 1;
+  }
+  for (int d = 0; d < dim; ++d) {
+    const int64_t times =
+        desc->border.mode[d] == SODA_HIP_BORDER_WRAP ? depth : 1;
+    if (domain.ghost_lo[d] < times * rlo[d] ||
+        domain.ghost_hi[d] < times * rhi[d]) {
+      char buf[256];
+      snprintf(buf, sizeof buf,
+               "border_fused: a frame of %d / %d cells along dimension %d, "
+               "where %d iteration(s) reach %d / %d; nothing was launched",
+               domain.ghost_lo[d], domain.ghost_hi[d], d, (int)times,
+               (int)(times * rlo[d]), (int)(times * rhi[d]));
+      return fail(SODA_HIP_ERR_INVALID, buf);
+    }
+  }
+  out.depth = depth;
+  if (*all_wrap) {
+    domain.refill_every = depth;
+    if (int rc = plan_core(kTorus, plan, &domain, iterate, &out.main, capacity,
+                           chunks, count))
+      return rc;
+  } else if (depth > 1) {
+    int32_t c = 0;
+    for (int32_t left = iterate; left > 0; left -= depth, ++c)
+      if (chunks && c < capacity) chunks[c] = left < depth ? left : depth;
+    if (count) *count = c;
+    for (int d = 0; d < dim; ++d) {
+      if (desc->border.mode[d] == SODA_HIP_BORDER_WRAP || rlo[d] + rhi[d] == 0)
+        continue;
+      soda_hip_border_strip_t& s = out.strip[out.num_strips++];
+      s.dim = d;
+      s.lo = s.hi = depth * (rlo[d] + rhi[d]);
+      s.take_lo = (depth - 1) * rlo[d];
+      s.take_hi = (depth - 1) * rhi[d];
+      soda_hip_periodic_desc_t sdom = domain;
+      sdom.extent[d] = s.lo + s.hi;
+      for (int e = 0; e < SODA_HIP_MAX_DIM; ++e)
+        s.extent[e] = e < dim ? sdom.extent[e] : 1;
+      if (int rc = plan_core(kBorder, plan, &sdom, 0, &s.info, 0, nullptr,
+                             nullptr))
+        return rc;
+    }
+  }
+  out.scratch_bytes = out.main.scratch_bytes;
+  for (int i = 0; i < out.num_strips; ++i)
+    out.scratch_bytes += out.strip[i].info.scratch_bytes;
+  if (info) *info = out;
+  return SODA_HIP_OK;
+}
+
+// `nbox` boxes from the arrays src[i] of extent `sext` into dst[i] of `dext`,
+// `count` tensors with cells of elem[i] bytes; one launch per cell size among
+// them.  A box that leaves either extent is refused before anything runs.
+int box_launch(soda_hip_border_fused* f, void* const* dst, const int32_t* dext,
+               const void* const* src, const int32_t* sext,
+               const int32_t* elem, int count, const Box* boxes, int nbox,
+               int dim, hipStream_t stream) {
+  for (int b = 0; b < nbox; ++b)
+    for (int d = 0; d < dim; ++d) {
+      const Box& x = boxes[b];
+      if (x.size[d] < 0 || x.to[d] < 0 || x.from[d] < 0 ||
+          (int64_t)x.to[d] + x.size[d] > dext[d] ||
+          (int64_t)x.from[d] + x.size[d] > sext[d])
+        return fail(SODA_HIP_ERR_INVALID,
+                    "border_fused: a box leaves its array; nothing was "
+                    "launched");
+    }
+  for (int size = 1; size <= 8; size *= 2) {
+    BoxArgs a;
+    memset(&a, 0, sizeof a);
+    int m = 0;
+    for (int i = 0; i < count; ++i)
+      if (elem[i] == size) {
+        a.dst[m] = dst[i];
+        a.src[m] = src[i];
+        ++m;
+      }
+    if (!m) continue;
+    const int v = 16 / size;
+    for (int d = 0; d < 4; ++d) {
+      a.dext[d] = d < dim ? dext[d] : 1;
+      a.sext[d] = d < dim ? sext[d] : 1;
+    }
+    for (int b = 0; b < nbox && a.nbox < kBoxMax; ++b) {
+      int64_t rows = 1;
+      bool empty = false;
+      for (int d = 0; d < dim; ++d) {
+        if (boxes[b].size[d] < 1) empty = true;
+        if (d) rows *= boxes[b].size[d];
+      }
+      if (empty) continue;
+      if (rows > 0x7fffffffLL)
+        return fail(SODA_HIP_ERR_INVALID,
+                    "border_fused: 2^31 rows or more; nothing was launched");
+      const int k = a.nbox++;
+      for (int d = 0; d < 4; ++d) {
+        a.dorg[k][d] = d < dim ? boxes[b].to[d] : 0;
+        a.sorg[k][d] = d < dim ? boxes[b].from[d] : 0;
+        a.size[k][d] = d < dim ? boxes[b].size[d] : 1;
+      }
+      // fragments a row may need: it starts up to v - 1 cells behind a
+      // 16-byte boundary
+      a.per_row[k] = (uint32_t)(((int64_t)boxes[b].size[0] + 2 * v - 2) / v);
+      a.start[k] = a.total;
+      a.total += (uint64_t)rows * a.per_row[k];
+    }
+    if (!a.total) continue;
+    hipFunction_t fn = f->box_fn[log2_elem(size)];
+    if (!fn) return fail(SODA_HIP_ERR_INVALID, "border_fused: no box kernel");
+    int64_t blocks = (int64_t)((a.total + kBoxBlock - 1) / kBoxBlock);
+    if (blocks > kBoxMaxBlocks) blocks = kBoxMaxBlocks;
+    size_t bytes = sizeof a;
+    void* extra[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &a,
+                     HIP_LAUNCH_PARAM_BUFFER_SIZE, &bytes,
+                     HIP_LAUNCH_PARAM_END};
+    HIP_TRY(hipModuleLaunchKernel(fn, (unsigned)blocks, (unsigned)m, 1,
+                                  kBoxBlock, 1, 1, 0, stream, nullptr, extra));
+  }
+  return SODA_HIP_OK;
+}
+
+// The two boxes of a strip in padded coordinates: the gather takes the
+// domain's cells [0, L) and [N - H, N) along d into the strip's [0, L + H),
+// the scatter the strip's [0, take_lo) and [L + H - take_hi, L + H) back to
+// the domain's two rims; every other dimension over the whole domain.
+void strip_boxes(const soda_hip_border_fused* f,
+                 const soda_hip_border_fused::Strip& s, bool gather,
+                 Box* low, Box* high) {
+  const Torus& m = f->main->t;
+  const int d = s.d;
+  for (int e = 0; e < 4; ++e) {
+    low->to[e] = low->from[e] = high->to[e] = high->from[e] = m.glo[e];
+    low->size[e] = high->size[e] = m.n[e];
+  }
+  const int32_t g = m.glo[d], n = m.n[d], w = s.lo + s.hi;
+  if (gather) {                 // main -> strip
+    low->size[d] = s.lo;
+    high->size[d] = s.hi;
+    high->to[d] = g + s.lo;
+    high->from[d] = g + n - s.hi;
+  } else {                      // strip -> main
+    low->size[d] = s.take_lo;
+    high->size[d] = s.take_hi;
+    high->to[d] = g + n - s.take_hi;
+    high->from[d] = g + w - s.take_hi;
+  }
+}
+
+// The chunks of a fused run on padded arrays (run_chunks' contract): per chunk
+// of n <= depth iterations the strips gathered from the chunk's inputs and
+// advanced n times, the interior launched on P, the strips' rims scattered
+// over its result, the frame filled.  One stream, in that order.
+int fused_chunks(soda_hip_border_fused* f, void* const* outputs,
+                 const void* const* inputs, int32_t iterate, void* stream_) {
+  soda_hip_periodic* h = f->main;
+  if (!f->nstrips) return run_chunks(h, outputs, inputs, iterate, stream_);
+  soda_hip_program* p = h->prog;
+  const soda_hip_plan_t& plan = p->plan;
+  HIP_TRY(hipSetDevice(p->device));
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  const int nin = plan.num_inputs, nout = plan.num_outputs, dim = plan.dim;
+  const int chunks = (iterate + f->depth - 1) / f->depth;
+  std::vector<const void*> src(inputs, inputs + nin + plan.num_params);
+  std::vector<const void*> ssrc(src);
+  std::vector<void*> dst(nout), sin(nin), sout(nout);
+  std::vector<int32_t> ein(nin), eout(nout);
+  for (int i = 0; i < nin; ++i) ein[i] = plan.elem_size[i];
+  for (int o = 0; o < nout; ++o) eout[o] = plan.elem_size[nin + o];
+  int32_t left = iterate;
+  for (int c = 0; c < chunks; ++c) {
+    const int32_t n = left < f->depth ? left : f->depth;
+    const bool to_out = ((chunks - 1 - c) % 2) == 0;
+    for (int o = 0; o < nout; ++o)
+      dst[o] = to_out ? outputs[o] : h->pong[o].ptr;
+    for (int k = 0; k < f->nstrips; ++k) {
+      const soda_hip_border_fused::Strip& s = f->strip[k];
+      Box box[2];
+      strip_boxes(f, s, true, &box[0], &box[1]);
+      for (int i = 0; i < nin; ++i) {
+        sin[i] = s.h->pad_in[i].ptr;
+        ssrc[i] = sin[i];
+      }
+      for (int o = 0; o < nout; ++o) sout[o] = s.h->pad_out[o].ptr;
+      if (int rc = box_launch(f, sin.data(), s.h->t.p, src.data(), h->t.p,
+                              ein.data(), nin, box, 2, dim, stream))
+        return rc;
+      if (int rc = wrap_launch(s.h, kFill, sin.data(), ssrc.data(), ein.data(),
+                               nin, stream))
+        return rc;
+      if (int rc = run_chunks(s.h, sout.data(), ssrc.data(), n, stream_))
+        return rc;
+    }
+    if (int rc = run_core(p, {dst.data(), src.data(), h->t.p, n, stream_}))
+      return rc;
+    for (int k = 0; k < f->nstrips; ++k) {
+      const soda_hip_border_fused::Strip& s = f->strip[k];
+      Box box[2];
+      strip_boxes(f, s, false, &box[0], &box[1]);
+      for (int o = 0; o < nout; ++o) sout[o] = s.h->pad_out[o].ptr;
+      if (int rc = box_launch(f, dst.data(), h->t.p,
+                              const_cast<const void* const*>(sout.data()),
+                              s.h->t.p, eout.data(), nout, box, 2, dim,
+                              stream))
+        return rc;
+    }
+    if (int rc = wrap_launch(h, kFill, dst.data(), dst.data(), eout.data(),
+                             nout, stream))
+      return rc;
+    left -= n;
+    if (c + 1 < chunks)
+      for (int i = 0; i < nin; ++i) src[i] = dst[i];
+  }
+  return SODA_HIP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int soda_hip_border_fused_plan(const soda_hip_plan_t* plan,
+                               const soda_hip_border_fused_desc_t* desc,
+                               int32_t iterate,
+                               soda_hip_border_fused_info_t* info,
+                               int32_t capacity, int32_t* chunks,
+                               int32_t* count) {
+  bool all_wrap;
+  return fused_plan_core(plan, desc, iterate, info, capacity, chunks, count,
+                         &all_wrap);
+}
+
+int soda_hip_border_fused_create(soda_hip_program_t* p,
+                                 const soda_hip_border_fused_desc_t* desc,
+                                 const void* const* code,
+                                 const size_t* code_size,
+                                 const void* const* box_code,
+                                 const size_t* box_code_size,
+                                 soda_hip_border_fused_t** handle) {
+  if (handle) *handle = nullptr;
+  if (!p || !desc || !code || !code_size || !box_code || !box_code_size ||
+      !handle)
+    return fail(SODA_HIP_ERR_INVALID, "border_fused_create: NULL argument");
+  const soda_hip_plan_t& plan = p->plan;
+  soda_hip_border_fused_info_t info;
+  bool all_wrap;
+  if (int rc = fused_plan_core(&plan, desc, 0, &info, 0, nullptr, nullptr,
+                               &all_wrap))
+    return rc;
+  bool need[4] = {false, false, false, false};
+  for (int s = 0; info.num_strips && s < plan.num_inputs + plan.num_outputs;
+       ++s) {
+    const int l = log2_elem(plan.elem_size[s]);
+    if (l < 0)
+      return fail(SODA_HIP_ERR_UNSUPPORTED,
+                  "border_fused: cells of 1, 2, 4 or 8 bytes only");
+    if (!box_code[l] || !box_code_size[l])
+      return fail(SODA_HIP_ERR_INVALID,
+                  "border_fused_create: the box module of a cell size of the "
+                  "program is missing");
+    need[l] = true;
+  }
+  soda_hip_border_fused* f = new (std::nothrow) soda_hip_border_fused;
+  if (!f) return fail(SODA_HIP_ERR_NOMEM, "new border_fused handle");
+  f->depth = info.depth;
+  soda_hip_periodic_desc_t domain = desc->border.domain;
+  domain.refill_every = all_wrap ? info.depth : 1;
+  int rc = create_core(kBorder, p, &domain, desc->border.mode,
+                       desc->border.constant, code, code_size, &f->main);
+  for (int i = 0; i < info.num_strips && !rc; ++i) {
+    const soda_hip_border_strip_t& s = info.strip[i];
+    soda_hip_border_fused::Strip& mine = f->strip[i];
+    soda_hip_periodic_desc_t sdom = domain;
+    sdom.extent[s.dim] = s.lo + s.hi;
+    rc = create_core(kBorder, p, &sdom, desc->border.mode,
+                     desc->border.constant, code, code_size, &mine.h);
+    if (rc) break;
+    mine.d = s.dim;
+    mine.lo = s.lo;
+    mine.hi = s.hi;
+    mine.take_lo = s.take_lo;
+    mine.take_hi = s.take_hi;
+    f->nstrips = i + 1;
+  }
+  for (int l = 0; l < 4 && !rc; ++l) {
+    if (!need[l]) continue;
+    hipError_t e = hipModuleLoadData(&f->box_module[l], box_code[l]);
+    if (e != hipSuccess) {
+      rc = hip_fail(e, "border_fused_create: hipModuleLoadData");
+      break;
+    }
+    char name[64];
+    snprintf(name, sizeof name, "soda_box_e%d_d%d", 1 << l, plan.dim);
+    e = hipModuleGetFunction(&f->box_fn[l], f->box_module[l], name);
+    if (e != hipSuccess)
+      rc = hip_fail(e, "border_fused_create: hipModuleGetFunction (is this "
+                       "the box module of the cell size and dimension "
+                       "count?)");
+  }
+  if (rc) {
+    const std::string why = last_error_text();
+    soda_hip_border_fused_destroy(f);
+    return fail(rc, why);
+  }
+  *handle = f;
+  return SODA_HIP_OK;
+}
+
+int soda_hip_border_fused_destroy(soda_hip_border_fused_t* f) {
+  if (!f) return SODA_HIP_OK;
+  for (auto& s : f->strip) soda_hip_periodic_destroy(s.h);
+  if (f->main) (void)hipSetDevice(f->main->prog->device);
+  for (auto& m : f->box_module)
+    if (m) (void)hipModuleUnload(m);
+  soda_hip_periodic_destroy(f->main);
+  delete f;
+  return SODA_HIP_OK;
+}
+
+int soda_hip_border_fused_info(soda_hip_border_fused_t* f,
+                               soda_hip_border_fused_info_t* info) {
+  if (!f || !info)
+    return fail(SODA_HIP_ERR_INVALID, "border_fused_info: NULL argument");
+  memset(info, 0, sizeof *info);
+  if (int rc = soda_hip_periodic_info(f->main, &info->main)) return rc;
+  info->depth = f->depth;
+  info->num_strips = f->nstrips;
+  info->scratch_bytes = info->main.scratch_bytes;
+  for (int i = 0; i < f->nstrips; ++i) {
+    const soda_hip_border_fused::Strip& s = f->strip[i];
+    soda_hip_border_strip_t& out = info->strip[i];
+    out.dim = s.d;
+    out.lo = s.lo;
+    out.hi = s.hi;
+    out.take_lo = s.take_lo;
+    out.take_hi = s.take_hi;
+    for (int e = 0; e < SODA_HIP_MAX_DIM; ++e) out.extent[e] = s.h->t.n[e];
+    if (int rc = soda_hip_periodic_info(s.h, &out.info)) return rc;
+    info->scratch_bytes += out.info.scratch_bytes;
+  }
+  return SODA_HIP_OK;
+}
+
+int soda_hip_border_fused_move(soda_hip_border_fused_t* f, int32_t strip,
+                               int32_t gather, void* const* main_arrays,
+                               void* const* strip_arrays, int32_t count,
+                               void* stream) {
+  if (!f || !main_arrays || !strip_arrays)
+    return fail(SODA_HIP_ERR_INVALID, "border_fused_move: NULL argument");
+  const soda_hip_plan_t& plan = f->main->prog->plan;
+  if (strip < 0 || strip >= f->nstrips || count < 0 ||
+      count > plan.num_outputs)
+    return fail(SODA_HIP_ERR_INVALID,
+                "border_fused_move: no such strip, or more arrays than "
+                "outputs; nothing was launched");
+  int32_t elem[SODA_HIP_MAX_TENSORS];
+  for (int i = 0; i < count; ++i) {
+    elem[i] = plan.elem_size[plan.num_inputs + i];
+    if (!main_arrays[i] || !strip_arrays[i] ||
+        reinterpret_cast<uintptr_t>(main_arrays[i]) % elem[i] ||
+        reinterpret_cast<uintptr_t>(strip_arrays[i]) % elem[i])
+      return fail(SODA_HIP_ERR_INVALID,
+                  "border_fused_move: an array is NULL or not aligned to its "
+                  "cell size; nothing was launched");
+  }
+  HIP_TRY(hipSetDevice(f->main->prog->device));
+  const soda_hip_border_fused::Strip& s = f->strip[strip];
+  Box box[2];
+  strip_boxes(f, s, gather != 0, &box[0], &box[1]);
+  void* const* dst = gather ? strip_arrays : main_arrays;
+  void* const* src = gather ? main_arrays : strip_arrays;
+  return box_launch(f, dst, gather ? s.h->t.p : f->main->t.p,
+                    const_cast<const void* const*>(src),
+                    gather ? f->main->t.p : s.h->t.p, elem, count, box, 2,
+                    plan.dim, static_cast<hipStream_t>(stream));
+}
+
+int soda_hip_border_fused_run_padded(soda_hip_border_fused_t* f,
+                                     void* const* outputs,
+                                     const void* const* inputs,
+                                     int32_t iterate, void* stream) {
+  if (!f || !outputs || !inputs)
+    return fail(SODA_HIP_ERR_INVALID, "border_fused_run_padded: NULL argument");
+  return run_padded_core(f->main, outputs, inputs, iterate, stream, f);
+}
+
+int soda_hip_border_fused_run_device(soda_hip_border_fused_t* f,
+                                     void* const* outputs,
+                                     const void* const* inputs,
+                                     int32_t iterate, void* stream) {
+  if (!f || !outputs || !inputs)
+    return fail(SODA_HIP_ERR_INVALID, "border_fused_run_device: NULL argument");
+  return run_device_core(f->main, outputs, inputs, iterate, stream, f);
 }
 
 }  // extern "C"

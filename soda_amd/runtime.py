@@ -267,6 +267,37 @@ class BorderDesc(ctypes.Structure):
               ('constant', ctypes.c_uint64 * MAX_TENSORS)]
 
 
+class BorderFusedDesc(ctypes.Structure):
+  """Mirror of soda_hip_border_fused_desc_t: a bordered request, the fusion
+  depth, what one iteration reaches."""
+  _fields_ = [('border', BorderDesc),
+              ('depth', ctypes.c_int32),
+              ('reach_lo', ctypes.c_int32 * MAX_DIM),
+              ('reach_hi', ctypes.c_int32 * MAX_DIM),
+              ('reserved', ctypes.c_int32)]
+
+
+class BorderStrip(ctypes.Structure):
+  """Mirror of soda_hip_border_strip_t: the strip of one wall dimension."""
+  _fields_ = [('dim', ctypes.c_int32),
+              ('lo', ctypes.c_int32),
+              ('hi', ctypes.c_int32),
+              ('take_lo', ctypes.c_int32),
+              ('take_hi', ctypes.c_int32),
+              ('reserved', ctypes.c_int32),
+              ('extent', ctypes.c_int32 * MAX_DIM),
+              ('info', PeriodicInfo)]
+
+
+class BorderFusedInfo(ctypes.Structure):
+  """Mirror of soda_hip_border_fused_info_t."""
+  _fields_ = [('main', PeriodicInfo),
+              ('depth', ctypes.c_int32),
+              ('num_strips', ctypes.c_int32),
+              ('strip', BorderStrip * MAX_DIM),
+              ('scratch_bytes', ctypes.c_int64)]
+
+
 # every symbol include/soda_hip.h declares: name -> (restype, argtypes)
 _vp = ctypes.c_void_p
 _i32 = ctypes.c_int32
@@ -388,6 +419,27 @@ API = {
     'soda_hip_border_run_device': (ctypes.c_int, [_vp, _pvp, _pvp, _i32, _vp]),
     'soda_hip_periodic_run_device': (ctypes.c_int, [_vp, _pvp, _pvp, _i32,
                                                     _vp]),
+    'soda_hip_box_host': (ctypes.c_int, [_vp, _pi32, _vp, _pi32, _i32, _i32,
+                                         _i32, _pi32, _pi32, _pi32]),
+    'soda_hip_border_fused_plan': (ctypes.c_int, [
+        ctypes.POINTER(Plan), ctypes.POINTER(BorderFusedDesc), _i32,
+        ctypes.POINTER(BorderFusedInfo), _i32, _pi32, _pi32
+    ]),
+    'soda_hip_border_fused_create': (ctypes.c_int, [
+        _vp, ctypes.POINTER(BorderFusedDesc), _pvp,
+        ctypes.POINTER(ctypes.c_size_t), _pvp, ctypes.POINTER(ctypes.c_size_t),
+        ctypes.POINTER(_vp)
+    ]),
+    'soda_hip_border_fused_destroy': (ctypes.c_int, [_vp]),
+    'soda_hip_border_fused_info': (ctypes.c_int, [
+        _vp, ctypes.POINTER(BorderFusedInfo)
+    ]),
+    'soda_hip_border_fused_move': (ctypes.c_int, [_vp, _i32, _i32, _pvp, _pvp,
+                                                  _i32, _vp]),
+    'soda_hip_border_fused_run_padded': (ctypes.c_int, [_vp, _pvp, _pvp, _i32,
+                                                        _vp]),
+    'soda_hip_border_fused_run_device': (ctypes.c_int, [_vp, _pvp, _pvp, _i32,
+                                                        _vp]),
     'soda_hip_run_device_window': (ctypes.c_int, [_vp, _pvp, _pvp, _pi32, _pi32,
                                                   _pi32, _i32, _vp]),
     'soda_hip_run_device_cone': (ctypes.c_int, [_vp, _pvp, _pvp, _pi32, _pi32,
@@ -526,7 +578,8 @@ def library() -> ctypes.CDLL:
                           (10, LaunchInfo), (11, ResidualStruct),
                           (12, ResBox), (14, NormsStruct),
                           (15, PeriodicDesc), (16, PeriodicInfo),
-                          (17, BorderDesc)):
+                          (17, BorderDesc), (18, BorderFusedDesc),
+                          (19, BorderStrip), (20, BorderFusedInfo)):
       if lib.soda_hip_sizeof(which) != ctypes.sizeof(mirror):
         raise util.BackendError(
             'struct layout mismatch between libsoda_hip.so and runtime.py '
@@ -1722,6 +1775,212 @@ class Bordered(Periodic):
     prog._periodic.append(self)
 
 
+# -- bordered domains, fused away from the walls -------------
+def box_host(dst, src, boxes):
+  """Copies boxes between two C-contiguous numpy arrays of one cell type and
+  dimension count but different shapes (soda_hip_box_host, plain C++; no GPU
+  needed).  `boxes`: (dst_origin, src_origin, size) each, dimension 0 (the LAST
+  numpy axis) first; a box with a size of 0 is empty.  Returns `dst`."""
+  import numpy as np
+  for arr, write in ((dst, True), (src, False)):
+    if not isinstance(arr, np.ndarray) or not arr.flags['C_CONTIGUOUS'] or \
+        (write and not arr.flags['WRITEABLE']):
+      raise util.InputError('box_host: C-contiguous numpy arrays, the '
+                            'destination writable')
+  dim = dst.ndim
+  if src.ndim != dim or src.dtype != dst.dtype or not 1 <= dim <= MAX_DIM or \
+      dst.dtype.itemsize not in (1, 2, 4, 8) or not dst.size or not src.size:
+    raise util.InputError(
+        'box_host: two arrays of one cell type of 1, 2, 4 or 8 bytes and of '
+        '1 to %d dimensions' % MAX_DIM)
+  if np.shares_memory(dst, src):
+    raise util.InputError('box_host: the arrays overlap')
+  boxes = [tuple(tuple(int(v) for v in part) for part in box) for box in boxes]
+  if any(len(box) != 3 or any(len(part) != dim for part in box)
+         for box in boxes):
+    raise util.InputError('box_host: a box is (dst_origin, src_origin, size), '
+                          '%d entries each' % dim)
+  flat = lambda k: (ctypes.c_int32 * max(1, len(boxes) * dim))(
+      *[v for box in boxes for v in box[k]])
+  check(library().soda_hip_box_host(
+      dst.ctypes.data, (ctypes.c_int32 * dim)(*dst.shape[::-1]),
+      src.ctypes.data, (ctypes.c_int32 * dim)(*src.shape[::-1]),
+      dst.dtype.itemsize, dim, len(boxes), flat(0), flat(1), flat(2)),
+        'box_host')
+  return dst
+
+
+def box_resources(elem: int, dim: int):
+  """(code object, kernel_resources of it) of the box module of a cell size
+  and dimension count: JIT-built like every module, cached like them; needs
+  no GPU."""
+  from soda_amd.codegen.hip import box as _box
+  code = compile_source(_box.source(elem, dim), 'box_e%d_%dd.hip' % (elem, dim))
+  return code, kernel_resources(code)
+
+
+def border_fused_ghosts(stencil: core.Stencil, modes, depth: int):
+  """(reach_lo, reach_hi, ghost_lo, ghost_hi) of a fused bordered domain at
+  `depth` >= 1: the reach of ONE iteration (periodic_ghosts(stencil, 1)), and
+  a frame that wide in a wall dimension, `depth` times as wide in a `wrap`
+  dimension.  Refuses (InputError) a program whose window of `depth`
+  iterations exceeds `depth` times the window of one: the widths of the strips
+  rest on that bound.  (Coupled outputs may reach less: the most over all
+  outputs bounds every one of them.)"""
+  raw = _border_modes(modes, stencil.dim)
+  if depth < 1:
+    raise util.InputError('border: depth < 1')
+  rlo, rhi = periodic_ghosts(stencil, 1)
+  for k in sorted({depth, 2}):
+    klo, khi = periodic_ghosts(stencil, k)
+    if any(a > k * r for a, r in zip(klo + khi, rlo + rhi)):
+      raise util.InputError(
+          'border: %d iterations of `%s` reach more than %d times what one '
+          'reaches; fused borders are not served (depth=1 is)' % (
+              k, stencil.app_name, k))
+  lo = [r if m else depth * r for r, m in zip(rlo, raw)]
+  hi = [r if m else depth * r for r, m in zip(rhi, raw)]
+  return rlo, rhi, lo, hi
+
+
+def _border_fused_desc(border: BorderDesc, depth: int, reach_lo,
+                       reach_hi) -> BorderFusedDesc:
+  desc = BorderFusedDesc()
+  desc.border = border
+  desc.depth = depth
+  for d, (l, h) in enumerate(zip(reach_lo, reach_hi)):
+    desc.reach_lo[d], desc.reach_hi[d] = l, h
+  return desc
+
+
+def _border_fused_info(raw: BorderFusedInfo, dim: int) -> dict:
+  out = _periodic_info(raw.main, dim)
+  out['depth'] = raw.depth
+  out['scratch_bytes'] = int(raw.scratch_bytes)
+  out['strips'] = []
+  for s in raw.strip[:raw.num_strips]:
+    strip = _periodic_info(s.info, dim)
+    del strip['refill_every']
+    strip.update(dim=s.dim, lo=s.lo, hi=s.hi, take_lo=s.take_lo,
+                 take_hi=s.take_hi, extent=tuple(s.extent[:dim]))
+    out['strips'].append(strip)
+  return out
+
+
+def border_fused_plan(plan: Plan, extent: Sequence[int], modes, depth: int,
+                      reach_lo: Sequence[int], reach_hi: Sequence[int],
+                      ghost_lo: Sequence[int], ghost_hi: Sequence[int],
+                      iterate: int = 0, refill_every: int = 0,
+                      preserve: bool = False, not_iterable: bool = False):
+  """border_plan for the fused form (soda_hip_border_fused_plan; no GPU
+  needed): (info, chunks), info as BorderedFused.info().  `depth` 0: the
+  plan's deepest pass."""
+  raw_modes = list(modes) if not isinstance(modes, str) and all(
+      isinstance(m, int) for m in modes) else _border_modes(modes, plan.dim)
+  if len(raw_modes) != plan.dim or len(reach_lo) != plan.dim or \
+      len(reach_hi) != plan.dim:
+    raise util.InputError('border: one mode and one reach per side per '
+                          'dimension (%d)' % plan.dim)
+  desc = _border_fused_desc(_border_desc(_periodic_desc(
+      plan.dim, extent, refill_every, ghost_lo, ghost_hi, preserve,
+      not_iterable), raw_modes, ()), depth, reach_lo, reach_hi)
+  raw = BorderFusedInfo()
+  cap = max(1, iterate)
+  chunks = (ctypes.c_int32 * cap)()
+  n = ctypes.c_int32()
+  check(library().soda_hip_border_fused_plan(
+      ctypes.byref(plan), ctypes.byref(desc), iterate, ctypes.byref(raw), cap,
+      chunks, ctypes.byref(n)), 'border_fused_plan')
+  return _border_fused_info(raw, plan.dim), list(chunks[:n.value])
+
+
+class BorderedFused(Bordered):
+  """Bordered, fused away from the walls (soda_hip_border_fused_create;
+  DESIGN.md 4.13): a chunk of up to `depth` iterations is one fused run of the
+  padded domain, mended along every wall by a narrow strip that advances one
+  iteration at a time.  The bits are Bordered's, whatever the depth.  Made by
+  `Program.bordered(..., depth=)`; close it before its program."""
+
+  _entry = 'soda_hip_border_fused_'
+  _what = 'border_fused'
+
+  def __init__(self, prog: 'Program', extent: Sequence[int], modes,
+               constants=None, depth: int = 0):
+    """`depth`: iterations of a chunk; 0: the deepest fusion depth of the
+    program, so that the interior of a chunk is one launch.  A program that
+    fuses little gains little and may lose: the strips cost `depth` small
+    launches and fills per wall dimension and chunk whatever the program fuses
+    (DESIGN.md 4.13 has heat3d at depth 2).  info()['depth'] is the depth as
+    resolved: 1, and Bordered's loop, where the program cannot iterate or a
+    wall dimension is narrower than the two parts of its strip."""
+    st = prog.stencil
+    self.prog, self.extent = prog, tuple(int(e) for e in extent)
+    prog._check_extent(self.extent)
+    self.modes = tuple([modes] * st.dim if isinstance(modes, str) else modes)
+    raw_modes = _border_modes(modes, st.dim)
+    depth = int(depth)
+    if depth < 0:
+      raise util.InputError('border: depth < 0')
+    if not depth:
+      depth = max(p.fused_iters for p in prog.module.passes)
+    rlo, rhi, lo, hi = border_fused_ghosts(st, modes, depth)
+    desc = _border_fused_desc(_border_desc(_periodic_desc(
+        st.dim, self.extent, 0, lo, hi, st.preserve_border,
+        not_iterable=list(st.input_types) != list(st.output_types)),
+                                           raw_modes,
+                                           _border_constants(st, constants)),
+                              depth, rlo, rhi)
+    codes, sizes = self._codes_of(extend_resources)
+    extend_codes = self._codes
+    box_codes, box_sizes = self._codes_of(box_resources)
+    self._codes = extend_codes + self._codes
+    self._lib = library()
+    self._handle = ctypes.c_void_p()
+    check(self._lib.soda_hip_border_fused_create(
+        prog._handle, ctypes.byref(desc), codes, sizes, box_codes, box_sizes,
+        ctypes.byref(self._handle)),
+          '`%s` on %s with borders %s, fused %d deep' % (
+              st.app_name, 'x'.join(map(str, self.extent)),
+              ', '.join(self.modes), depth))
+    prog._periodic.append(self)
+
+  def info(self) -> dict:
+    """Bordered.info() of the handle on the domain, and: 'depth' as resolved,
+    'strips' (per strip: dim, lo, hi, take_lo, take_hi, extent, ghost_lo,
+    ghost_hi, padded, scratch_bytes), 'scratch_bytes' of all of them."""
+    raw = BorderFusedInfo()
+    check(self._fn('info')(self._handle, ctypes.byref(raw)),
+          '%s: info' % self._what)
+    return _border_fused_info(raw, self.prog.stencil.dim)
+
+  def fill(self, arrays: Sequence[int], stream: int = 0) -> None:
+    raise util.InputError('border_fused: no fill entry; Bordered has one')
+
+  def _move(self, strip, gather, main_arrays, strip_arrays, stream):
+    if len(main_arrays) != len(strip_arrays):
+      raise util.InputError('border_fused: one strip array per main array')
+    n = len(main_arrays)
+    check(self._fn('move')(
+        self._handle, strip, gather,
+        (ctypes.c_void_p * max(1, n))(*main_arrays),
+        (ctypes.c_void_p * max(1, n))(*strip_arrays), n,
+        ctypes.c_void_p(stream)), '%s: move' % self._what)
+
+  def gather(self, strip: int, strip_arrays: Sequence[int],
+             main_arrays: Sequence[int], stream: int = 0) -> None:
+    """The two rims of padded device arrays of info()['padded'] along the
+    dimension of strip `strip` into the domain of padded arrays of the
+    strip's extent (pair i: the cells of output i); asynchronous on
+    `stream` (soda_hip_border_fused_move)."""
+    self._move(strip, 1, main_arrays, strip_arrays, stream)
+
+  def scatter(self, strip: int, main_arrays: Sequence[int],
+              strip_arrays: Sequence[int], stream: int = 0) -> None:
+    """The strip's rims, take_lo and take_hi cells wide, back into the two
+    rims of the domain's padded arrays."""
+    self._move(strip, 0, main_arrays, strip_arrays, stream)
+
+
 class Program:
   """A SODA program JIT-built for gfx950 and loaded on one GPU."""
 
@@ -2227,20 +2486,26 @@ class Program:
     return result
 
   # -- bordered domains ------------------------------------------------------
-  def bordered(self, extent: Sequence[int], modes, constants=None) -> Bordered:
+  def bordered(self, extent: Sequence[int], modes, constants=None,
+               depth: int = 1) -> Bordered:
     """This program on a domain of `extent` with a border mode per dimension
-    (runtime.Bordered).  The handle is closed with the program
+    (runtime.Bordered).  `depth` other than 1: fused away from
+    the walls in chunks of `depth` iterations, 0 for the program's deepest
+    (runtime.BorderedFused) -- the same bits, faster where the
+    program fuses deep.  The handle is closed with the program
     at the latest."""
-    return Bordered(self, extent, modes, constants)
+    if depth == 1:
+      return Bordered(self, extent, modes, constants)
+    return BorderedFused(self, extent, modes, constants, depth)
 
   def run_bordered(self, inputs: Dict[str, 'numpy.ndarray'], modes,
-                   constants=None, iterate: Optional[int] = None
-                   ) -> Dict[str, 'numpy.ndarray']:
+                   constants=None, iterate: Optional[int] = None,
+                   depth: int = 1) -> Dict[str, 'numpy.ndarray']:
     """`run` with borders: numpy arrays of the domain in, the outputs out,
     EVERY cell of them defined -- each iteration sees its inputs extended by
     `modes` (one name, or one per dimension, dimension 0 first) and
     `constants` (a scalar or {input: scalar}; default zero).  A plain allocate
-    / copy in / Bordered.run_device / copy out."""
+    / copy in / Bordered.run_device / copy out.  `depth`: as for `bordered`."""
     import numpy as np
     st = self.stencil
     lib = self._lib
@@ -2252,7 +2517,7 @@ class Program:
     result = {n: np.empty(first.shape, dtype=np.dtype(t.np_name))
               for n, t in zip(st.output_names, st.output_types)}
     dense = list(result.values())
-    with self.bordered(extent, modes, constants) as bor, \
+    with self.bordered(extent, modes, constants, depth) as bor, \
         _staged(lib, self.device, host_in, dense, 'run_bordered',
                 synchronize=True) as (dev_in, dev_out):
       bor.run_device(dev_out, dev_in, iterate)
