@@ -42,7 +42,8 @@ Floating-point results are bit-identical to the CPU oracle because the kernels
 compile the same C expression text with -ffp-contract=off.
 
 Layout of the package: module.py (Module, descriptors, the device runtime
-text), march.py (`march2d` / `march3d`), ldswin.py, tile3d.py, direct.py; this
+text), march_schedule.py and march.py (`march2d` / `march3d`: what a kernel is,
+built in named steps, and its text), ldswin.py, tile3d.py, direct.py; this
 file holds the options and `lower()`, which picks the family and the shape
  in named steps: check_options, _lower_ldswin, _derive,
 _add_march_passes (the shape from _one_iteration_shape, every kernel a

@@ -1,8 +1,8 @@
 """`tile3d`: LDS-tiled 3-D kernels that fuse more than two iterations.
 
 `march3d` keeps a tile of rows x planes per tensor per fused iteration in
-REGISTERS: two iterations of heat3d already need 260 VGPRs (march.py,
-MAX_FUSE_3D).  Here the planes live in LDS (3.5-D blocking):
+REGISTERS: two iterations of heat3d already need 260 VGPRs
+(march_schedule.py, MAX_FUSE_3D).  Here the planes live in LDS (3.5-D blocking):
 
   * a block of W waves owns a tile of TX x TY cells in (x, y) -- ghost cells
     included -- and marches along dimension 2 in chunks, one plane per step;

@@ -226,7 +226,8 @@ def march_valu_per_launch(profile: Dict[str, Dict[str, int]],
   """Wave-instructions of class `kind` one launch issues: every live wave runs
   the prologue (peeled warm-up included) once and ceil((chunk + warm - peeled)
   / unroll) trips of the loop (march.py `_emit_wave`: tau from m_begin + m_lo +
-  lead + peeled to m_end + max_delay, `warm` = max_delay - m_lo - lead)."""
+  lead + peeled to m_end + max_delay; march_schedule.py `_warm_up`: `warm` =
+  max_delay - m_lo - lead)."""
   pre = profile['pre'].get(kind, 0) + profile['post'].get(kind, 0)
   loop = profile['loop'].get(kind, 0)
   total = 0.0

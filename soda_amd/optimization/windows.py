@@ -115,7 +115,7 @@ def decompose(stencil: core.Stencil, skip=()) -> core.Stencil:
   """The derived program (a new Stencil), or `stencil` itself if no statement
   qualifies.  `skip`: (dimension, op) pairs left as written, op None = any --
   the marching kernels reduce dimension-0 windows for all cells of a lane
-  jointly (march._emit_xwindow: cheaper than chains there, where every far tap
+  jointly (march._xwindow_body: cheaper than chains there, where every far tap
   is a lane move) and keep sums along the streamed dimension as sliding sums
   (two operations per cell, no auxiliary tensors)."""
   table = stencil.symbol_table
