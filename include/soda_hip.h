@@ -800,8 +800,10 @@ int soda_hip_run_device_until_norm(soda_hip_program_t* program,
  * the frame with one small kernel (codegen/hip/wrap.py, a module of its own
  * per cell size and dimension count), and go on.  The result does not depend
  * on k, bit for bit.
- * Not served on a torus: residuals, norms, run_until, slabs, groups, ranks,
- * batches, the wire format, `border: preserve` (a torus has no border). */
+ * Residuals, norms and runs until converged: the block "residual, norms and
+ * run_until on a domain" below.
+ * Not served on a torus: slabs, groups, ranks, batches, the wire format,
+ * `border: preserve` (a torus has no border). */
 typedef struct soda_hip_periodic_desc {
   int32_t extent[SODA_HIP_MAX_DIM];    /* N, the torus */
   int32_t refill_every;                /* k: iterations between two refills;
@@ -934,8 +936,10 @@ int soda_hip_periodic_run_device(soda_hip_periodic_t* handle,
  * the frame is refilled after every iteration (refill_every resolves to 1).
  * With every dimension WRAP the request is the torus above, at its own
  * refill_every, bit for bit.
- * Not served on a bordered domain: residuals, norms, run_until, slabs, groups,
- * ranks, batches, the wire format, `border: preserve`. */
+ * Residuals, norms and runs until converged: the block "residual, norms and
+ * run_until on a domain" below.
+ * Not served on a bordered domain: slabs, groups, ranks, batches, the wire
+ * format, `border: preserve`. */
 #define SODA_HIP_BORDER_WRAP 0
 #define SODA_HIP_BORDER_CLAMP 1
 #define SODA_HIP_BORDER_MIRROR 2
@@ -1158,6 +1162,163 @@ int soda_hip_border_fused_run_device(soda_hip_border_fused_t* handle,
                                      void* const* outputs,
                                      const void* const* inputs,
                                      int32_t iterate, void* stream);
+
+/* -- residual, norms and run_until on a domain ------------- */
+/* The residual of soda_hip_run_device_residual and the norms of
+ * soda_hip_run_device_norms with the DOMAIN in place of the open box: a run of
+ * n iterations on a handle of domain extent N pairs every output with the
+ * input it replaces, `cur` the output after n iterations, `prev` the output
+ * after n - 1 (the caller's input when n = 1), and counts all N cells of every
+ * pair -- under these handles every cell is defined; no ghost cell is counted.
+ * Per-cell delta, fields and words are unchanged, so every number is again a
+ * sum or a maximum of exact per-cell values and equals the CPU's.
+ *
+ * Torus, and walls at depth 1: the last chunk of the run takes the residual
+ * with the interior [ghost_lo, ghost_lo + N) of the padded arrays as its box,
+ * as soda_hip_run_device_residual takes it -- in the twin of the deepest
+ * scheduled pass that has one, else by `<app>_residual` behind the
+ * one-iteration pass; norms always that second way.
+ * Fused walls: the interior launch is wrong near the walls and the strips mend
+ * it, so each cell is counted where it is made right, by a partition of the
+ * domain that follows from the plan's numbers (T the depth, a / b the reach of
+ * one iteration below / above, whatever the last chunk's length):
+ *   trusted   [(T-1) a[d], N[d] - (T-1) b[d]) in every wall dimension d, all of
+ *             [0, N[d]) in a WRAP dimension: counted by the interior run;
+ *   rims      per strip (wall dimension d) the cells it scatters, the low and
+ *             the high rim, cut to the trusted interval in every wall
+ *             dimension e < d, whole in every other dimension: counted behind
+ *             the strip's last iteration by `<app>_residual` / the norms
+ *             kernel on the strip's own padded arrays (cur: the strip's
+ *             result, prev: its state one iteration earlier), one launch per
+ *             non-empty box, added into the same struct.
+ * The struct is zeroed once, ahead of the last chunk's gather; then strips
+ * (rims behind each), interior, scatter, fill: one stream, no side streams.
+ * soda_hip_border_fused_residual_boxes gives the partition (pure function). */
+typedef struct soda_hip_border_rims {
+  int32_t dim;                         /* the strip's wall dimension d */
+  int32_t reserved;
+  int32_t lo[2][SODA_HIP_MAX_DIM];     /* [0] the low rim, [1] the high rim: */
+  int32_t hi[2][SODA_HIP_MAX_DIM];     /* [lo, hi) per dimension of the STRIP's
+                                          padded arrays; lo == hi somewhere: an
+                                          empty rim (a one-sided program) */
+} soda_hip_border_rims_t;
+typedef struct soda_hip_border_fused_boxes {
+  int32_t depth;                       /* T as resolved */
+  int32_t num_strips;                  /* 0 at depth 1 and on a torus: the
+                                          trusted box is the whole domain */
+  int32_t trusted_lo[SODA_HIP_MAX_DIM];   /* [lo, hi) per dimension of the */
+  int32_t trusted_hi[SODA_HIP_MAX_DIM];   /* domain's padded arrays of P */
+  soda_hip_border_rims_t strip[SODA_HIP_MAX_DIM];   /* by rising dimension */
+} soda_hip_border_fused_boxes_t;
+/* The partition for `plan` and `desc` (desc->border.domain.extent is N).  Pure
+ * function (no GPU, no program); refuses what soda_hip_border_fused_plan
+ * refuses.  The boxes are pairwise disjoint and their union, each moved back
+ * to the domain, is the domain. */
+int soda_hip_border_fused_residual_boxes(
+    const soda_hip_plan_t* plan, const soda_hip_border_fused_desc_t* desc,
+    soda_hip_border_fused_boxes_t* boxes);
+/* <handle>_run_padded that also leaves the residual of its last iteration in
+ * the caller's 32 device bytes `residual_dev` (8-byte aligned, no byte shared
+ * with a padded output) / the norms in the soda_hip_norms_t at `acc_dev`.  The
+ * contracts of <handle>_run_padded hold: inputs arrive extended, outputs leave
+ * extended, inputs are never written, asynchronous on `stream`; the struct is
+ * zeroed inside the call by a kernel node, and the call can be captured after
+ * the first eager call -- every replay zeroes and refills the struct.
+ * Nothing launched: SODA_HIP_ERR_UNSUPPORTED for a program built without
+ * `residual`, and for norms on pairs of another cell kind or size than the
+ * norms handle's; SODA_HIP_ERR_INVALID for iterate < 1, iterate > 1 on a
+ * program that cannot iterate, a struct that is misaligned or overlaps an
+ * output, a norms handle of another dimension count or device. */
+int soda_hip_periodic_run_padded_residual(soda_hip_periodic_t* handle,
+                                          void* const* outputs,
+                                          const void* const* inputs,
+                                          int32_t iterate, void* residual_dev,
+                                          void* stream);
+int soda_hip_periodic_run_padded_norms(soda_hip_periodic_t* handle,
+                                       soda_hip_norms_handle_t* norms,
+                                       void* const* outputs,
+                                       const void* const* inputs,
+                                       int32_t iterate, void* acc_dev,
+                                       void* stream);
+int soda_hip_border_run_padded_residual(soda_hip_border_t* handle,
+                                        void* const* outputs,
+                                        const void* const* inputs,
+                                        int32_t iterate, void* residual_dev,
+                                        void* stream);
+int soda_hip_border_run_padded_norms(soda_hip_border_t* handle,
+                                     soda_hip_norms_handle_t* norms,
+                                     void* const* outputs,
+                                     const void* const* inputs,
+                                     int32_t iterate, void* acc_dev,
+                                     void* stream);
+int soda_hip_border_fused_run_padded_residual(soda_hip_border_fused_t* handle,
+                                              void* const* outputs,
+                                              const void* const* inputs,
+                                              int32_t iterate,
+                                              void* residual_dev, void* stream);
+int soda_hip_border_fused_run_padded_norms(soda_hip_border_fused_t* handle,
+                                           soda_hip_norms_handle_t* norms,
+                                           void* const* outputs,
+                                           const void* const* inputs,
+                                           int32_t iterate, void* acc_dev,
+                                           void* stream);
+/* soda_hip_run_device_until / _until_norm on a domain: DENSE device arrays of
+ * N, the device entry contract on them, arguments and stop rules of those two
+ * entries.  SYNCHRONOUS, not for a stream that is being captured.  The inputs
+ * are padded once into the handle's scratch, chunks of `check_every`
+ * iterations (the last may be shorter) run on padded scratch through the
+ * entries above -- the first from the padded inputs into the padded outputs,
+ * every later one back into the set the one before it read, which is free by
+ * then -- the struct is fetched after each chunk, and the interior of the
+ * final state is cropped into `outputs`.  The handle allocates nothing for it
+ * (the struct fetched lives in the program's scratch).  Refusals as above,
+ * and max_iterate < 1, check_every < 1, max_iterate > 1 on a program that
+ * cannot iterate: SODA_HIP_ERR_INVALID. */
+int soda_hip_periodic_run_until(soda_hip_periodic_t* handle,
+                                void* const* outputs,
+                                const void* const* inputs, int32_t max_iterate,
+                                int32_t check_every, double tol,
+                                uint64_t int_tol,
+                                soda_hip_residual_t* result_host,
+                                int32_t* iterations_done, void* stream);
+int soda_hip_periodic_run_until_norm(soda_hip_periodic_t* handle,
+                                     soda_hip_norms_handle_t* norms,
+                                     void* const* outputs,
+                                     const void* const* inputs,
+                                     int32_t max_iterate, int32_t check_every,
+                                     int32_t which, double tol,
+                                     soda_hip_norms_t* result_host,
+                                     int32_t* iterations_done, void* stream);
+int soda_hip_border_run_until(soda_hip_border_t* handle, void* const* outputs,
+                              const void* const* inputs, int32_t max_iterate,
+                              int32_t check_every, double tol, uint64_t int_tol,
+                              soda_hip_residual_t* result_host,
+                              int32_t* iterations_done, void* stream);
+int soda_hip_border_run_until_norm(soda_hip_border_t* handle,
+                                   soda_hip_norms_handle_t* norms,
+                                   void* const* outputs,
+                                   const void* const* inputs,
+                                   int32_t max_iterate, int32_t check_every,
+                                   int32_t which, double tol,
+                                   soda_hip_norms_t* result_host,
+                                   int32_t* iterations_done, void* stream);
+int soda_hip_border_fused_run_until(soda_hip_border_fused_t* handle,
+                                    void* const* outputs,
+                                    const void* const* inputs,
+                                    int32_t max_iterate, int32_t check_every,
+                                    double tol, uint64_t int_tol,
+                                    soda_hip_residual_t* result_host,
+                                    int32_t* iterations_done, void* stream);
+int soda_hip_border_fused_run_until_norm(soda_hip_border_fused_t* handle,
+                                         soda_hip_norms_handle_t* norms,
+                                         void* const* outputs,
+                                         const void* const* inputs,
+                                         int32_t max_iterate,
+                                         int32_t check_every, int32_t which,
+                                         double tol,
+                                         soda_hip_norms_t* result_host,
+                                         int32_t* iterations_done,
+                                         void* stream);
 
 /* Replaces soda::app::<app>(): host arrays described by (ptr, extent, stride,
  * min) per tensor, inputs then outputs; copies in, runs, copies the outputs

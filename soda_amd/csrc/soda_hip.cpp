@@ -148,6 +148,7 @@ size_t soda_hip_sizeof(int which) {
     case 18: return sizeof(soda_hip_border_fused_desc_t);
     case 19: return sizeof(soda_hip_border_strip_t);
     case 20: return sizeof(soda_hip_border_fused_info_t);
+    case 21: return sizeof(soda_hip_border_fused_boxes_t);
     default: return 0;
   }
 }
@@ -1608,6 +1609,55 @@ static int launch_pass(soda_hip_program* p, const RunRequest& rq,
   return SODA_HIP_OK;
 }
 
+// zeroed inside the call, on the caller's stream, by a kernel of the program:
+// a captured call zeroes and refills the struct at every replay (as a 32-byte
+// memset node the zeroing did not survive a replay)
+int residual_zero(soda_hip_program* p, const ResidualRun& res, void* stream_) {
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  if (res.norms) return norms_zero(res.norms, res.dev, stream);
+  const int zk = p->plan.residual.zero_kernel;
+  void* dev = res.dev;
+  size_t size = sizeof dev;
+  void* extra[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &dev,
+                   HIP_LAUNCH_PARAM_BUFFER_SIZE, &size, HIP_LAUNCH_PARAM_END};
+  HIP_TRY(hipModuleLaunchKernel(p->functions[zk], 1, 1, 1, 64, 1, 1, 0, stream,
+                                nullptr, extra));
+  return SODA_HIP_OK;
+}
+
+int residual_add(soda_hip_program* p, void* const* cur,
+                 const void* const* prev, const int32_t* extent,
+                 const ResidualRun& res, const soda_hip_resbox_t& box,
+                 void* stream) {
+  const soda_hip_plan_t& plan = p->plan;
+  bool any = false;
+  for (int o = 0; o < plan.num_outputs; ++o) {
+    bool empty = false;
+    for (int d = 0; d < plan.dim; ++d) {
+      if (box.lo[o][d] < 0 || box.hi[o][d] > extent[d])
+        return fail(SODA_HIP_ERR_INVALID,
+                    "residual: the box does not lie in the arrays; nothing "
+                    "was launched");
+      if (box.hi[o][d] <= box.lo[o][d]) empty = true;
+    }
+    if (!empty) any = true;
+  }
+  if (!any) return SODA_HIP_OK;
+  // (prev holds no param arrays: the residual kernels read none)
+  std::vector<const void*> in(plan.num_inputs + plan.num_params, prev[0]);
+  for (int i = 0; i < plan.num_inputs; ++i) in[i] = prev[i];
+  soda_hip_kargs_t args;
+  int64_t cells;
+  if (int rc = run_geometry(plan, {cur, in.data(), extent, 1, stream}, &args,
+                            &cells))
+    return rc;
+  for (int i = 0; i < plan.num_inputs; ++i)
+    args.buf[i] = const_cast<void*>(prev[i]);
+  for (int o = 0; o < plan.num_outputs; ++o)
+    args.buf[plan.num_inputs + o] = cur[o];
+  return launch_generic(p, args, static_cast<hipStream_t>(stream), res, box);
+}
+
 int run_core(soda_hip_program_t* p, const RunRequest& rq) {
   if (!p || !rq.outputs || !rq.inputs || !rq.extent)
     return fail(SODA_HIP_ERR_INVALID, "run_device: NULL argument");
@@ -1615,7 +1665,8 @@ int run_core(soda_hip_program_t* p, const RunRequest& rq) {
   const ResidualRun* res = rq.residual;
   const int32_t iterate = rq.iterate, batch = rq.batch;
   if (res && (batch != 1 || rq.force_pass >= 0 || !plan.residual.present ||
-              !res->dev || res->box_iterate < iterate))
+              !res->dev || (res->box ? rq.slab != nullptr
+                                     : res->box_iterate < iterate)))
     return fail(SODA_HIP_ERR_INVALID, "run_core: bad residual run");
   if (batch < 1 || (batch > 1 && (!plan.batched || rq.slab)))
     return fail(SODA_HIP_ERR_INVALID, "run_core: bad batch");
@@ -1674,25 +1725,16 @@ int run_core(soda_hip_program_t* p, const RunRequest& rq) {
     // The cells counted: the global grid's box, of which a slab takes its
     // kept rows -- the ghost rows of the result, which the last pass writes
     // too, lie outside and are not counted.
-    residual_slab_box(plan, base.gextent, base.origin, base.extent,
-                      cone ? cone->keep_lo : 0,
-                      cone ? cone->keep_hi : base.extent[plan.dim - 1],
-                      res->box_iterate, &res_box);
-    // zeroed inside the call, on the caller's stream, by a kernel of the
-    // program: a captured call zeroes and refills the struct at every replay
-    // (as a 32-byte memset node the zeroing did not survive a replay)
-    if (res->norms) {
-      if (int rc = norms_zero(res->norms, res->dev, stream)) return rc;
-    } else {
-      const int zk = plan.residual.zero_kernel;
-      void* dev = res->dev;
-      size_t size = sizeof dev;
-      void* extra[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &dev,
-                       HIP_LAUNCH_PARAM_BUFFER_SIZE, &size,
-                       HIP_LAUNCH_PARAM_END};
-      HIP_TRY(hipModuleLaunchKernel(p->functions[zk], 1, 1, 1, 64, 1, 1, 0,
-                                    stream, nullptr, extra));
-    }
+    // A domain hands its own box in (ResidualRun): its interior.
+    if (res->box)
+      res_box = *res->box;
+    else
+      residual_slab_box(plan, base.gextent, base.origin, base.extent,
+                        cone ? cone->keep_lo : 0,
+                        cone ? cone->keep_hi : base.extent[plan.dim - 1],
+                        res->box_iterate, &res_box);
+    if (!res->accumulate)
+      if (int rc = residual_zero(p, *res, rq.stream)) return rc;
     p->last_res_mode = s.res_twin ? 1 : 2;
     p->last_res_fused = plan.passes[s.res_pass].fused_iters;
   }
@@ -2108,12 +2150,9 @@ int soda_hip_run_device_until_norm(soda_hip_program_t* p,
     return rc;
   soda_hip_norms_t host;
   auto converged = [&](bool* stop) {
-    double norm = 0.0;
-    if (soda_hip_norms_value(&host, which, &norm))
+    if (!norms_converged(host, which, tol, stop))
       return fail(SODA_HIP_ERR_RUNTIME,
                   "run_device_until_norm: the struct fetched is of no kind");
-    if (which == SODA_HIP_NORMS_WHICH_L2) norm = sqrt(norm);
-    *stop = host.unordered == 0 && host.infinite == 0 && norm <= tol;
     return (int)SODA_HIP_OK;
   };
   if (int rc = run_until(p, "run_device_until_norm", outputs, inputs, extent,
@@ -3289,3 +3328,29 @@ int soda_hip_event_destroy(soda_hip_event_t* event) {
 }
 
 }  // extern "C"
+
+namespace soda_detail {
+
+int check_residual_request(const soda_hip_program* p, void* const* outputs,
+                           const int32_t* extent, const void* dev,
+                           const char* who) {
+  return check_residual(p, outputs, extent, dev, who);
+}
+
+int check_norms_request(const soda_hip_program* p,
+                        const soda_hip_norms_handle* h, void* const* outputs,
+                        const int32_t* extent, const void* dev,
+                        const char* who) {
+  return check_norms_run(p, h, outputs, extent, dev, who);
+}
+
+bool norms_converged(const soda_hip_norms_t& acc, int32_t which, double tol,
+                     bool* stop) {
+  double norm = 0.0;
+  if (soda_hip_norms_value(&acc, which, &norm)) return false;
+  if (which == SODA_HIP_NORMS_WHICH_L2) norm = sqrt(norm);
+  *stop = acc.unordered == 0 && acc.infinite == 0 && norm <= tol;
+  return true;
+}
+
+}  // namespace soda_detail

@@ -183,10 +183,17 @@ namespace soda_detail {
 // `norms` != nullptr (soda_hip_run_device_norms): `dev` is a soda_hip_norms_t,
 // the run always ends in the one-iteration pass, and the handle's kernels run
 // in place of `<app>_residual_zero` and `<app>_residual`.
+// `box` != nullptr (bordered and periodic domains, soda_periodic.cpp): the
+// cells counted, in the coordinates of the arrays the run addresses, in place
+// of the box after `box_iterate` iterations, which is then not looked at; not
+// on a slab.  `accumulate`: do not zero the struct, add to it -- several runs
+// and boxes fill one struct that residual_zero zeroed once.
 struct ResidualRun {
   void* dev;
   int32_t box_iterate;
   soda_hip_norms_handle* norms = nullptr;
+  const soda_hip_resbox_t* box = nullptr;
+  bool accumulate = false;
 };
 
 // One run of a program on device arrays: `RunRequest rq = {outputs, inputs,
@@ -209,6 +216,31 @@ struct RunRequest {
   const ResidualRun* residual = nullptr;
 };
 int run_core(soda_hip_program* p, const RunRequest& rq);
+
+// The pieces of a residual that several runs and boxes fill (ResidualRun's
+// `accumulate`), each one launch on `stream`.  residual_zero: the struct
+// zeroed by `<app>_residual_zero` / the norms handle's kernel.  residual_add:
+// the cells `box` of the dense arrays `cur` (one per output) against `prev`
+// (one per input), all of `extent`, added by `<app>_residual` / the norms
+// kernel per pair; a box that is empty for every pair launches nothing.
+int residual_zero(soda_hip_program* p, const ResidualRun& res, void* stream);
+int residual_add(soda_hip_program* p, void* const* cur,
+                 const void* const* prev, const int32_t* extent,
+                 const ResidualRun& res, const soda_hip_resbox_t& box,
+                 void* stream);
+// What soda_hip_run_device_residual / _norms ask of a program (and a norms
+// handle) and of the struct (`dev` null: of the program and handle only),
+// for entries that run on other arrays than a program's plain ones.
+int check_residual_request(const soda_hip_program* p, void* const* outputs,
+                           const int32_t* extent, const void* dev,
+                           const char* who);
+int check_norms_request(const soda_hip_program* p,
+                        const soda_hip_norms_handle* h, void* const* outputs,
+                        const int32_t* extent, const void* dev,
+                        const char* who);
+// the stop rule of a run until a norm is small; false: a struct of no kind
+bool norms_converged(const soda_hip_norms_t& acc, int32_t which, double tol,
+                     bool* stop);
 
 // What run_core asks of the caller's addresses before anything is launched,
 // each tensor taken as the dense array of `cells` x `batch` cells the kernels

@@ -16,6 +16,11 @@
 // handles together: one on the domain, whose chunks run fused, and one per
 // wall dimension on a narrow strip, which runs the loop above and mends the
 // rim; the box kernel (soda_rt_box.h) carries cells between them.
+//
+// Residual, norms and run_until on all three: the last chunk
+// of a run takes the residual through run_core with the interior as its box;
+// a fused handle counts each cell where it is made right -- the interior run
+// a trusted box, every strip its two rims.
 #include "soda_internal.h"
 
 #include <cstring>
@@ -277,11 +282,45 @@ int check_contract(const soda_hip_plan_t& plan, void* const* outputs,
   return SODA_HIP_OK;
 }
 
+// The same box for every pair: [lo, hi) per dimension of the handle's padded
+// arrays.
+soda_hip_resbox_t resbox_of(const soda_hip_periodic* h, const int32_t* lo,
+                            const int32_t* hi) {
+  soda_hip_resbox_t box;
+  memset(&box, 0, sizeof box);
+  for (int o = 0; o < h->prog->plan.num_outputs; ++o)
+    for (int d = 0; d < SODA_HIP_MAX_DIM; ++d) {
+      box.lo[o][d] = d < h->t.dim ? lo[d] : 0;
+      box.hi[o][d] = d < h->t.dim ? hi[d] : 1;
+    }
+  return box;
+}
+
+// the counted cells of a torus or a depth-1 bordered domain: the interior
+soda_hip_resbox_t interior_box(const soda_hip_periodic* h) {
+  int32_t hi[4];
+  for (int d = 0; d < 4; ++d) hi[d] = h->t.glo[d] + h->t.n[d];
+  return resbox_of(h, h->t.glo, hi);
+}
+
+// What the last chunk of run_chunks takes of a residual.
+// `behind` false: box[0] rides in the chunk's run (run_core: a twin, or the
+// generic kernels behind the one-iteration pass).  `behind` true, a strip:
+// every box is counted behind the chunk by the generic kernels, cur the
+// chunk's result, prev what it read.
+struct ChunkResidual {
+  ResidualRun run;
+  soda_hip_resbox_t box[2];
+  int nbox;
+  bool behind;
+};
+
 // The chunks of a run on padded arrays: `inputs` wrapped in, `outputs` wrapped
 // out, the chunks alternating between `outputs` and the handle's `pong` so
 // that the last one lands in `outputs`.
 int run_chunks(soda_hip_periodic* h, void* const* outputs,
-               const void* const* inputs, int32_t iterate, void* stream) {
+               const void* const* inputs, int32_t iterate, void* stream,
+               const ChunkResidual* res = nullptr) {
   soda_hip_program* p = h->prog;
   const soda_hip_plan_t& plan = p->plan;
   const int nin = plan.num_inputs, nout = plan.num_outputs;
@@ -296,8 +335,19 @@ int run_chunks(soda_hip_periodic* h, void* const* outputs,
     const bool to_out = ((chunks - 1 - c) % 2) == 0;
     for (int o = 0; o < nout; ++o)
       dst[o] = to_out ? outputs[o] : h->pong[o].ptr;
-    if (int rc = run_core(p, {dst.data(), src.data(), h->t.p, n, stream}))
-      return rc;
+    RunRequest rq = {dst.data(), src.data(), h->t.p, n, stream};
+    ResidualRun riding;
+    if (res && c + 1 == chunks && !res->behind) {
+      riding = res->run;
+      riding.box = &res->box[0];
+      rq.residual = &riding;
+    }
+    if (int rc = run_core(p, rq)) return rc;
+    if (res && c + 1 == chunks && res->behind)
+      for (int b = 0; b < res->nbox; ++b)
+        if (int rc = residual_add(p, dst.data(), src.data(), h->t.p, res->run,
+                                  res->box[b], stream))
+          return rc;
     if (int rc = wrap_launch(h, kFill, dst.data(), dst.data(), elem.data(),
                              nout, static_cast<hipStream_t>(stream)))
       return rc;
@@ -306,6 +356,14 @@ int run_chunks(soda_hip_periodic* h, void* const* outputs,
       for (int i = 0; i < nin; ++i) src[i] = dst[i];
   }
   return SODA_HIP_OK;
+}
+
+// run_chunks that takes the residual of `run` over the handle's interior
+int run_chunks_residual(soda_hip_periodic* h, void* const* outputs,
+                        const void* const* inputs, int32_t iterate,
+                        void* stream, const ResidualRun& run) {
+  const ChunkResidual res = {run, {interior_box(h), {}}, 1, false};
+  return run_chunks(h, outputs, inputs, iterate, stream, &res);
 }
 
 // soda_hip_periodic_plan, and soda_hip_border_plan behind its modes
@@ -504,7 +562,17 @@ int fill_core(soda_hip_periodic* h, void* const* arrays, int32_t count,
 
 // (a fused bordered handle's chunks, below)
 int fused_chunks(soda_hip_border_fused* f, void* const* outputs,
-                 const void* const* inputs, int32_t iterate, void* stream);
+                 const void* const* inputs, int32_t iterate, void* stream,
+                 const ResidualRun* res = nullptr);
+
+// the chunks of a handle, fused or not, with or without a residual
+int any_chunks(soda_hip_periodic* h, soda_hip_border_fused* fused,
+               void* const* outputs, const void* const* inputs,
+               int32_t iterate, void* stream, const ResidualRun* res) {
+  if (fused) return fused_chunks(fused, outputs, inputs, iterate, stream, res);
+  if (res) return run_chunks_residual(h, outputs, inputs, iterate, stream, *res);
+  return run_chunks(h, outputs, inputs, iterate, stream);
+}
 
 // `fused`: the handle whose chunks these are, if not h's own
 int run_padded_core(soda_hip_periodic* h, void* const* outputs,
@@ -560,6 +628,163 @@ int run_device_core(soda_hip_periodic* h, void* const* outputs,
   return wrap_launch(h, kCrop, outputs,
                      const_cast<const void* const*>(pout.data()), eout.data(),
                      nout, stream);
+}
+
+// <handle>_run_padded_residual / _run_padded_norms (`norms` != nullptr):
+// run_padded_core with the struct at `dev` filled.  Every
+// refusal comes before the first launch.
+int run_padded_residual_core(soda_hip_periodic* h,
+                             soda_hip_norms_handle* norms,
+                             void* const* outputs, const void* const* inputs,
+                             int32_t iterate, void* dev, void* stream,
+                             soda_hip_border_fused* fused = nullptr) {
+  const std::string who = std::string(h->kind->who) +
+                          (norms ? "_run_padded_norms" : "_run_padded_residual");
+  soda_hip_program* p = h->prog;
+  for (int o = 0; o < p->plan.num_outputs; ++o)
+    if (!outputs[o]) return fail(SODA_HIP_ERR_INVALID, who + ": NULL output");
+  if (int rc = norms ? check_norms_request(p, norms, outputs, h->t.p, dev,
+                                           who.c_str())
+                     : check_residual_request(p, outputs, h->t.p, dev,
+                                              who.c_str()))
+    return rc;
+  if (int rc = check_iterate(p->plan, h->not_iterable, iterate, who.c_str()))
+    return rc;
+  if (int rc = check_contract(p->plan, outputs, inputs, h->t.p, who.c_str()))
+    return rc;
+  const ResidualRun run = {dev, 0, norms};
+  return any_chunks(h, fused, outputs, inputs, iterate, stream, &run);
+}
+
+// <handle>_run_until / _run_until_norm on DENSE arrays of N: pads once, runs
+// `check_every` iterations at a time on the handle's padded scratch until
+// `converged(&stop)` says so by the struct of the last chunk -- `host_bytes`
+// fetched into `host` -- or `max_iterate` iterations are done, crops.  The
+// first chunk goes from pad_in to pad_out, every later one back into the set
+// the one before it read (an iterable program's pad_in[i] is as large as its
+// pad_out[i]).  Synchronous.
+template <class Converged>
+int run_until_core(soda_hip_periodic* h, soda_hip_norms_handle* norms,
+                   void* const* outputs, const void* const* inputs,
+                   int32_t max_iterate, int32_t check_every, void* host,
+                   size_t host_bytes, Converged converged,
+                   int32_t* iterations_done, void* stream_,
+                   soda_hip_border_fused* fused) {
+  const std::string who = std::string(h->kind->who) +
+                          (norms ? "_run_until_norm" : "_run_until");
+  soda_hip_program* p = h->prog;
+  const soda_hip_plan_t& plan = p->plan;
+  const int nin = plan.num_inputs, nout = plan.num_outputs;
+  if (max_iterate < 1 || check_every < 1)
+    return fail(SODA_HIP_ERR_INVALID,
+                who + ": max_iterate and check_every must be >= 1");
+  for (int o = 0; o < nout; ++o)
+    if (!outputs[o]) return fail(SODA_HIP_ERR_INVALID, who + ": NULL output");
+  if (int rc = norms ? check_norms_request(p, norms, outputs, h->t.n, nullptr,
+                                           who.c_str())
+                     : check_residual_request(p, outputs, h->t.n, nullptr,
+                                              who.c_str()))
+    return rc;
+  if (int rc = check_iterate(plan, h->not_iterable, max_iterate, who.c_str()))
+    return rc;
+  if (int rc = check_contract(plan, outputs, inputs, h->t.n, who.c_str()))
+    return rc;
+  HIP_TRY(hipSetDevice(p->device));
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  hipStreamCaptureStatus capture = hipStreamCaptureStatusNone;
+  if (hipStreamIsCapturing(stream, &capture) != hipSuccess) {
+    (void)hipGetLastError();
+    capture = hipStreamCaptureStatusNone;
+  }
+  if (capture != hipStreamCaptureStatusNone)
+    return fail(SODA_HIP_ERR_INVALID,
+                who + ": synchronous, not for a stream that is being captured; "
+                      "nothing was launched");
+  if (int rc = ensure(p->until_struct, host_bytes)) return rc;
+  std::vector<void*> a(nin), b(nout), crop(nout);
+  std::vector<const void*> src(nin + plan.num_params);
+  std::vector<int32_t> ein(nin), eout(nout);
+  for (int i = 0; i < nin; ++i) {
+    a[i] = h->pad_in[i].ptr;
+    src[i] = a[i];
+    ein[i] = plan.elem_size[i];
+  }
+  for (int k = 0; k < plan.num_params; ++k) src[nin + k] = inputs[nin + k];
+  for (int o = 0; o < nout; ++o) {
+    b[o] = h->pad_out[o].ptr;
+    eout[o] = plan.elem_size[nin + o];
+  }
+  if (int rc = wrap_launch(h, kPad, a.data(), inputs, ein.data(), nin, stream))
+    return rc;
+  memset(host, 0, host_bytes);
+  const ResidualRun run = {p->until_struct.ptr, 0, norms};
+  int32_t done = 0;
+  for (int32_t chunk = 0; done < max_iterate; ++chunk) {
+    const int32_t n =
+        max_iterate - done < check_every ? max_iterate - done : check_every;
+    void* const* dst = chunk % 2 ? a.data() : b.data();
+    if (int rc = any_chunks(h, fused, dst, src.data(), n, stream_, &run))
+      return rc;
+    HIP_TRY(hipMemcpyAsync(host, p->until_struct.ptr, host_bytes,
+                           hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    done += n;
+    for (int o = 0; o < nout; ++o) crop[o] = dst[o];
+    bool stop = false;
+    if (int rc = converged(&stop)) return rc;
+    if (stop) break;
+    // (another chunk follows: the program iterates, nin == nout)
+    for (int i = 0; i < nin; ++i) src[i] = dst[i];
+  }
+  if (int rc = wrap_launch(h, kCrop, outputs,
+                           const_cast<const void* const*>(crop.data()),
+                           eout.data(), nout, stream))
+    return rc;
+  HIP_TRY(hipStreamSynchronize(stream));
+  if (iterations_done) *iterations_done = done;
+  return SODA_HIP_OK;
+}
+
+int until_residual(soda_hip_periodic* h, void* const* outputs,
+                   const void* const* inputs, int32_t max_iterate,
+                   int32_t check_every, double tol, uint64_t int_tol,
+                   soda_hip_residual_t* result_host, int32_t* iterations_done,
+                   void* stream, soda_hip_border_fused* fused = nullptr) {
+  soda_hip_residual_t host;
+  auto converged = [&](bool* stop) {
+    *stop = residual_converged(host, tol, int_tol);
+    return (int)SODA_HIP_OK;
+  };
+  if (int rc = run_until_core(h, nullptr, outputs, inputs, max_iterate,
+                              check_every, &host, sizeof host, converged,
+                              iterations_done, stream, fused))
+    return rc;
+  if (result_host) *result_host = host;
+  return SODA_HIP_OK;
+}
+
+int until_norm(soda_hip_periodic* h, soda_hip_norms_handle* norms,
+               void* const* outputs, const void* const* inputs,
+               int32_t max_iterate, int32_t check_every, int32_t which,
+               double tol, soda_hip_norms_t* result_host,
+               int32_t* iterations_done, void* stream,
+               soda_hip_border_fused* fused = nullptr) {
+  const std::string who = std::string(h->kind->who) + "_run_until_norm";
+  if (which != SODA_HIP_NORMS_WHICH_L1 && which != SODA_HIP_NORMS_WHICH_L2)
+    return fail(SODA_HIP_ERR_INVALID, who + ": bad `which`");
+  soda_hip_norms_t host;
+  auto converged = [&](bool* stop) {
+    if (!norms_converged(host, which, tol, stop))
+      return fail(SODA_HIP_ERR_RUNTIME,
+                  who + ": the struct fetched is of no kind");
+    return (int)SODA_HIP_OK;
+  };
+  if (int rc = run_until_core(h, norms, outputs, inputs, max_iterate,
+                              check_every, &host, sizeof host, converged,
+                              iterations_done, stream, fused))
+    return rc;
+  if (result_host) *result_host = host;
+  return SODA_HIP_OK;
 }
 
 // Whether every mode of a bordered request wraps; its modes checked.
@@ -728,6 +953,108 @@ int soda_hip_border_run_device(soda_hip_border_t* h, void* const* outputs,
   return run_device_core(h, outputs, inputs, iterate, stream);
 }
 
+// -- residual, norms and run_until on both -----------------
+
+int soda_hip_periodic_run_padded_residual(soda_hip_periodic_t* h,
+                                          void* const* outputs,
+                                          const void* const* inputs,
+                                          int32_t iterate, void* residual_dev,
+                                          void* stream) {
+  if (!h || !outputs || !inputs || !residual_dev)
+    return fail(SODA_HIP_ERR_INVALID,
+                "periodic_run_padded_residual: NULL argument");
+  return run_padded_residual_core(h, nullptr, outputs, inputs, iterate,
+                                  residual_dev, stream);
+}
+
+int soda_hip_periodic_run_padded_norms(soda_hip_periodic_t* h,
+                                       soda_hip_norms_handle_t* norms,
+                                       void* const* outputs,
+                                       const void* const* inputs,
+                                       int32_t iterate, void* acc_dev,
+                                       void* stream) {
+  if (!h || !norms || !outputs || !inputs || !acc_dev)
+    return fail(SODA_HIP_ERR_INVALID,
+                "periodic_run_padded_norms: NULL argument");
+  return run_padded_residual_core(h, norms, outputs, inputs, iterate, acc_dev,
+                                  stream);
+}
+
+int soda_hip_periodic_run_until(soda_hip_periodic_t* h, void* const* outputs,
+                                const void* const* inputs, int32_t max_iterate,
+                                int32_t check_every, double tol,
+                                uint64_t int_tol,
+                                soda_hip_residual_t* result_host,
+                                int32_t* iterations_done, void* stream) {
+  if (!h || !outputs || !inputs)
+    return fail(SODA_HIP_ERR_INVALID, "periodic_run_until: NULL argument");
+  return until_residual(h, outputs, inputs, max_iterate, check_every, tol,
+                        int_tol, result_host, iterations_done, stream);
+}
+
+int soda_hip_periodic_run_until_norm(soda_hip_periodic_t* h,
+                                     soda_hip_norms_handle_t* norms,
+                                     void* const* outputs,
+                                     const void* const* inputs,
+                                     int32_t max_iterate, int32_t check_every,
+                                     int32_t which, double tol,
+                                     soda_hip_norms_t* result_host,
+                                     int32_t* iterations_done, void* stream) {
+  if (!h || !norms || !outputs || !inputs)
+    return fail(SODA_HIP_ERR_INVALID, "periodic_run_until_norm: NULL argument");
+  return until_norm(h, norms, outputs, inputs, max_iterate, check_every, which,
+                    tol, result_host, iterations_done, stream);
+}
+
+int soda_hip_border_run_padded_residual(soda_hip_border_t* h,
+                                        void* const* outputs,
+                                        const void* const* inputs,
+                                        int32_t iterate, void* residual_dev,
+                                        void* stream) {
+  if (!h || !outputs || !inputs || !residual_dev)
+    return fail(SODA_HIP_ERR_INVALID,
+                "border_run_padded_residual: NULL argument");
+  return run_padded_residual_core(h, nullptr, outputs, inputs, iterate,
+                                  residual_dev, stream);
+}
+
+int soda_hip_border_run_padded_norms(soda_hip_border_t* h,
+                                     soda_hip_norms_handle_t* norms,
+                                     void* const* outputs,
+                                     const void* const* inputs,
+                                     int32_t iterate, void* acc_dev,
+                                     void* stream) {
+  if (!h || !norms || !outputs || !inputs || !acc_dev)
+    return fail(SODA_HIP_ERR_INVALID, "border_run_padded_norms: NULL argument");
+  return run_padded_residual_core(h, norms, outputs, inputs, iterate, acc_dev,
+                                  stream);
+}
+
+int soda_hip_border_run_until(soda_hip_border_t* h, void* const* outputs,
+                              const void* const* inputs, int32_t max_iterate,
+                              int32_t check_every, double tol, uint64_t int_tol,
+                              soda_hip_residual_t* result_host,
+                              int32_t* iterations_done, void* stream) {
+  if (!h || !outputs || !inputs)
+    return fail(SODA_HIP_ERR_INVALID, "border_run_until: NULL argument");
+  return until_residual(h, outputs, inputs, max_iterate, check_every, tol,
+                        int_tol, result_host, iterations_done, stream);
+}
+
+int soda_hip_border_run_until_norm(soda_hip_border_t* h,
+                                   soda_hip_norms_handle_t* norms,
+                                   void* const* outputs,
+                                   const void* const* inputs,
+                                   int32_t max_iterate, int32_t check_every,
+                                   int32_t which, double tol,
+                                   soda_hip_norms_t* result_host,
+                                   int32_t* iterations_done, void* stream) {
+  if (!h || !norms || !outputs || !inputs)
+    return fail(SODA_HIP_ERR_INVALID, "border_run_until_norm: NULL argument");
+  return until_norm(h, norms, outputs, inputs, max_iterate, check_every, which,
+                    tol, result_host, iterations_done, stream);
+}
+
 }  // extern "C"
 
 // -- bordered domains, fused away from the walls -----------
@@ -774,6 +1101,7 @@ struct soda_hip_border_fused {
   } strip[SODA_HIP_MAX_DIM];
   hipModule_t box_module[4] = {nullptr, nullptr, nullptr, nullptr};
   hipFunction_t box_fn[4] = {nullptr, nullptr, nullptr, nullptr};  // log2(elem)
+  soda_hip_border_fused_boxes_t boxes;   // where a residual counts each cell
 };
 
 namespace {
@@ -879,6 +1207,51 @@ int fused_plan_core(const soda_hip_plan_t* plan,
   return SODA_HIP_OK;
 }
 
+// The partition of the domain a residual counts by, from the
+// numbers of a resolved plan alone: the trusted box in the padded coordinates
+// of the domain, per strip the two rims it scatters in the strip's own, cut to
+// the trusted interval in every wall dimension below the strip's.  A wall
+// dimension's trusted interval is what its strip does not take (all of it
+// where the reach is zero and there is no strip), a WRAP dimension's is all.
+void residual_boxes(const soda_hip_border_fused_info_t& info,
+                    const int32_t* n, int dim,
+                    soda_hip_border_fused_boxes_t* out) {
+  memset(out, 0, sizeof *out);
+  out->depth = info.depth;
+  out->num_strips = info.num_strips;
+  int32_t tlo[4] = {0, 0, 0, 0}, thi[4] = {1, 1, 1, 1};   // domain coordinates
+  for (int d = 0; d < dim; ++d) thi[d] = n[d];
+  for (int i = 0; i < info.num_strips; ++i) {
+    const soda_hip_border_strip_t& s = info.strip[i];
+    tlo[s.dim] = s.take_lo;
+    thi[s.dim] = n[s.dim] - s.take_hi;
+  }
+  for (int d = 0; d < SODA_HIP_MAX_DIM; ++d) {
+    const int32_t g = d < dim ? info.main.ghost_lo[d] : 0;
+    out->trusted_lo[d] = g + tlo[d];
+    out->trusted_hi[d] = g + thi[d];
+  }
+  for (int i = 0; i < info.num_strips; ++i) {
+    const soda_hip_border_strip_t& s = info.strip[i];
+    soda_hip_border_rims_t& r = out->strip[i];
+    r.dim = s.dim;
+    for (int side = 0; side < 2; ++side)
+      for (int e = 0; e < SODA_HIP_MAX_DIM; ++e) {
+        const int32_t g = e < dim ? s.info.ghost_lo[e] : 0;
+        int32_t lo = 0, hi = e < dim ? n[e] : 1;
+        if (e == s.dim) {
+          lo = side ? s.lo + s.hi - s.take_hi : 0;
+          hi = side ? s.lo + s.hi : s.take_lo;
+        } else if (e < s.dim) {      // (trusted == whole where e has no walls)
+          lo = tlo[e];
+          hi = thi[e];
+        }
+        r.lo[side][e] = g + lo;
+        r.hi[side][e] = g + hi;
+      }
+  }
+}
+
 // `nbox` boxes from the arrays src[i] of extent `sext` into dst[i] of `dext`,
 // `count` tensors with cells of elem[i] bytes; one launch per cell size among
 // them.  A box that leaves either extent is refused before anything runs.
@@ -981,10 +1354,15 @@ void strip_boxes(const soda_hip_border_fused* f,
 // of n <= depth iterations the strips gathered from the chunk's inputs and
 // advanced n times, the interior launched on P, the strips' rims scattered
 // over its result, the frame filled.  One stream, in that order.
+// `res`: the last chunk also takes the residual, each cell where it is made
+// right: the struct zeroed once ahead of the gather, the rims
+// behind every strip's last iteration, the trusted box in the interior's run.
 int fused_chunks(soda_hip_border_fused* f, void* const* outputs,
-                 const void* const* inputs, int32_t iterate, void* stream_) {
+                 const void* const* inputs, int32_t iterate, void* stream_,
+                 const ResidualRun* res) {
   soda_hip_periodic* h = f->main;
-  if (!f->nstrips) return run_chunks(h, outputs, inputs, iterate, stream_);
+  if (!f->nstrips)
+    return any_chunks(h, nullptr, outputs, inputs, iterate, stream_, res);
   soda_hip_program* p = h->prog;
   const soda_hip_plan_t& plan = p->plan;
   HIP_TRY(hipSetDevice(p->device));
@@ -1003,6 +1381,13 @@ int fused_chunks(soda_hip_border_fused* f, void* const* outputs,
     const bool to_out = ((chunks - 1 - c) % 2) == 0;
     for (int o = 0; o < nout; ++o)
       dst[o] = to_out ? outputs[o] : h->pong[o].ptr;
+    const bool take = res && c + 1 == chunks;
+    ChunkResidual part;
+    if (take) {
+      if (int rc = residual_zero(p, *res, stream_)) return rc;
+      part.run = *res;
+      part.run.accumulate = true;
+    }
     for (int k = 0; k < f->nstrips; ++k) {
       const soda_hip_border_fused::Strip& s = f->strip[k];
       Box box[2];
@@ -1018,11 +1403,24 @@ int fused_chunks(soda_hip_border_fused* f, void* const* outputs,
       if (int rc = wrap_launch(s.h, kFill, sin.data(), ssrc.data(), ein.data(),
                                nin, stream))
         return rc;
-      if (int rc = run_chunks(s.h, sout.data(), ssrc.data(), n, stream_))
+      if (take) {
+        const soda_hip_border_rims_t& r = f->boxes.strip[k];
+        part.box[0] = resbox_of(s.h, r.lo[0], r.hi[0]);
+        part.box[1] = resbox_of(s.h, r.lo[1], r.hi[1]);
+        part.nbox = 2;
+        part.behind = true;
+      }
+      if (int rc = run_chunks(s.h, sout.data(), ssrc.data(), n, stream_,
+                              take ? &part : nullptr))
         return rc;
     }
-    if (int rc = run_core(p, {dst.data(), src.data(), h->t.p, n, stream_}))
-      return rc;
+    RunRequest rq = {dst.data(), src.data(), h->t.p, n, stream_};
+    if (take) {
+      part.box[0] = resbox_of(h, f->boxes.trusted_lo, f->boxes.trusted_hi);
+      part.run.box = &part.box[0];
+      rq.residual = &part.run;
+    }
+    if (int rc = run_core(p, rq)) return rc;
     for (int k = 0; k < f->nstrips; ++k) {
       const soda_hip_border_fused::Strip& s = f->strip[k];
       Box box[2];
@@ -1131,6 +1529,7 @@ int soda_hip_border_fused_create(soda_hip_program_t* p,
     soda_hip_border_fused_destroy(f);
     return fail(rc, why);
   }
+  residual_boxes(info, domain.extent, plan.dim, &f->boxes);
   *handle = f;
   return SODA_HIP_OK;
 }
@@ -1220,6 +1619,79 @@ int soda_hip_border_fused_run_device(soda_hip_border_fused_t* f,
   if (!f || !outputs || !inputs)
     return fail(SODA_HIP_ERR_INVALID, "border_fused_run_device: NULL argument");
   return run_device_core(f->main, outputs, inputs, iterate, stream, f);
+}
+
+// -- residual, norms and run_until --------------------------
+
+int soda_hip_border_fused_residual_boxes(
+    const soda_hip_plan_t* plan, const soda_hip_border_fused_desc_t* desc,
+    soda_hip_border_fused_boxes_t* boxes) {
+  if (!boxes)
+    return fail(SODA_HIP_ERR_INVALID,
+                "border_fused_residual_boxes: NULL argument");
+  soda_hip_border_fused_info_t info;
+  bool all_wrap;
+  if (int rc = fused_plan_core(plan, desc, 0, &info, 0, nullptr, nullptr,
+                               &all_wrap))
+    return rc;
+  residual_boxes(info, desc->border.domain.extent, plan->dim, boxes);
+  return SODA_HIP_OK;
+}
+
+int soda_hip_border_fused_run_padded_residual(soda_hip_border_fused_t* f,
+                                              void* const* outputs,
+                                              const void* const* inputs,
+                                              int32_t iterate,
+                                              void* residual_dev,
+                                              void* stream) {
+  if (!f || !outputs || !inputs || !residual_dev)
+    return fail(SODA_HIP_ERR_INVALID,
+                "border_fused_run_padded_residual: NULL argument");
+  return run_padded_residual_core(f->main, nullptr, outputs, inputs, iterate,
+                                  residual_dev, stream, f);
+}
+
+int soda_hip_border_fused_run_padded_norms(soda_hip_border_fused_t* f,
+                                           soda_hip_norms_handle_t* norms,
+                                           void* const* outputs,
+                                           const void* const* inputs,
+                                           int32_t iterate, void* acc_dev,
+                                           void* stream) {
+  if (!f || !norms || !outputs || !inputs || !acc_dev)
+    return fail(SODA_HIP_ERR_INVALID,
+                "border_fused_run_padded_norms: NULL argument");
+  return run_padded_residual_core(f->main, norms, outputs, inputs, iterate,
+                                  acc_dev, stream, f);
+}
+
+int soda_hip_border_fused_run_until(soda_hip_border_fused_t* f,
+                                    void* const* outputs,
+                                    const void* const* inputs,
+                                    int32_t max_iterate, int32_t check_every,
+                                    double tol, uint64_t int_tol,
+                                    soda_hip_residual_t* result_host,
+                                    int32_t* iterations_done, void* stream) {
+  if (!f || !outputs || !inputs)
+    return fail(SODA_HIP_ERR_INVALID, "border_fused_run_until: NULL argument");
+  return until_residual(f->main, outputs, inputs, max_iterate, check_every,
+                        tol, int_tol, result_host, iterations_done, stream, f);
+}
+
+int soda_hip_border_fused_run_until_norm(soda_hip_border_fused_t* f,
+                                         soda_hip_norms_handle_t* norms,
+                                         void* const* outputs,
+                                         const void* const* inputs,
+                                         int32_t max_iterate,
+                                         int32_t check_every, int32_t which,
+                                         double tol,
+                                         soda_hip_norms_t* result_host,
+                                         int32_t* iterations_done,
+                                         void* stream) {
+  if (!f || !norms || !outputs || !inputs)
+    return fail(SODA_HIP_ERR_INVALID,
+                "border_fused_run_until_norm: NULL argument");
+  return until_norm(f->main, norms, outputs, inputs, max_iterate, check_every,
+                    which, tol, result_host, iterations_done, stream, f);
 }
 
 }  // extern "C"

@@ -298,6 +298,23 @@ class BorderFusedInfo(ctypes.Structure):
               ('scratch_bytes', ctypes.c_int64)]
 
 
+class BorderRims(ctypes.Structure):
+  """Mirror of soda_hip_border_rims_t."""
+  _fields_ = [('dim', ctypes.c_int32),
+              ('reserved', ctypes.c_int32),
+              ('lo', (ctypes.c_int32 * MAX_DIM) * 2),
+              ('hi', (ctypes.c_int32 * MAX_DIM) * 2)]
+
+
+class BorderFusedBoxes(ctypes.Structure):
+  """Mirror of soda_hip_border_fused_boxes_t."""
+  _fields_ = [('depth', ctypes.c_int32),
+              ('num_strips', ctypes.c_int32),
+              ('trusted_lo', ctypes.c_int32 * MAX_DIM),
+              ('trusted_hi', ctypes.c_int32 * MAX_DIM),
+              ('strip', BorderRims * MAX_DIM)]
+
+
 # every symbol include/soda_hip.h declares: name -> (restype, argtypes)
 _vp = ctypes.c_void_p
 _i32 = ctypes.c_int32
@@ -440,6 +457,24 @@ API = {
                                                         _vp]),
     'soda_hip_border_fused_run_device': (ctypes.c_int, [_vp, _pvp, _pvp, _i32,
                                                         _vp]),
+    'soda_hip_border_fused_residual_boxes': (ctypes.c_int, [
+        ctypes.POINTER(Plan), ctypes.POINTER(BorderFusedDesc),
+        ctypes.POINTER(BorderFusedBoxes)
+    ]),
+    **{
+        'soda_hip_%s_%s' % (handle, name): (ctypes.c_int, argtypes)
+        for handle in ('periodic', 'border', 'border_fused')
+        for name, argtypes in (
+            ('run_padded_residual', [_vp, _pvp, _pvp, _i32, _vp, _vp]),
+            ('run_padded_norms', [_vp, _vp, _pvp, _pvp, _i32, _vp, _vp]),
+            ('run_until', [_vp, _pvp, _pvp, _i32, _i32, ctypes.c_double,
+                           ctypes.c_uint64, ctypes.POINTER(ResidualStruct),
+                           _pi32, _vp]),
+            ('run_until_norm', [_vp, _vp, _pvp, _pvp, _i32, _i32, _i32,
+                                ctypes.c_double, ctypes.POINTER(NormsStruct),
+                                _pi32, _vp]),
+        )
+    },
     'soda_hip_run_device_window': (ctypes.c_int, [_vp, _pvp, _pvp, _pi32, _pi32,
                                                   _pi32, _i32, _vp]),
     'soda_hip_run_device_cone': (ctypes.c_int, [_vp, _pvp, _pvp, _pi32, _pi32,
@@ -579,7 +614,8 @@ def library() -> ctypes.CDLL:
                           (12, ResBox), (14, NormsStruct),
                           (15, PeriodicDesc), (16, PeriodicInfo),
                           (17, BorderDesc), (18, BorderFusedDesc),
-                          (19, BorderStrip), (20, BorderFusedInfo)):
+                          (19, BorderStrip), (20, BorderFusedInfo),
+                          (21, BorderFusedBoxes)):
       if lib.soda_hip_sizeof(which) != ctypes.sizeof(mirror):
         raise util.BackendError(
             'struct layout mismatch between libsoda_hip.so and runtime.py '
@@ -1593,12 +1629,75 @@ class Periodic:
           '%s of `%s`' % (what, st.app_name))
 
   def run_padded(self, outputs: Sequence[int], inputs: Sequence[int],
-                 iterate: Optional[int] = None, stream: int = 0) -> None:
+                 iterate: Optional[int] = None, stream: int = 0,
+                 residual: Optional[int] = None,
+                 norms: Optional[int] = None) -> None:
     """`iterate` iterations on PADDED device arrays of info()['padded']: the
     inputs (then the param arrays) arrive wrapped, the outputs leave wrapped,
-    the inputs are never written (soda_hip_periodic_run_padded)."""
-    self._run(self._fn('run_padded'), '%s run_padded' % self._what,
+    the inputs are never written (soda_hip_periodic_run_padded).
+    `residual` = the device address of 32 bytes / `norms` = of a
+    soda_hip_norms_t (8-byte aligned, one of the two): the run also leaves
+    there how much its LAST iteration changed the DOMAIN, all of its cells and
+    no ghost cell (soda_hip_periodic_run_padded_residual / _norms; DESIGN.md
+    4.14; `Program.residual(ptr)` / `Program.norms().fetch(ptr)` read them).
+    The struct is zeroed on `stream` inside the call, which stays asynchronous
+    and capturable.  Needs a program built with LowerOptions.residual."""
+    if residual is None and norms is None:
+      return self._run(self._fn('run_padded'), '%s run_padded' % self._what,
+                       outputs, inputs, iterate, stream)
+    if residual is not None and norms is not None:
+      raise util.InputError('%s run_padded: residual or norms, not both' %
+                            self._what)
+    if residual is not None:
+      fn = self._fn('run_padded_residual')
+      entry = lambda h, outs, ins, n, on: fn(h, outs, ins, n,
+                                             ctypes.c_void_p(residual), on)
+    else:
+      fn, nh = self._fn('run_padded_norms'), self.prog.norms()._handle
+      entry = lambda h, outs, ins, n, on: fn(h, nh, outs, ins, n,
+                                             ctypes.c_void_p(norms), on)
+    self._run(entry, '%s run_padded with %s' % (
+        self._what, 'a residual' if norms is None else 'norms'),
               outputs, inputs, iterate, stream)
+
+  def run_until(self, outputs: Sequence[int], inputs: Sequence[int],
+                tol: float, max_iterate: int, check_every: int = 8,
+                int_tol: int = 0, norm: Optional[str] = None,
+                stream: int = 0):
+    """Iterates on DENSE device arrays of the domain's extent until converged
+    (soda_hip_periodic_run_until / _until_norm; synchronous): `check_every`
+    iterations at a time on the handle's padded scratch, the stop rules of
+    `Program.run_until` on the residual of the whole domain (`norm` = 'l1' |
+    'l2': on that exact norm).  Returns (iterations done, Residual -- or the
+    NormsStruct of the last chunk)."""
+    if norm not in (None, 'l1', 'l2'):
+      raise util.InputError("run_until: norm is None, 'l1' or 'l2'")
+    st = self.prog.stencil
+    if len(outputs) != len(st.output_names) or \
+        len(inputs) != len(st.input_names) + len(st.param_stmts):
+      raise util.InputError('%s run_until: %d outputs, %d inputs and param '
+                            'arrays' % (self._what, len(st.output_names),
+                                        len(st.input_names) +
+                                        len(st.param_stmts)))
+    outs = (ctypes.c_void_p * len(outputs))(*outputs)
+    ins = (ctypes.c_void_p * len(inputs))(*inputs)
+    done = ctypes.c_int32(0)
+    on = ctypes.c_void_p(stream)
+    if norm is None:
+      raw = ResidualStruct()
+      check(self._fn('run_until')(
+          self._handle, outs, ins, int(max_iterate), int(check_every),
+          float(tol), int(int_tol), ctypes.byref(raw), ctypes.byref(done), on),
+            '%s: running `%s` until converged' % (self._what, st.app_name))
+      return done.value, Residual.from_struct(raw)
+    raw = NormsStruct()
+    check(self._fn('run_until_norm')(
+        self._handle, self.prog.norms()._handle, outs, ins, int(max_iterate),
+        int(check_every), {'l1': NORMS_L1, 'l2': NORMS_L2}[norm], float(tol),
+        ctypes.byref(raw), ctypes.byref(done), on),
+          '%s: running `%s` until its %s norm is small' % (
+              self._what, st.app_name, norm))
+    return done.value, raw
 
   def run_device(self, outputs: Sequence[int], inputs: Sequence[int],
                  iterate: Optional[int] = None, stream: int = 0) -> None:
@@ -1892,6 +1991,42 @@ def border_fused_plan(plan: Plan, extent: Sequence[int], modes, depth: int,
       ctypes.byref(plan), ctypes.byref(desc), iterate, ctypes.byref(raw), cap,
       chunks, ctypes.byref(n)), 'border_fused_plan')
   return _border_fused_info(raw, plan.dim), list(chunks[:n.value])
+
+
+def border_fused_residual_boxes(plan: Plan, extent: Sequence[int], modes,
+                                depth: int, reach_lo: Sequence[int],
+                                reach_hi: Sequence[int],
+                                ghost_lo: Sequence[int],
+                                ghost_hi: Sequence[int],
+                                preserve: bool = False,
+                                not_iterable: bool = False) -> dict:
+  """The partition of the domain by which a fused bordered handle counts a
+  residual (soda_hip_border_fused_residual_boxes; no GPU needed; arguments as
+  border_fused_plan): {'depth' as resolved, 'trusted': (lo, hi) in the padded
+  coordinates of the domain, 'strips': [{'dim', 'low': (lo, hi), 'high': (lo,
+  hi)}] in each strip's own padded coordinates}, dimension 0 first.  At depth
+  1 and on a torus there are no strips and the trusted box is the domain."""
+  raw_modes = list(modes) if not isinstance(modes, str) and all(
+      isinstance(m, int) for m in modes) else _border_modes(modes, plan.dim)
+  if len(raw_modes) != plan.dim or len(reach_lo) != plan.dim or \
+      len(reach_hi) != plan.dim:
+    raise util.InputError('border: one mode and one reach per side per '
+                          'dimension (%d)' % plan.dim)
+  desc = _border_fused_desc(_border_desc(_periodic_desc(
+      plan.dim, extent, 0, ghost_lo, ghost_hi, preserve, not_iterable),
+                                         raw_modes, ()), depth, reach_lo,
+                            reach_hi)
+  raw = BorderFusedBoxes()
+  check(library().soda_hip_border_fused_residual_boxes(
+      ctypes.byref(plan), ctypes.byref(desc), ctypes.byref(raw)),
+        'border_fused_residual_boxes')
+  dim = plan.dim
+  box = lambda lo, hi: (tuple(lo[:dim]), tuple(hi[:dim]))
+  return {'depth': raw.depth,
+          'trusted': box(raw.trusted_lo, raw.trusted_hi),
+          'strips': [{'dim': s.dim, 'low': box(s.lo[0], s.hi[0]),
+                      'high': box(s.lo[1], s.hi[1])}
+                     for s in raw.strip[:raw.num_strips]]}
 
 
 class BorderedFused(Bordered):
@@ -2523,6 +2658,57 @@ class Program:
       bor.run_device(dev_out, dev_in, iterate)
       _copy_out(lib, dense, dev_out, 'run_bordered')
     return result
+
+  def _run_domain_until(self, handle, what, inputs, tol, max_iterate,
+                        check_every, int_tol, norm):
+    """run_until's numpy plumbing around `handle`.run_until (which is closed
+    here)."""
+    import numpy as np
+    st = self.stencil
+    lib = self._lib
+    first = np.asarray(inputs[st.input_names[0]])
+    host_in = _host_inputs(st, inputs, first.shape)
+    result = {n: np.empty(first.shape, dtype=np.dtype(t.np_name))
+              for n, t in zip(st.output_names, st.output_types)}
+    dense = list(result.values())
+    with handle as dom, _staged(lib, self.device, host_in, dense, what,
+                                synchronize=True) as (dev_in, dev_out):
+      done, last = dom.run_until(dev_out, dev_in, tol, max_iterate,
+                                 check_every, int_tol, norm)
+      _copy_out(lib, dense, dev_out, what)
+    return result, done, last
+
+  def run_periodic_until(self, inputs: Dict[str, 'numpy.ndarray'], tol: float,
+                         max_iterate: int, check_every: int = 8,
+                         int_tol: int = 0, norm: Optional[str] = None,
+                         refill_every: Optional[int] = None):
+    """`run_until` on a torus: numpy arrays of the domain in; returns (outputs,
+    iterations done, Residual -- or NormsStruct with `norm`), EVERY cell of
+    the outputs defined and every cell of the domain counted
+    (Periodic.run_until)."""
+    import numpy as np
+    extent = tuple(np.asarray(inputs[self.stencil.input_names[0]]).shape[::-1])
+    if norm not in (None, 'l1', 'l2'):
+      raise util.InputError("run_until: norm is None, 'l1' or 'l2'")
+    return self._run_domain_until(
+        self.periodic(extent, refill_every), 'run_periodic_until', inputs, tol,
+        max_iterate, check_every, int_tol, norm)
+
+  def run_bordered_until(self, inputs: Dict[str, 'numpy.ndarray'], modes,
+                         tol: float, max_iterate: int, constants=None,
+                         depth: int = 1, check_every: int = 8,
+                         int_tol: int = 0, norm: Optional[str] = None):
+    """`run_until` with borders (`modes`, `constants`, `depth` as for
+    `run_bordered`): returns (outputs, iterations done, Residual -- or
+    NormsStruct with `norm`), EVERY cell of the outputs defined and every cell
+    of the domain counted (Bordered.run_until)."""
+    import numpy as np
+    extent = tuple(np.asarray(inputs[self.stencil.input_names[0]]).shape[::-1])
+    if norm not in (None, 'l1', 'l2'):
+      raise util.InputError("run_until: norm is None, 'l1' or 'l2'")
+    return self._run_domain_until(
+        self.bordered(extent, modes, constants, depth), 'run_bordered_until',
+        inputs, tol, max_iterate, check_every, int_tol, norm)
 
   def run_batch(self, inputs: Dict[str, 'numpy.ndarray'],
                 iterate: Optional[int] = None) -> Dict[str, 'numpy.ndarray']:
