@@ -21,6 +21,9 @@
 // of a run takes the residual through run_core with the interior as its box;
 // a fused handle counts each cell where it is made right -- the interior run
 // a trusted box, every strip its two rims.
+//
+// Top to bottom: the helper kernels' launchers and loader, planning, the two
+// handle structs, the chunk loop, the run cores, the exported entries.
 #include "soda_internal.h"
 
 #include <cstring>
@@ -30,11 +33,14 @@ using namespace soda_detail;
 
 namespace {
 
-const int kWrapBlock = 256;
-const int kWrapMaxRegions = 5;
-const int64_t kWrapMaxBlocks = 1 << 15;   // the lanes stride over the items
+// -- the helper kernels: their arguments, their launches, their modules ------
 
-// the kernel's one argument, as soda_rt_wrap.h declares it
+const int kHelperBlock = 256;
+const int kWrapMaxRegions = 5;
+const int kBoxMax = 4;
+const int64_t kHelperMaxBlocks = 1 << 15;   // the lanes stride over the items
+
+// the wrap kernel's one argument, as soda_rt_wrap.h declares it
 struct WrapArgs {
   void* dst[16];
   const void* src[16];
@@ -60,6 +66,26 @@ struct ExtendArgs {
   uint64_t constant[16];
 };
 
+// the box kernel's one argument, as soda_rt_box.h declares it
+struct BoxArgs {
+  void* dst[16];
+  const void* src[16];
+  int32_t dext[4];
+  int32_t sext[4];
+  int32_t nbox;
+  uint32_t reserved;
+  int32_t dorg[kBoxMax][4];
+  int32_t sorg[kBoxMax][4];
+  int32_t size[kBoxMax][4];
+  uint32_t per_row[kBoxMax];
+  uint64_t start[kBoxMax];
+  uint64_t total;
+};
+
+struct Box {
+  int32_t to[4], from[4], size[4];
+};
+
 enum WrapJob { kFill, kPad, kCrop };
 
 // what tells a torus from a bordered domain: the names in messages, the kernel
@@ -76,6 +102,31 @@ struct Torus {
   int dim;
   int32_t n[4], glo[4], ghi[4], p[4];
 };
+
+// the modules and kernels of one helper (wrap or extend, box), by log2(elem)
+struct Helpers {
+  hipModule_t module[4] = {nullptr, nullptr, nullptr, nullptr};
+  hipFunction_t fn[4] = {nullptr, nullptr, nullptr, nullptr};
+};
+
+// what a wrap launch needs of a handle: the frame and the rule that fills it
+struct Frame {
+  const Kind* kind = &kTorus;
+  int32_t mode[4] = {0, 0, 0, 0};      // kBorder: SODA_HIP_BORDER_* ...
+  uint64_t constant[SODA_HIP_MAX_TENSORS] = {};   // ... and per input
+  Torus t;
+  Helpers wrap;                        // the wrap or the extend kernels
+};
+
+int log2_elem(int elem) {
+  return elem == 1 ? 0 : elem == 2 ? 1 : elem == 4 ? 2 : elem == 8 ? 3 : -1;
+}
+
+int64_t cells_of(const int32_t* e, int dim) {
+  int64_t c = 1;
+  for (int d = 0; d < dim; ++d) c *= e[d];
+  return c;
+}
 
 int32_t plan_vec(const soda_hip_plan_t& plan) {
   int32_t vec = 1;
@@ -132,77 +183,176 @@ bool wrap_regions(const Torus& t, WrapJob job, int elem, WrapArgs* a) {
   return add(0, inner, (int64_t)t.glo[0] + t.ghi[0], true);
 }
 
-}  // namespace
-
-struct soda_hip_border_fused;
-
-struct soda_hip_periodic {
-  soda_hip_program* prog = nullptr;
-  const Kind* kind = &kTorus;
-  int32_t mode[4] = {0, 0, 0, 0};      // kBorder: SODA_HIP_BORDER_* ...
-  uint64_t constant[SODA_HIP_MAX_TENSORS] = {};   // ... and per input
-  Torus t;
-  int32_t k = 1;
-  bool not_iterable = false;
-  hipModule_t module[4] = {nullptr, nullptr, nullptr, nullptr};
-  hipFunction_t fn[4] = {nullptr, nullptr, nullptr, nullptr};   // by log2(elem)
-  std::vector<DeviceBuffer> pad_in;    // dense entry: the padded inputs
-  std::vector<DeviceBuffer> pad_out;   // ... and outputs
-  std::vector<DeviceBuffer> pong;      // the chunks' partner of the outputs
-};
-
-namespace {
-
-int log2_elem(int elem) {
-  return elem == 1 ? 0 : elem == 2 ? 1 : elem == 4 ? 2 : elem == 8 ? 3 : -1;
-}
-
-int64_t cells_of(const int32_t* e, int dim) {
-  int64_t c = 1;
-  for (int d = 0; d < dim; ++d) c *= e[d];
-  return c;
-}
-
-// One job on `count` tensors: dst[i] / src[i] with cells of elem[i] bytes (a
-// bordered domain: and the constant of input i); one launch per cell size
-// among them.
-int wrap_launch(soda_hip_periodic* h, WrapJob job, void* const* dst,
-                const void* const* src, const int32_t* elem, int count,
-                hipStream_t stream) {
-  const std::string who(h->kind->who);
+// One launch of a helper kernel per cell size among `count` tensors with cells
+// of elem[i] bytes.  `prepare(size, tensor, m, &args, &total)` fills the
+// kernel's argument for the `m` tensors tensor[0..m) of that size and says
+// how many items the launch has (0: none, it is skipped), or refuses.  `bytes`
+// of `args` reach the kernel.
+template <class Args, class Prepare>
+int launch_by_size(const Helpers& kernels, const char* who, const char* what,
+                   const int32_t* elem, int count, size_t bytes,
+                   hipStream_t stream, Prepare prepare) {
   for (int size = 1; size <= 8; size *= 2) {
-    ExtendArgs args;
-    memset(&args, 0, sizeof args);
-    WrapArgs& a = args.w;
-    int m = 0;
+    int tensor[16], m = 0;
     for (int i = 0; i < count; ++i)
-      if (elem[i] == size) {
-        a.dst[m] = dst[i];
-        a.src[m] = src[i];
-        args.constant[m] = h->constant[i];
-        ++m;
-      }
+      if (elem[i] == size) tensor[m++] = i;
     if (!m) continue;
-    if (!wrap_regions(h->t, job, size, &a))
+    Args args;
+    memset(&args, 0, sizeof args);
+    uint64_t total = 0;
+    if (int rc = prepare(size, tensor, m, &args, &total)) return rc;
+    if (!total) continue;
+    hipFunction_t fn = kernels.fn[log2_elem(size)];
+    if (!fn)
       return fail(SODA_HIP_ERR_INVALID,
-                  who + ": 2^31 rows or more; nothing was launched");
-    if (!a.total) continue;          // no ghost cells: nothing to fill
-    hipFunction_t fn = h->fn[log2_elem(size)];
-    if (!fn) return fail(SODA_HIP_ERR_INVALID, who + ": no wrap kernel");
-    int64_t blocks = (int64_t)((a.total + kWrapBlock - 1) / kWrapBlock);
-    if (blocks > kWrapMaxBlocks) blocks = kWrapMaxBlocks;
-    for (int d = 0; d < 4; ++d) args.mode[d] = h->mode[d];
-    // the wrap kernel takes the block without the border behind it
-    size_t bytes = h->kind->extend ? sizeof args : sizeof a;
+                  std::string(who) + ": no " + what + " kernel");
+    int64_t blocks = (int64_t)((total + kHelperBlock - 1) / kHelperBlock);
+    if (blocks > kHelperMaxBlocks) blocks = kHelperMaxBlocks;
     void* extra[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &args,
                      HIP_LAUNCH_PARAM_BUFFER_SIZE, &bytes,
                      HIP_LAUNCH_PARAM_END};
     HIP_TRY(hipModuleLaunchKernel(fn, (unsigned)blocks, (unsigned)m, 1,
-                                  kWrapBlock, 1, 1, 0, stream, nullptr,
+                                  kHelperBlock, 1, 1, 0, stream, nullptr,
                                   extra));
   }
   return SODA_HIP_OK;
 }
+
+// One job on `count` tensors: dst[i] / src[i] with cells of elem[i] bytes (a
+// bordered domain: and the constant of input i); one launch per cell size
+// among them (no ghost cells: nothing to fill, no launch).
+int wrap_launch(const Frame& f, WrapJob job, void* const* dst,
+                const void* const* src, const int32_t* elem, int count,
+                hipStream_t stream) {
+  // the wrap kernel takes the block without the border behind it
+  const size_t bytes = f.kind->extend ? sizeof(ExtendArgs) : sizeof(WrapArgs);
+  return launch_by_size<ExtendArgs>(
+      f.wrap, f.kind->who, "wrap", elem, count, bytes, stream,
+      [&](int size, const int* tensor, int m, ExtendArgs* args,
+          uint64_t* total) -> int {
+        for (int j = 0; j < m; ++j) {
+          args->w.dst[j] = dst[tensor[j]];
+          args->w.src[j] = src[tensor[j]];
+          args->constant[j] = f.constant[tensor[j]];
+        }
+        for (int d = 0; d < 4; ++d) args->mode[d] = f.mode[d];
+        if (!wrap_regions(f.t, job, size, &args->w))
+          return fail(SODA_HIP_ERR_INVALID,
+                      std::string(f.kind->who) +
+                          ": 2^31 rows or more; nothing was launched");
+        *total = args->w.total;
+        return SODA_HIP_OK;
+      });
+}
+
+// `nbox` boxes from the arrays src[i] of extent `sext` into dst[i] of `dext`,
+// `count` tensors with cells of elem[i] bytes; one launch per cell size among
+// them.  A box that leaves either extent is refused before anything runs.
+int box_launch(const Helpers& kernels, void* const* dst, const int32_t* dext,
+               const void* const* src, const int32_t* sext,
+               const int32_t* elem, int count, const Box* boxes, int nbox,
+               int dim, hipStream_t stream) {
+  for (int b = 0; b < nbox; ++b)
+    for (int d = 0; d < dim; ++d) {
+      const Box& x = boxes[b];
+      if (x.size[d] < 0 || x.to[d] < 0 || x.from[d] < 0 ||
+          (int64_t)x.to[d] + x.size[d] > dext[d] ||
+          (int64_t)x.from[d] + x.size[d] > sext[d])
+        return fail(SODA_HIP_ERR_INVALID,
+                    "border_fused: a box leaves its array; nothing was "
+                    "launched");
+    }
+  return launch_by_size<BoxArgs>(
+      kernels, "border_fused", "box", elem, count, sizeof(BoxArgs), stream,
+      [&](int size, const int* tensor, int m, BoxArgs* a,
+          uint64_t* total) -> int {
+        for (int j = 0; j < m; ++j) {
+          a->dst[j] = dst[tensor[j]];
+          a->src[j] = src[tensor[j]];
+        }
+        const int v = 16 / size;
+        for (int d = 0; d < 4; ++d) {
+          a->dext[d] = d < dim ? dext[d] : 1;
+          a->sext[d] = d < dim ? sext[d] : 1;
+        }
+        for (int b = 0; b < nbox && a->nbox < kBoxMax; ++b) {
+          int64_t rows = 1;
+          bool empty = false;
+          for (int d = 0; d < dim; ++d) {
+            if (boxes[b].size[d] < 1) empty = true;
+            if (d) rows *= boxes[b].size[d];
+          }
+          if (empty) continue;
+          if (rows > 0x7fffffffLL)
+            return fail(SODA_HIP_ERR_INVALID,
+                        "border_fused: 2^31 rows or more; nothing was "
+                        "launched");
+          const int k = a->nbox++;
+          for (int d = 0; d < 4; ++d) {
+            a->dorg[k][d] = d < dim ? boxes[b].to[d] : 0;
+            a->sorg[k][d] = d < dim ? boxes[b].from[d] : 0;
+            a->size[k][d] = d < dim ? boxes[b].size[d] : 1;
+          }
+          // fragments a row may need: it starts up to v - 1 cells behind a
+          // 16-byte boundary
+          a->per_row[k] =
+              (uint32_t)(((int64_t)boxes[b].size[0] + 2 * v - 2) / v);
+          a->start[k] = a->total;
+          a->total += (uint64_t)rows * a->per_row[k];
+        }
+        *total = a->total;
+        return SODA_HIP_OK;
+      });
+}
+
+// need[l]: cells of 1 << l bytes are among the program's inputs and outputs.
+// Refuses any other cell size, and a needed size whose `what` module is not
+// in `code`.
+int helpers_needed(const soda_hip_plan_t& plan, const void* const* code,
+                   const size_t* code_size, const std::string& who,
+                   const char* what, bool need[4]) {
+  for (int s = 0; s < plan.num_inputs + plan.num_outputs; ++s) {
+    const int l = log2_elem(plan.elem_size[s]);
+    if (l < 0)
+      return fail(SODA_HIP_ERR_UNSUPPORTED,
+                  who + ": cells of 1, 2, 4 or 8 bytes only");
+    need[l] = true;
+  }
+  for (int l = 0; l < 4; ++l)
+    if (need[l] && (!code[l] || !code_size[l]))
+      return fail(SODA_HIP_ERR_INVALID,
+                  who + "_create: the " + what + " module of a cell size of "
+                        "the program is missing");
+  return SODA_HIP_OK;
+}
+
+// The module of every needed cell size loaded from `code`, and its kernel
+// `<kernel>_e<bytes>_d<dim>` looked up.
+int load_helpers(Helpers* out, const bool need[4], const void* const* code,
+                 const char* kernel, int dim, const std::string& who,
+                 const char* what) {
+  for (int l = 0; l < 4; ++l) {
+    if (!need[l]) continue;
+    hipError_t e = hipModuleLoadData(&out->module[l], code[l]);
+    if (e != hipSuccess)
+      return hip_fail(e, (who + "_create: hipModuleLoadData").c_str());
+    char name[64];
+    snprintf(name, sizeof name, "%s_e%d_d%d", kernel, 1 << l, dim);
+    e = hipModuleGetFunction(&out->fn[l], out->module[l], name);
+    if (e != hipSuccess)
+      return hip_fail(e, (who + "_create: hipModuleGetFunction (is this the " +
+                          what + " module of the cell size and dimension "
+                                 "count?)").c_str());
+  }
+  return SODA_HIP_OK;
+}
+
+void unload_helpers(Helpers* h) {
+  for (auto& m : h->module)
+    if (m) (void)hipModuleUnload(m);
+}
+
+// -- planning: no GPU ---------------------------------------------------------
 
 bool can_iterate(const soda_hip_plan_t& plan, bool not_iterable) {
   if (not_iterable || plan.num_inputs != plan.num_outputs) return false;
@@ -226,144 +376,25 @@ int check_iterate(const soda_hip_plan_t& plan, bool not_iterable,
   return SODA_HIP_OK;
 }
 
-// The device entry contract (include/soda_hip.h, soda_hip_run_device) on the
-// caller's arrays, each the dense array of `extent`: no output shares a byte
-// with an input, a param array or another output; inputs and outputs are
-// aligned to min(16, vec x cell size) bytes.
-int check_contract(const soda_hip_plan_t& plan, void* const* outputs,
-                   const void* const* inputs, const int32_t* extent,
-                   const char* who_) {
-  const std::string who(who_);
-  const int nin = plan.num_inputs, nout = plan.num_outputs;
-  const int prm0 = nin + nout + plan.num_locals;
-  for (int i = 0; i < nin + plan.num_params; ++i)
-    if (!inputs[i]) return fail(SODA_HIP_ERR_INVALID, who + ": NULL input");
-  for (int o = 0; o < nout; ++o)
-    if (!outputs[o]) return fail(SODA_HIP_ERR_INVALID, who + ": NULL output");
-  const uint64_t cells = (uint64_t)cells_of(extent, plan.dim);
-  auto overlap = [](const void* a, uint64_t na, const void* b, uint64_t nb) {
-    const uintptr_t a0 = reinterpret_cast<uintptr_t>(a);
-    const uintptr_t b0 = reinterpret_cast<uintptr_t>(b);
-    return a0 < b0 + nb && b0 < a0 + na;
-  };
-  for (int o = 0; o < nout; ++o) {
-    const uint64_t no = cells * plan.elem_size[nin + o];
-    for (int i = 0; i < nin; ++i)
-      if (overlap(outputs[o], no, inputs[i], cells * plan.elem_size[i]))
-        return fail(SODA_HIP_ERR_INVALID,
-                    who + ": an output overlaps an input; nothing was "
-                          "launched");
-    for (int k = 0; k < plan.num_params; ++k)
-      if (overlap(outputs[o], no, inputs[nin + k],
-                  (uint64_t)plan.param_elems[k] * plan.elem_size[prm0 + k]))
-        return fail(SODA_HIP_ERR_INVALID,
-                    who + ": an output overlaps a param array; nothing was "
-                          "launched");
-    for (int q = 0; q < o; ++q)
-      if (overlap(outputs[o], no, outputs[q],
-                  cells * plan.elem_size[nin + q]))
-        return fail(SODA_HIP_ERR_INVALID,
-                    who + ": two outputs overlap; nothing was launched");
-  }
-  const int32_t vec = plan_vec(plan);
-  for (int t = 0; t < nin + nout; ++t) {
-    const void* ptr = t < nin ? inputs[t] : outputs[t - nin];
-    int64_t align = (int64_t)vec * plan.elem_size[t];
-    if (align > 16) align = 16;
-    if (reinterpret_cast<uintptr_t>(ptr) % (uintptr_t)align) {
-      char buf[200];
-      snprintf(buf, sizeof buf,
-               ": %s %d at %p is not aligned to %d bytes; nothing was "
-               "launched", t < nin ? "input" : "output",
-               t < nin ? t : t - nin, ptr, (int)align);
-      return fail(SODA_HIP_ERR_INVALID, who + buf);
-    }
-  }
-  return SODA_HIP_OK;
+// the deepest fusion of the plan's passes: the default chunk of a handle
+int32_t deepest_pass(const soda_hip_plan_t& plan) {
+  int32_t deepest = 0;
+  for (int i = 0; i < plan.num_passes; ++i)
+    if (plan.passes[i].fused_iters > deepest)
+      deepest = plan.passes[i].fused_iters;
+  return deepest;
 }
 
-// The same box for every pair: [lo, hi) per dimension of the handle's padded
-// arrays.
-soda_hip_resbox_t resbox_of(const soda_hip_periodic* h, const int32_t* lo,
-                            const int32_t* hi) {
-  soda_hip_resbox_t box;
-  memset(&box, 0, sizeof box);
-  for (int o = 0; o < h->prog->plan.num_outputs; ++o)
-    for (int d = 0; d < SODA_HIP_MAX_DIM; ++d) {
-      box.lo[o][d] = d < h->t.dim ? lo[d] : 0;
-      box.hi[o][d] = d < h->t.dim ? hi[d] : 1;
-    }
-  return box;
-}
+// the iterations of the next chunk of a run with `left` to go, `k` at most
+int32_t chunk_len(int32_t left, int32_t k) { return left < k ? left : k; }
 
-// the counted cells of a torus or a depth-1 bordered domain: the interior
-soda_hip_resbox_t interior_box(const soda_hip_periodic* h) {
-  int32_t hi[4];
-  for (int d = 0; d < 4; ++d) hi[d] = h->t.glo[d] + h->t.n[d];
-  return resbox_of(h, h->t.glo, hi);
-}
-
-// What the last chunk of run_chunks takes of a residual (DESIGN.md 4.14).
-// `behind` false: box[0] rides in the chunk's run (run_core: a twin, or the
-// generic kernels behind the one-iteration pass).  `behind` true, a strip:
-// every box is counted behind the chunk by the generic kernels, cur the
-// chunk's result, prev what it read.
-struct ChunkResidual {
-  ResidualRun run;
-  soda_hip_resbox_t box[2];
-  int nbox;
-  bool behind;
-};
-
-// The chunks of a run on padded arrays: `inputs` wrapped in, `outputs` wrapped
-// out, the chunks alternating between `outputs` and the handle's `pong` so
-// that the last one lands in `outputs`.
-int run_chunks(soda_hip_periodic* h, void* const* outputs,
-               const void* const* inputs, int32_t iterate, void* stream,
-               const ChunkResidual* res = nullptr) {
-  soda_hip_program* p = h->prog;
-  const soda_hip_plan_t& plan = p->plan;
-  const int nin = plan.num_inputs, nout = plan.num_outputs;
-  const int chunks = (iterate + h->k - 1) / h->k;
-  std::vector<const void*> src(inputs, inputs + nin + plan.num_params);
-  std::vector<void*> dst(nout);
-  std::vector<int32_t> elem(nout);
-  for (int o = 0; o < nout; ++o) elem[o] = plan.elem_size[nin + o];
-  int32_t left = iterate;
-  for (int c = 0; c < chunks; ++c) {
-    const int32_t n = left < h->k ? left : h->k;
-    const bool to_out = ((chunks - 1 - c) % 2) == 0;
-    for (int o = 0; o < nout; ++o)
-      dst[o] = to_out ? outputs[o] : h->pong[o].ptr;
-    RunRequest rq = {dst.data(), src.data(), h->t.p, n, stream};
-    ResidualRun riding;
-    if (res && c + 1 == chunks && !res->behind) {
-      riding = res->run;
-      riding.box = &res->box[0];
-      rq.residual = &riding;
-    }
-    if (int rc = run_core(p, rq)) return rc;
-    if (res && c + 1 == chunks && res->behind)
-      for (int b = 0; b < res->nbox; ++b)
-        if (int rc = residual_add(p, dst.data(), src.data(), h->t.p, res->run,
-                                  res->box[b], stream))
-          return rc;
-    if (int rc = wrap_launch(h, kFill, dst.data(), dst.data(), elem.data(),
-                             nout, static_cast<hipStream_t>(stream)))
-      return rc;
-    left -= n;
-    if (c + 1 < chunks)
-      for (int i = 0; i < nin; ++i) src[i] = dst[i];
-  }
-  return SODA_HIP_OK;
-}
-
-// run_chunks that takes the residual of `run` over the handle's interior
-int run_chunks_residual(soda_hip_periodic* h, void* const* outputs,
-                        const void* const* inputs, int32_t iterate,
-                        void* stream, const ResidualRun& run) {
-  const ChunkResidual res = {run, {interior_box(h), {}}, 1, false};
-  return run_chunks(h, outputs, inputs, iterate, stream, &res);
+// a plan entry's answer: the chunks of a run of `iterate` in chunks of `k`
+void list_chunks(int32_t iterate, int32_t k, int32_t capacity, int32_t* chunks,
+                 int32_t* count) {
+  int32_t n = 0;
+  for (int32_t left = iterate; left > 0; left -= k, ++n)
+    if (chunks && n < capacity) chunks[n] = chunk_len(left, k);
+  if (count) *count = n;
 }
 
 // soda_hip_periodic_plan, and soda_hip_border_plan behind its modes
@@ -390,9 +421,7 @@ int plan_core(const Kind& kind, const soda_hip_plan_t* plan,
   int32_t k = desc->refill_every;
   if (k < 0)
     return fail(SODA_HIP_ERR_INVALID, who + ": refill_every < 0");
-  if (k == 0)
-    for (int i = 0; i < plan->num_passes; ++i)
-      if (plan->passes[i].fused_iters > k) k = plan->passes[i].fused_iters;
+  if (k == 0) k = deepest_pass(*plan);
   if (k < 1) return fail(SODA_HIP_ERR_INVALID, who + ": bad plan");
   soda_hip_periodic_info_t out;
   memset(&out, 0, sizeof out);
@@ -449,341 +478,7 @@ int plan_core(const Kind& kind, const soda_hip_plan_t* plan,
         cells * plan->elem_size[nin + o] *
         (can_iterate(*plan, desc->not_iterable != 0) ? 2 : 1);
   if (info) *info = out;
-  int32_t n = 0;
-  for (int32_t left = iterate; left > 0; left -= k, ++n)
-    if (chunks && n < capacity) chunks[n] = left < k ? left : k;
-  if (count) *count = n;
-  return SODA_HIP_OK;
-}
-
-
-int create_core(const Kind& kind, soda_hip_program_t* p,
-                const soda_hip_periodic_desc_t* desc, const int32_t* mode,
-                const uint64_t* constant, const void* const* code,
-                const size_t* code_size, soda_hip_periodic** handle) {
-  const std::string who(kind.who);
-  const soda_hip_plan_t& plan = p->plan;
-  if (p->bank_tensors)
-    return fail(SODA_HIP_ERR_UNSUPPORTED,
-                who + ": programs on wire-format banks are not served on " +
-                    kind.domain + "; nothing was launched");
-  soda_hip_periodic_info_t info;
-  if (int rc = plan_core(kind, &plan, desc, 0, &info, 0, nullptr, nullptr))
-    return rc;
-  const int nin = plan.num_inputs, nout = plan.num_outputs;
-  bool need[4] = {false, false, false, false};
-  for (int s = 0; s < nin + nout; ++s) {
-    const int l = log2_elem(plan.elem_size[s]);
-    if (l < 0)
-      return fail(SODA_HIP_ERR_UNSUPPORTED,
-                  who + ": cells of 1, 2, 4 or 8 bytes only");
-    need[l] = true;
-  }
-  for (int l = 0; l < 4; ++l)
-    if (need[l] && (!code[l] || !code_size[l]))
-      return fail(SODA_HIP_ERR_INVALID,
-                  who + "_create: the wrap module of a cell size of the "
-                        "program is missing");
-  HIP_TRY(hipSetDevice(p->device));
-  soda_hip_periodic* h = new (std::nothrow) soda_hip_periodic;
-  if (!h) return fail(SODA_HIP_ERR_NOMEM, "new " + who + " handle");
-  h->prog = p;
-  h->kind = &kind;
-  h->k = info.refill_every;
-  h->not_iterable = desc->not_iterable != 0;
-  const bool iterates = can_iterate(plan, h->not_iterable);
-  h->t.dim = plan.dim;
-  for (int d = 0; d < 4; ++d) {
-    h->t.n[d] = d < plan.dim ? desc->extent[d] : 1;
-    h->t.glo[d] = info.ghost_lo[d];
-    h->t.ghi[d] = info.ghost_hi[d];
-    h->t.p[d] = info.padded[d];
-    if (mode) h->mode[d] = d < plan.dim ? mode[d] : 0;
-  }
-  if (constant)
-    for (int i = 0; i < nin; ++i) h->constant[i] = constant[i];
-  int rc = SODA_HIP_OK;
-  for (int l = 0; l < 4 && !rc; ++l) {
-    if (!need[l]) continue;
-    hipError_t e = hipModuleLoadData(&h->module[l], code[l]);
-    if (e != hipSuccess) {
-      rc = hip_fail(e, (who + "_create: hipModuleLoadData").c_str());
-      break;
-    }
-    char name[64];
-    snprintf(name, sizeof name, "%s_e%d_d%d", kind.kernel, 1 << l, plan.dim);
-    e = hipModuleGetFunction(&h->fn[l], h->module[l], name);
-    if (e != hipSuccess)
-      rc = hip_fail(e, (who + "_create: hipModuleGetFunction (is this the "
-                              "wrap module of the cell size and dimension "
-                              "count?)").c_str());
-  }
-  const int64_t cells = cells_of(h->t.p, plan.dim);
-  h->pad_in.resize(nin);
-  h->pad_out.resize(nout);
-  h->pong.resize(iterates ? nout : 0);
-  for (int i = 0; i < nin && !rc; ++i)
-    rc = ensure(h->pad_in[i], (size_t)cells * plan.elem_size[i]);
-  for (int o = 0; o < nout && !rc; ++o) {
-    rc = ensure(h->pad_out[o], (size_t)cells * plan.elem_size[nin + o]);
-    if (!rc && iterates)
-      rc = ensure(h->pong[o], (size_t)cells * plan.elem_size[nin + o]);
-  }
-  if (rc) {
-    const std::string why = last_error_text();
-    soda_hip_periodic_destroy(h);
-    return fail(rc, why);
-  }
-  *handle = h;
-  return SODA_HIP_OK;
-}
-
-int fill_core(soda_hip_periodic* h, void* const* arrays, int32_t count,
-              void* stream) {
-  const std::string who(h->kind->who);
-  const soda_hip_plan_t& plan = h->prog->plan;
-  if (count < 0 || count > plan.num_outputs)
-    return fail(SODA_HIP_ERR_INVALID,
-                who + "_fill: one array per output at most; nothing was "
-                      "launched");
-  int32_t elem[SODA_HIP_MAX_TENSORS];
-  for (int i = 0; i < count; ++i) {
-    elem[i] = plan.elem_size[plan.num_inputs + i];
-    if (!arrays[i] || reinterpret_cast<uintptr_t>(arrays[i]) % elem[i])
-      return fail(SODA_HIP_ERR_INVALID,
-                  who + "_fill: an array is NULL or not aligned to its cell "
-                        "size; nothing was launched");
-  }
-  HIP_TRY(hipSetDevice(h->prog->device));
-  return wrap_launch(h, kFill, arrays,
-                     const_cast<const void* const*>(arrays), elem, count,
-                     static_cast<hipStream_t>(stream));
-}
-
-// (a fused bordered handle's chunks, below)
-int fused_chunks(soda_hip_border_fused* f, void* const* outputs,
-                 const void* const* inputs, int32_t iterate, void* stream,
-                 const ResidualRun* res = nullptr);
-
-// the chunks of a handle, fused or not, with or without a residual
-int any_chunks(soda_hip_periodic* h, soda_hip_border_fused* fused,
-               void* const* outputs, const void* const* inputs,
-               int32_t iterate, void* stream, const ResidualRun* res) {
-  if (fused) return fused_chunks(fused, outputs, inputs, iterate, stream, res);
-  if (res) return run_chunks_residual(h, outputs, inputs, iterate, stream, *res);
-  return run_chunks(h, outputs, inputs, iterate, stream);
-}
-
-// `fused`: the handle whose chunks these are, if not h's own
-int run_padded_core(soda_hip_periodic* h, void* const* outputs,
-                    const void* const* inputs, int32_t iterate, void* stream,
-                    soda_hip_border_fused* fused = nullptr) {
-  const std::string who = std::string(h->kind->who) + "_run_padded";
-  if (int rc = check_iterate(h->prog->plan, h->not_iterable, iterate,
-                             who.c_str()))
-    return rc;
-  if (int rc = check_contract(h->prog->plan, outputs, inputs, h->t.p,
-                              who.c_str()))
-    return rc;
-  if (fused) return fused_chunks(fused, outputs, inputs, iterate, stream);
-  return run_chunks(h, outputs, inputs, iterate, stream);
-}
-
-int run_device_core(soda_hip_periodic* h, void* const* outputs,
-                    const void* const* inputs, int32_t iterate,
-                    void* stream_, soda_hip_border_fused* fused = nullptr) {
-  const std::string who = std::string(h->kind->who) + "_run_device";
-  soda_hip_program* p = h->prog;
-  const soda_hip_plan_t& plan = p->plan;
-  if (int rc = check_iterate(plan, h->not_iterable, iterate, who.c_str()))
-    return rc;
-  const int nin = plan.num_inputs, nout = plan.num_outputs;
-  // the device entry contract on the caller's dense arrays of N
-  if (int rc = check_contract(plan, outputs, inputs, h->t.n, who.c_str()))
-    return rc;
-  HIP_TRY(hipSetDevice(p->device));
-  hipStream_t stream = static_cast<hipStream_t>(stream_);
-  // pad: every cell of the padded inputs, ghosts included
-  std::vector<void*> pin(nin), pout(nout);
-  std::vector<const void*> src(nin + plan.num_params);
-  std::vector<int32_t> ein(nin), eout(nout);
-  for (int i = 0; i < nin; ++i) {
-    pin[i] = h->pad_in[i].ptr;
-    src[i] = pin[i];
-    ein[i] = plan.elem_size[i];
-  }
-  for (int k = 0; k < plan.num_params; ++k) src[nin + k] = inputs[nin + k];
-  for (int o = 0; o < nout; ++o) {
-    pout[o] = h->pad_out[o].ptr;
-    eout[o] = plan.elem_size[nin + o];
-  }
-  if (int rc = wrap_launch(h, kPad, pin.data(), inputs, ein.data(), nin,
-                           stream))
-    return rc;
-  if (int rc = fused ? fused_chunks(fused, pout.data(), src.data(), iterate,
-                                    stream_)
-                     : run_chunks(h, pout.data(), src.data(), iterate,
-                                  stream_))
-    return rc;
-  return wrap_launch(h, kCrop, outputs,
-                     const_cast<const void* const*>(pout.data()), eout.data(),
-                     nout, stream);
-}
-
-// <handle>_run_padded_residual / _run_padded_norms (`norms` != nullptr):
-// run_padded_core with the struct at `dev` filled (DESIGN.md 4.14).  Every
-// refusal comes before the first launch.
-int run_padded_residual_core(soda_hip_periodic* h,
-                             soda_hip_norms_handle* norms,
-                             void* const* outputs, const void* const* inputs,
-                             int32_t iterate, void* dev, void* stream,
-                             soda_hip_border_fused* fused = nullptr) {
-  const std::string who = std::string(h->kind->who) +
-                          (norms ? "_run_padded_norms" : "_run_padded_residual");
-  soda_hip_program* p = h->prog;
-  for (int o = 0; o < p->plan.num_outputs; ++o)
-    if (!outputs[o]) return fail(SODA_HIP_ERR_INVALID, who + ": NULL output");
-  if (int rc = norms ? check_norms_request(p, norms, outputs, h->t.p, dev,
-                                           who.c_str())
-                     : check_residual_request(p, outputs, h->t.p, dev,
-                                              who.c_str()))
-    return rc;
-  if (int rc = check_iterate(p->plan, h->not_iterable, iterate, who.c_str()))
-    return rc;
-  if (int rc = check_contract(p->plan, outputs, inputs, h->t.p, who.c_str()))
-    return rc;
-  const ResidualRun run = {dev, 0, norms};
-  return any_chunks(h, fused, outputs, inputs, iterate, stream, &run);
-}
-
-// <handle>_run_until / _run_until_norm on DENSE arrays of N: pads once, runs
-// `check_every` iterations at a time on the handle's padded scratch until
-// `converged(&stop)` says so by the struct of the last chunk -- `host_bytes`
-// fetched into `host` -- or `max_iterate` iterations are done, crops.  The
-// first chunk goes from pad_in to pad_out, every later one back into the set
-// the one before it read (an iterable program's pad_in[i] is as large as its
-// pad_out[i]).  Synchronous.
-template <class Converged>
-int run_until_core(soda_hip_periodic* h, soda_hip_norms_handle* norms,
-                   void* const* outputs, const void* const* inputs,
-                   int32_t max_iterate, int32_t check_every, void* host,
-                   size_t host_bytes, Converged converged,
-                   int32_t* iterations_done, void* stream_,
-                   soda_hip_border_fused* fused) {
-  const std::string who = std::string(h->kind->who) +
-                          (norms ? "_run_until_norm" : "_run_until");
-  soda_hip_program* p = h->prog;
-  const soda_hip_plan_t& plan = p->plan;
-  const int nin = plan.num_inputs, nout = plan.num_outputs;
-  if (max_iterate < 1 || check_every < 1)
-    return fail(SODA_HIP_ERR_INVALID,
-                who + ": max_iterate and check_every must be >= 1");
-  for (int o = 0; o < nout; ++o)
-    if (!outputs[o]) return fail(SODA_HIP_ERR_INVALID, who + ": NULL output");
-  if (int rc = norms ? check_norms_request(p, norms, outputs, h->t.n, nullptr,
-                                           who.c_str())
-                     : check_residual_request(p, outputs, h->t.n, nullptr,
-                                              who.c_str()))
-    return rc;
-  if (int rc = check_iterate(plan, h->not_iterable, max_iterate, who.c_str()))
-    return rc;
-  if (int rc = check_contract(plan, outputs, inputs, h->t.n, who.c_str()))
-    return rc;
-  HIP_TRY(hipSetDevice(p->device));
-  hipStream_t stream = static_cast<hipStream_t>(stream_);
-  hipStreamCaptureStatus capture = hipStreamCaptureStatusNone;
-  if (hipStreamIsCapturing(stream, &capture) != hipSuccess) {
-    (void)hipGetLastError();
-    capture = hipStreamCaptureStatusNone;
-  }
-  if (capture != hipStreamCaptureStatusNone)
-    return fail(SODA_HIP_ERR_INVALID,
-                who + ": synchronous, not for a stream that is being captured; "
-                      "nothing was launched");
-  if (int rc = ensure(p->until_struct, host_bytes)) return rc;
-  std::vector<void*> a(nin), b(nout), crop(nout);
-  std::vector<const void*> src(nin + plan.num_params);
-  std::vector<int32_t> ein(nin), eout(nout);
-  for (int i = 0; i < nin; ++i) {
-    a[i] = h->pad_in[i].ptr;
-    src[i] = a[i];
-    ein[i] = plan.elem_size[i];
-  }
-  for (int k = 0; k < plan.num_params; ++k) src[nin + k] = inputs[nin + k];
-  for (int o = 0; o < nout; ++o) {
-    b[o] = h->pad_out[o].ptr;
-    eout[o] = plan.elem_size[nin + o];
-  }
-  if (int rc = wrap_launch(h, kPad, a.data(), inputs, ein.data(), nin, stream))
-    return rc;
-  memset(host, 0, host_bytes);
-  const ResidualRun run = {p->until_struct.ptr, 0, norms};
-  int32_t done = 0;
-  for (int32_t chunk = 0; done < max_iterate; ++chunk) {
-    const int32_t n =
-        max_iterate - done < check_every ? max_iterate - done : check_every;
-    void* const* dst = chunk % 2 ? a.data() : b.data();
-    if (int rc = any_chunks(h, fused, dst, src.data(), n, stream_, &run))
-      return rc;
-    HIP_TRY(hipMemcpyAsync(host, p->until_struct.ptr, host_bytes,
-                           hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
-    done += n;
-    for (int o = 0; o < nout; ++o) crop[o] = dst[o];
-    bool stop = false;
-    if (int rc = converged(&stop)) return rc;
-    if (stop) break;
-    // (another chunk follows: the program iterates, nin == nout)
-    for (int i = 0; i < nin; ++i) src[i] = dst[i];
-  }
-  if (int rc = wrap_launch(h, kCrop, outputs,
-                           const_cast<const void* const*>(crop.data()),
-                           eout.data(), nout, stream))
-    return rc;
-  HIP_TRY(hipStreamSynchronize(stream));
-  if (iterations_done) *iterations_done = done;
-  return SODA_HIP_OK;
-}
-
-int until_residual(soda_hip_periodic* h, void* const* outputs,
-                   const void* const* inputs, int32_t max_iterate,
-                   int32_t check_every, double tol, uint64_t int_tol,
-                   soda_hip_residual_t* result_host, int32_t* iterations_done,
-                   void* stream, soda_hip_border_fused* fused = nullptr) {
-  soda_hip_residual_t host;
-  auto converged = [&](bool* stop) {
-    *stop = residual_converged(host, tol, int_tol);
-    return (int)SODA_HIP_OK;
-  };
-  if (int rc = run_until_core(h, nullptr, outputs, inputs, max_iterate,
-                              check_every, &host, sizeof host, converged,
-                              iterations_done, stream, fused))
-    return rc;
-  if (result_host) *result_host = host;
-  return SODA_HIP_OK;
-}
-
-int until_norm(soda_hip_periodic* h, soda_hip_norms_handle* norms,
-               void* const* outputs, const void* const* inputs,
-               int32_t max_iterate, int32_t check_every, int32_t which,
-               double tol, soda_hip_norms_t* result_host,
-               int32_t* iterations_done, void* stream,
-               soda_hip_border_fused* fused = nullptr) {
-  const std::string who = std::string(h->kind->who) + "_run_until_norm";
-  if (which != SODA_HIP_NORMS_WHICH_L1 && which != SODA_HIP_NORMS_WHICH_L2)
-    return fail(SODA_HIP_ERR_INVALID, who + ": bad `which`");
-  soda_hip_norms_t host;
-  auto converged = [&](bool* stop) {
-    if (!norms_converged(host, which, tol, stop))
-      return fail(SODA_HIP_ERR_RUNTIME,
-                  who + ": the struct fetched is of no kind");
-    return (int)SODA_HIP_OK;
-  };
-  if (int rc = run_until_core(h, norms, outputs, inputs, max_iterate,
-                              check_every, &host, sizeof host, converged,
-                              iterations_done, stream, fused))
-    return rc;
-  if (result_host) *result_host = host;
+  list_chunks(iterate, k, capacity, chunks, count);
   return SODA_HIP_OK;
 }
 
@@ -810,303 +505,10 @@ int border_modes(const soda_hip_plan_t* plan,
   return SODA_HIP_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-int soda_hip_periodic_plan(const soda_hip_plan_t* plan,
-                           const soda_hip_periodic_desc_t* desc,
-                           int32_t iterate, soda_hip_periodic_info_t* info,
-                           int32_t capacity, int32_t* chunks, int32_t* count) {
-  return plan_core(kTorus, plan, desc, iterate, info, capacity, chunks, count);
-}
-
-int soda_hip_periodic_create(soda_hip_program_t* p,
-                             const soda_hip_periodic_desc_t* desc,
-                             const void* const* wrap_code,
-                             const size_t* wrap_code_size,
-                             soda_hip_periodic_t** handle) {
-  if (handle) *handle = nullptr;
-  if (!p || !desc || !wrap_code || !wrap_code_size || !handle)
-    return fail(SODA_HIP_ERR_INVALID, "periodic_create: NULL argument");
-  return create_core(kTorus, p, desc, nullptr, nullptr, wrap_code,
-                     wrap_code_size, handle);
-}
-
-int soda_hip_periodic_destroy(soda_hip_periodic_t* h) {
-  if (!h) return SODA_HIP_OK;
-  (void)hipSetDevice(h->prog->device);
-  for (auto* v : {&h->pad_in, &h->pad_out, &h->pong})
-    for (auto& b : *v)
-      if (b.ptr) (void)hipFree(b.ptr);
-  for (auto& m : h->module)
-    if (m) (void)hipModuleUnload(m);
-  delete h;
-  return SODA_HIP_OK;
-}
-
-int soda_hip_periodic_info(soda_hip_periodic_t* h,
-                           soda_hip_periodic_info_t* info) {
-  if (!h || !info)
-    return fail(SODA_HIP_ERR_INVALID,
-                std::string(h ? h->kind->who : "periodic") +
-                    "_info: NULL argument");
-  memset(info, 0, sizeof *info);
-  info->refill_every = h->k;
-  for (int d = 0; d < 4; ++d) {
-    info->ghost_lo[d] = h->t.glo[d];
-    info->ghost_hi[d] = h->t.ghi[d];
-    info->padded[d] = h->t.p[d];
-  }
-  for (const auto* v : {&h->pad_in, &h->pad_out, &h->pong})
-    for (const auto& b : *v) info->scratch_bytes += (int64_t)b.bytes;
-  return SODA_HIP_OK;
-}
-
-int soda_hip_periodic_fill(soda_hip_periodic_t* h, void* const* arrays,
-                           int32_t count, void* stream) {
-  if (!h || !arrays)
-    return fail(SODA_HIP_ERR_INVALID, "periodic_fill: NULL argument");
-  return fill_core(h, arrays, count, stream);
-}
-
-int soda_hip_periodic_run_padded(soda_hip_periodic_t* h, void* const* outputs,
-                                 const void* const* inputs, int32_t iterate,
-                                 void* stream) {
-  if (!h || !outputs || !inputs)
-    return fail(SODA_HIP_ERR_INVALID, "periodic_run_padded: NULL argument");
-  return run_padded_core(h, outputs, inputs, iterate, stream);
-}
-
-int soda_hip_periodic_run_device(soda_hip_periodic_t* h, void* const* outputs,
-                                 const void* const* inputs, int32_t iterate,
-                                 void* stream) {
-  if (!h || !outputs || !inputs)
-    return fail(SODA_HIP_ERR_INVALID, "periodic_run_device: NULL argument");
-  return run_device_core(h, outputs, inputs, iterate, stream);
-}
-
-// -- bordered domains (DESIGN.md 4.12): the same handle behind its modes ----
-
-int soda_hip_border_plan(const soda_hip_plan_t* plan,
-                         const soda_hip_border_desc_t* desc, int32_t iterate,
-                         soda_hip_periodic_info_t* info, int32_t capacity,
-                         int32_t* chunks, int32_t* count) {
-  if (!plan || !desc)
-    return fail(SODA_HIP_ERR_INVALID, "border_plan: NULL argument");
-  bool all_wrap;
-  if (int rc = border_modes(plan, desc, &all_wrap)) return rc;
-  if (all_wrap)
-    return soda_hip_periodic_plan(plan, &desc->domain, iterate, info, capacity,
-                                  chunks, count);
-  soda_hip_periodic_desc_t domain = desc->domain;
-  if (domain.refill_every == 0) domain.refill_every = 1;
-  return plan_core(kBorder, plan, &domain, iterate, info, capacity, chunks,
-                   count);
-}
-
-int soda_hip_border_create(soda_hip_program_t* p,
-                           const soda_hip_border_desc_t* desc,
-                           const void* const* code, const size_t* code_size,
-                           soda_hip_border_t** handle) {
-  if (handle) *handle = nullptr;
-  if (!p || !desc || !code || !code_size || !handle)
-    return fail(SODA_HIP_ERR_INVALID, "border_create: NULL argument");
-  bool all_wrap;
-  if (int rc = border_modes(&p->plan, desc, &all_wrap)) return rc;
-  soda_hip_periodic_desc_t domain = desc->domain;
-  if (!all_wrap && domain.refill_every == 0) domain.refill_every = 1;
-  return create_core(kBorder, p, &domain, desc->mode, desc->constant, code,
-                     code_size, handle);
-}
-
-int soda_hip_border_destroy(soda_hip_border_t* h) {
-  return soda_hip_periodic_destroy(h);
-}
-
-int soda_hip_border_info(soda_hip_border_t* h,
-                         soda_hip_periodic_info_t* info) {
-  if (!h) return fail(SODA_HIP_ERR_INVALID, "border_info: NULL argument");
-  return soda_hip_periodic_info(h, info);
-}
-
-int soda_hip_border_fill(soda_hip_border_t* h, void* const* arrays,
-                         int32_t count, void* stream) {
-  if (!h || !arrays)
-    return fail(SODA_HIP_ERR_INVALID, "border_fill: NULL argument");
-  return fill_core(h, arrays, count, stream);
-}
-
-int soda_hip_border_run_padded(soda_hip_border_t* h, void* const* outputs,
-                               const void* const* inputs, int32_t iterate,
-                               void* stream) {
-  if (!h || !outputs || !inputs)
-    return fail(SODA_HIP_ERR_INVALID, "border_run_padded: NULL argument");
-  return run_padded_core(h, outputs, inputs, iterate, stream);
-}
-
-int soda_hip_border_run_device(soda_hip_border_t* h, void* const* outputs,
-                               const void* const* inputs, int32_t iterate,
-                               void* stream) {
-  if (!h || !outputs || !inputs)
-    return fail(SODA_HIP_ERR_INVALID, "border_run_device: NULL argument");
-  return run_device_core(h, outputs, inputs, iterate, stream);
-}
-
-// -- residual, norms and run_until on both -----------------
-
-int soda_hip_periodic_run_padded_residual(soda_hip_periodic_t* h,
-                                          void* const* outputs,
-                                          const void* const* inputs,
-                                          int32_t iterate, void* residual_dev,
-                                          void* stream) {
-  if (!h || !outputs || !inputs || !residual_dev)
-    return fail(SODA_HIP_ERR_INVALID,
-                "periodic_run_padded_residual: NULL argument");
-  return run_padded_residual_core(h, nullptr, outputs, inputs, iterate,
-                                  residual_dev, stream);
-}
-
-int soda_hip_periodic_run_padded_norms(soda_hip_periodic_t* h,
-                                       soda_hip_norms_handle_t* norms,
-                                       void* const* outputs,
-                                       const void* const* inputs,
-                                       int32_t iterate, void* acc_dev,
-                                       void* stream) {
-  if (!h || !norms || !outputs || !inputs || !acc_dev)
-    return fail(SODA_HIP_ERR_INVALID,
-                "periodic_run_padded_norms: NULL argument");
-  return run_padded_residual_core(h, norms, outputs, inputs, iterate, acc_dev,
-                                  stream);
-}
-
-int soda_hip_periodic_run_until(soda_hip_periodic_t* h, void* const* outputs,
-                                const void* const* inputs, int32_t max_iterate,
-                                int32_t check_every, double tol,
-                                uint64_t int_tol,
-                                soda_hip_residual_t* result_host,
-                                int32_t* iterations_done, void* stream) {
-  if (!h || !outputs || !inputs)
-    return fail(SODA_HIP_ERR_INVALID, "periodic_run_until: NULL argument");
-  return until_residual(h, outputs, inputs, max_iterate, check_every, tol,
-                        int_tol, result_host, iterations_done, stream);
-}
-
-int soda_hip_periodic_run_until_norm(soda_hip_periodic_t* h,
-                                     soda_hip_norms_handle_t* norms,
-                                     void* const* outputs,
-                                     const void* const* inputs,
-                                     int32_t max_iterate, int32_t check_every,
-                                     int32_t which, double tol,
-                                     soda_hip_norms_t* result_host,
-                                     int32_t* iterations_done, void* stream) {
-  if (!h || !norms || !outputs || !inputs)
-    return fail(SODA_HIP_ERR_INVALID, "periodic_run_until_norm: NULL argument");
-  return until_norm(h, norms, outputs, inputs, max_iterate, check_every, which,
-                    tol, result_host, iterations_done, stream);
-}
-
-int soda_hip_border_run_padded_residual(soda_hip_border_t* h,
-                                        void* const* outputs,
-                                        const void* const* inputs,
-                                        int32_t iterate, void* residual_dev,
-                                        void* stream) {
-  if (!h || !outputs || !inputs || !residual_dev)
-    return fail(SODA_HIP_ERR_INVALID,
-                "border_run_padded_residual: NULL argument");
-  return run_padded_residual_core(h, nullptr, outputs, inputs, iterate,
-                                  residual_dev, stream);
-}
-
-int soda_hip_border_run_padded_norms(soda_hip_border_t* h,
-                                     soda_hip_norms_handle_t* norms,
-                                     void* const* outputs,
-                                     const void* const* inputs,
-                                     int32_t iterate, void* acc_dev,
-                                     void* stream) {
-  if (!h || !norms || !outputs || !inputs || !acc_dev)
-    return fail(SODA_HIP_ERR_INVALID, "border_run_padded_norms: NULL argument");
-  return run_padded_residual_core(h, norms, outputs, inputs, iterate, acc_dev,
-                                  stream);
-}
-
-int soda_hip_border_run_until(soda_hip_border_t* h, void* const* outputs,
-                              const void* const* inputs, int32_t max_iterate,
-                              int32_t check_every, double tol, uint64_t int_tol,
-                              soda_hip_residual_t* result_host,
-                              int32_t* iterations_done, void* stream) {
-  if (!h || !outputs || !inputs)
-    return fail(SODA_HIP_ERR_INVALID, "border_run_until: NULL argument");
-  return until_residual(h, outputs, inputs, max_iterate, check_every, tol,
-                        int_tol, result_host, iterations_done, stream);
-}
-
-int soda_hip_border_run_until_norm(soda_hip_border_t* h,
-                                   soda_hip_norms_handle_t* norms,
-                                   void* const* outputs,
-                                   const void* const* inputs,
-                                   int32_t max_iterate, int32_t check_every,
-                                   int32_t which, double tol,
-                                   soda_hip_norms_t* result_host,
-                                   int32_t* iterations_done, void* stream) {
-  if (!h || !norms || !outputs || !inputs)
-    return fail(SODA_HIP_ERR_INVALID, "border_run_until_norm: NULL argument");
-  return until_norm(h, norms, outputs, inputs, max_iterate, check_every, which,
-                    tol, result_host, iterations_done, stream);
-}
-
-}  // extern "C"
-
-// -- bordered domains, fused away from the walls (DESIGN.md 4.13) -----------
-// A handle on the domain whose chunks run fused on P, and per wall dimension a
-// handle of the same kind on a narrow strip that advances the cells near the
-// two walls one iteration at a time.  The box kernel gathers the strips from
-// the chunk's inputs and scatters their rims into its outputs.
-
-namespace {
-
-const int kBoxBlock = 256;
-const int kBoxMax = 4;
-const int64_t kBoxMaxBlocks = 1 << 15;    // the lanes stride over the items
-
-// the box kernel's one argument, as soda_rt_box.h declares it
-struct BoxArgs {
-  void* dst[16];
-  const void* src[16];
-  int32_t dext[4];
-  int32_t sext[4];
-  int32_t nbox;
-  uint32_t reserved;
-  int32_t dorg[kBoxMax][4];
-  int32_t sorg[kBoxMax][4];
-  int32_t size[kBoxMax][4];
-  uint32_t per_row[kBoxMax];
-  uint64_t start[kBoxMax];
-  uint64_t total;
-};
-
-struct Box {
-  int32_t to[4], from[4], size[4];
-};
-
-}  // namespace
-
-struct soda_hip_border_fused {
-  soda_hip_periodic* main = nullptr;
-  int32_t depth = 1;
-  int nstrips = 0;
-  struct Strip {
-    soda_hip_periodic* h = nullptr;
-    int32_t d = 0, lo = 0, hi = 0, take_lo = 0, take_hi = 0;
-  } strip[SODA_HIP_MAX_DIM];
-  hipModule_t box_module[4] = {nullptr, nullptr, nullptr, nullptr};
-  hipFunction_t box_fn[4] = {nullptr, nullptr, nullptr, nullptr};  // log2(elem)
-  soda_hip_border_fused_boxes_t boxes;   // where a residual counts each cell
-};
-
-namespace {
-
-// soda_hip_border_fused_plan; *all_wrap: the request is a torus
+// soda_hip_border_fused_plan: a handle on the domain whose
+// chunks run fused on P, and per wall dimension a handle of the same kind on
+// a narrow strip that advances the cells near the two walls one iteration at
+// a time.  *all_wrap: the request is a torus.
 int fused_plan_core(const soda_hip_plan_t* plan,
                     const soda_hip_border_fused_desc_t* desc, int32_t iterate,
                     soda_hip_border_fused_info_t* info, int32_t capacity,
@@ -1132,10 +534,7 @@ int fused_plan_core(const soda_hip_plan_t* plan,
     return rc;
   const int dim = plan->dim;
   int32_t depth = desc->depth;
-  if (depth == 0)
-    for (int i = 0; i < plan->num_passes; ++i)
-      if (plan->passes[i].fused_iters > depth)
-        depth = plan->passes[i].fused_iters;
+  if (depth == 0) depth = deepest_pass(*plan);
   if (depth < 1) return fail(SODA_HIP_ERR_INVALID, "border_fused: bad plan");
   const int32_t* rlo = desc->reach_lo;
   const int32_t* rhi = desc->reach_hi;
@@ -1179,10 +578,7 @@ int fused_plan_core(const soda_hip_plan_t* plan,
                            chunks, count))
       return rc;
   } else if (depth > 1) {
-    int32_t c = 0;
-    for (int32_t left = iterate; left > 0; left -= depth, ++c)
-      if (chunks && c < capacity) chunks[c] = left < depth ? left : depth;
-    if (count) *count = c;
+    list_chunks(iterate, depth, capacity, chunks, count);
     for (int d = 0; d < dim; ++d) {
       if (desc->border.mode[d] == SODA_HIP_BORDER_WRAP || rlo[d] + rhi[d] == 0)
         continue;
@@ -1252,74 +648,87 @@ void residual_boxes(const soda_hip_border_fused_info_t& info,
   }
 }
 
-// `nbox` boxes from the arrays src[i] of extent `sext` into dst[i] of `dext`,
-// `count` tensors with cells of elem[i] bytes; one launch per cell size among
-// them.  A box that leaves either extent is refused before anything runs.
-int box_launch(soda_hip_border_fused* f, void* const* dst, const int32_t* dext,
-               const void* const* src, const int32_t* sext,
-               const int32_t* elem, int count, const Box* boxes, int nbox,
-               int dim, hipStream_t stream) {
-  for (int b = 0; b < nbox; ++b)
-    for (int d = 0; d < dim; ++d) {
-      const Box& x = boxes[b];
-      if (x.size[d] < 0 || x.to[d] < 0 || x.from[d] < 0 ||
-          (int64_t)x.to[d] + x.size[d] > dext[d] ||
-          (int64_t)x.from[d] + x.size[d] > sext[d])
-        return fail(SODA_HIP_ERR_INVALID,
-                    "border_fused: a box leaves its array; nothing was "
-                    "launched");
-    }
-  for (int size = 1; size <= 8; size *= 2) {
-    BoxArgs a;
-    memset(&a, 0, sizeof a);
-    int m = 0;
-    for (int i = 0; i < count; ++i)
-      if (elem[i] == size) {
-        a.dst[m] = dst[i];
-        a.src[m] = src[i];
-        ++m;
-      }
-    if (!m) continue;
-    const int v = 16 / size;
-    for (int d = 0; d < 4; ++d) {
-      a.dext[d] = d < dim ? dext[d] : 1;
-      a.sext[d] = d < dim ? sext[d] : 1;
-    }
-    for (int b = 0; b < nbox && a.nbox < kBoxMax; ++b) {
-      int64_t rows = 1;
-      bool empty = false;
-      for (int d = 0; d < dim; ++d) {
-        if (boxes[b].size[d] < 1) empty = true;
-        if (d) rows *= boxes[b].size[d];
-      }
-      if (empty) continue;
-      if (rows > 0x7fffffffLL)
-        return fail(SODA_HIP_ERR_INVALID,
-                    "border_fused: 2^31 rows or more; nothing was launched");
-      const int k = a.nbox++;
-      for (int d = 0; d < 4; ++d) {
-        a.dorg[k][d] = d < dim ? boxes[b].to[d] : 0;
-        a.sorg[k][d] = d < dim ? boxes[b].from[d] : 0;
-        a.size[k][d] = d < dim ? boxes[b].size[d] : 1;
-      }
-      // fragments a row may need: it starts up to v - 1 cells behind a
-      // 16-byte boundary
-      a.per_row[k] = (uint32_t)(((int64_t)boxes[b].size[0] + 2 * v - 2) / v);
-      a.start[k] = a.total;
-      a.total += (uint64_t)rows * a.per_row[k];
-    }
-    if (!a.total) continue;
-    hipFunction_t fn = f->box_fn[log2_elem(size)];
-    if (!fn) return fail(SODA_HIP_ERR_INVALID, "border_fused: no box kernel");
-    int64_t blocks = (int64_t)((a.total + kBoxBlock - 1) / kBoxBlock);
-    if (blocks > kBoxMaxBlocks) blocks = kBoxMaxBlocks;
-    size_t bytes = sizeof a;
-    void* extra[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &a,
-                     HIP_LAUNCH_PARAM_BUFFER_SIZE, &bytes,
-                     HIP_LAUNCH_PARAM_END};
-    HIP_TRY(hipModuleLaunchKernel(fn, (unsigned)blocks, (unsigned)m, 1,
-                                  kBoxBlock, 1, 1, 0, stream, nullptr, extra));
+}  // namespace
+
+// -- the handles --------------------------------------------------------------
+
+struct soda_hip_periodic : Frame {
+  soda_hip_program* prog = nullptr;
+  int32_t k = 1;
+  bool not_iterable = false;
+  std::vector<DeviceBuffer> pad_in;    // dense entry: the padded inputs
+  std::vector<DeviceBuffer> pad_out;   // ... and outputs
+  std::vector<DeviceBuffer> pong;      // the chunks' partner of the outputs
+};
+
+struct soda_hip_border_fused {
+  soda_hip_periodic* main = nullptr;
+  int32_t depth = 1;
+  int nstrips = 0;
+  struct Strip {
+    soda_hip_periodic* h = nullptr;
+    int32_t d = 0, lo = 0, hi = 0, take_lo = 0, take_hi = 0;
+  } strip[SODA_HIP_MAX_DIM];
+  Helpers box;                           // the box kernels
+  soda_hip_border_fused_boxes_t boxes;   // where a residual counts each cell
+};
+
+namespace {
+
+int create_core(const Kind& kind, soda_hip_program_t* p,
+                const soda_hip_periodic_desc_t* desc, const int32_t* mode,
+                const uint64_t* constant, const void* const* code,
+                const size_t* code_size, soda_hip_periodic** handle) {
+  const std::string who(kind.who);
+  const soda_hip_plan_t& plan = p->plan;
+  if (p->bank_tensors)
+    return fail(SODA_HIP_ERR_UNSUPPORTED,
+                who + ": programs on wire-format banks are not served on " +
+                    kind.domain + "; nothing was launched");
+  soda_hip_periodic_info_t info;
+  if (int rc = plan_core(kind, &plan, desc, 0, &info, 0, nullptr, nullptr))
+    return rc;
+  const int nin = plan.num_inputs, nout = plan.num_outputs;
+  bool need[4] = {false, false, false, false};
+  if (int rc = helpers_needed(plan, code, code_size, who, "wrap", need))
+    return rc;
+  HIP_TRY(hipSetDevice(p->device));
+  soda_hip_periodic* h = new (std::nothrow) soda_hip_periodic;
+  if (!h) return fail(SODA_HIP_ERR_NOMEM, "new " + who + " handle");
+  h->prog = p;
+  h->kind = &kind;
+  h->k = info.refill_every;
+  h->not_iterable = desc->not_iterable != 0;
+  const bool iterates = can_iterate(plan, h->not_iterable);
+  h->t.dim = plan.dim;
+  for (int d = 0; d < 4; ++d) {
+    h->t.n[d] = d < plan.dim ? desc->extent[d] : 1;
+    h->t.glo[d] = info.ghost_lo[d];
+    h->t.ghi[d] = info.ghost_hi[d];
+    h->t.p[d] = info.padded[d];
+    if (mode) h->mode[d] = d < plan.dim ? mode[d] : 0;
   }
+  if (constant)
+    for (int i = 0; i < nin; ++i) h->constant[i] = constant[i];
+  int rc = load_helpers(&h->wrap, need, code, kind.kernel, plan.dim, who,
+                        "wrap");
+  const int64_t cells = cells_of(h->t.p, plan.dim);
+  h->pad_in.resize(nin);
+  h->pad_out.resize(nout);
+  h->pong.resize(iterates ? nout : 0);
+  for (int i = 0; i < nin && !rc; ++i)
+    rc = ensure(h->pad_in[i], (size_t)cells * plan.elem_size[i]);
+  for (int o = 0; o < nout && !rc; ++o) {
+    rc = ensure(h->pad_out[o], (size_t)cells * plan.elem_size[nin + o]);
+    if (!rc && iterates)
+      rc = ensure(h->pong[o], (size_t)cells * plan.elem_size[nin + o]);
+  }
+  if (rc) {
+    const std::string why = last_error_text();
+    soda_hip_periodic_destroy(h);
+    return fail(rc, why);
+  }
+  *handle = h;
   return SODA_HIP_OK;
 }
 
@@ -1350,90 +759,55 @@ void strip_boxes(const soda_hip_border_fused* f,
   }
 }
 
-// The chunks of a fused run on padded arrays (run_chunks' contract): per chunk
-// of n <= depth iterations the strips gathered from the chunk's inputs and
-// advanced n times, the interior launched on P, the strips' rims scattered
-// over its result, the frame filled.  One stream, in that order.
-// `res`: the last chunk also takes the residual, each cell where it is made
-// right (DESIGN.md 4.14): the struct zeroed once ahead of the gather, the rims
-// behind every strip's last iteration, the trusted box in the interior's run.
-int fused_chunks(soda_hip_border_fused* f, void* const* outputs,
-                 const void* const* inputs, int32_t iterate, void* stream_,
-                 const ResidualRun* res) {
-  soda_hip_periodic* h = f->main;
-  if (!f->nstrips)
-    return any_chunks(h, nullptr, outputs, inputs, iterate, stream_, res);
-  soda_hip_program* p = h->prog;
-  const soda_hip_plan_t& plan = p->plan;
-  HIP_TRY(hipSetDevice(p->device));
-  hipStream_t stream = static_cast<hipStream_t>(stream_);
-  const int nin = plan.num_inputs, nout = plan.num_outputs, dim = plan.dim;
-  const int chunks = (iterate + f->depth - 1) / f->depth;
+// -- the chunk loop -----------------------------------------------------------
+
+// The same box for every pair: [lo, hi) per dimension of the handle's padded
+// arrays.
+soda_hip_resbox_t resbox_of(const soda_hip_periodic* h, const int32_t* lo,
+                            const int32_t* hi) {
+  soda_hip_resbox_t box;
+  memset(&box, 0, sizeof box);
+  for (int o = 0; o < h->prog->plan.num_outputs; ++o)
+    for (int d = 0; d < SODA_HIP_MAX_DIM; ++d) {
+      box.lo[o][d] = d < h->t.dim ? lo[d] : 0;
+      box.hi[o][d] = d < h->t.dim ? hi[d] : 1;
+    }
+  return box;
+}
+
+// the counted cells of a torus or a depth-1 bordered domain: the interior
+soda_hip_resbox_t interior_box(const soda_hip_periodic* h) {
+  int32_t hi[4];
+  for (int d = 0; d < 4; ++d) hi[d] = h->t.glo[d] + h->t.n[d];
+  return resbox_of(h, h->t.glo, hi);
+}
+
+// The chunks of a run on padded arrays of handle `h`, `k` iterations each and
+// the last one what is left: `inputs` filled in, `outputs` filled out, the
+// chunks alternating between `outputs` and the handle's `pong` so that the
+// last one lands in `outputs`.  `step(dst, src, n, last)` advances one chunk
+// of n iterations from `src` (inputs, then the param arrays) to `dst`; the
+// frame of `dst` is filled behind it.
+template <class Step>
+int chunk_loop(soda_hip_periodic* h, int32_t k, void* const* outputs,
+               const void* const* inputs, int32_t iterate, void* stream,
+               Step step) {
+  const soda_hip_plan_t& plan = h->prog->plan;
+  const int nin = plan.num_inputs, nout = plan.num_outputs;
+  const int chunks = (iterate + k - 1) / k;
   std::vector<const void*> src(inputs, inputs + nin + plan.num_params);
-  std::vector<const void*> ssrc(src);
-  std::vector<void*> dst(nout), sin(nin), sout(nout);
-  std::vector<int32_t> ein(nin), eout(nout);
-  for (int i = 0; i < nin; ++i) ein[i] = plan.elem_size[i];
-  for (int o = 0; o < nout; ++o) eout[o] = plan.elem_size[nin + o];
+  std::vector<void*> dst(nout);
+  std::vector<int32_t> elem(nout);
+  for (int o = 0; o < nout; ++o) elem[o] = plan.elem_size[nin + o];
   int32_t left = iterate;
   for (int c = 0; c < chunks; ++c) {
-    const int32_t n = left < f->depth ? left : f->depth;
+    const int32_t n = chunk_len(left, k);
     const bool to_out = ((chunks - 1 - c) % 2) == 0;
     for (int o = 0; o < nout; ++o)
       dst[o] = to_out ? outputs[o] : h->pong[o].ptr;
-    const bool take = res && c + 1 == chunks;
-    ChunkResidual part;
-    if (take) {
-      if (int rc = residual_zero(p, *res, stream_)) return rc;
-      part.run = *res;
-      part.run.accumulate = true;
-    }
-    for (int k = 0; k < f->nstrips; ++k) {
-      const soda_hip_border_fused::Strip& s = f->strip[k];
-      Box box[2];
-      strip_boxes(f, s, true, &box[0], &box[1]);
-      for (int i = 0; i < nin; ++i) {
-        sin[i] = s.h->pad_in[i].ptr;
-        ssrc[i] = sin[i];
-      }
-      for (int o = 0; o < nout; ++o) sout[o] = s.h->pad_out[o].ptr;
-      if (int rc = box_launch(f, sin.data(), s.h->t.p, src.data(), h->t.p,
-                              ein.data(), nin, box, 2, dim, stream))
-        return rc;
-      if (int rc = wrap_launch(s.h, kFill, sin.data(), ssrc.data(), ein.data(),
-                               nin, stream))
-        return rc;
-      if (take) {
-        const soda_hip_border_rims_t& r = f->boxes.strip[k];
-        part.box[0] = resbox_of(s.h, r.lo[0], r.hi[0]);
-        part.box[1] = resbox_of(s.h, r.lo[1], r.hi[1]);
-        part.nbox = 2;
-        part.behind = true;
-      }
-      if (int rc = run_chunks(s.h, sout.data(), ssrc.data(), n, stream_,
-                              take ? &part : nullptr))
-        return rc;
-    }
-    RunRequest rq = {dst.data(), src.data(), h->t.p, n, stream_};
-    if (take) {
-      part.box[0] = resbox_of(h, f->boxes.trusted_lo, f->boxes.trusted_hi);
-      part.run.box = &part.box[0];
-      rq.residual = &part.run;
-    }
-    if (int rc = run_core(p, rq)) return rc;
-    for (int k = 0; k < f->nstrips; ++k) {
-      const soda_hip_border_fused::Strip& s = f->strip[k];
-      Box box[2];
-      strip_boxes(f, s, false, &box[0], &box[1]);
-      for (int o = 0; o < nout; ++o) sout[o] = s.h->pad_out[o].ptr;
-      if (int rc = box_launch(f, dst.data(), h->t.p,
-                              const_cast<const void* const*>(sout.data()),
-                              s.h->t.p, eout.data(), nout, box, 2, dim,
-                              stream))
-        return rc;
-    }
-    if (int rc = wrap_launch(h, kFill, dst.data(), dst.data(), eout.data(),
-                             nout, stream))
+    if (int rc = step(dst.data(), src.data(), n, c + 1 == chunks)) return rc;
+    if (int rc = wrap_launch(*h, kFill, dst.data(), dst.data(), elem.data(),
+                             nout, static_cast<hipStream_t>(stream)))
       return rc;
     left -= n;
     if (c + 1 < chunks)
@@ -1442,9 +816,542 @@ int fused_chunks(soda_hip_border_fused* f, void* const* outputs,
   return SODA_HIP_OK;
 }
 
+// What the last chunk of run_chunks takes of a residual (DESIGN.md 4.14).
+// `behind` false: box[0] rides in the chunk's run (run_core: a twin, or the
+// generic kernels behind the one-iteration pass).  `behind` true, a strip:
+// every box is counted behind the chunk by the generic kernels, cur the
+// chunk's result, prev what it read.
+struct ChunkResidual {
+  ResidualRun run;
+  soda_hip_resbox_t box[2];
+  int nbox;
+  bool behind;
+};
+
+// The chunks of a torus, a depth-1 bordered domain or a strip: a chunk is one
+// run of the program on the padded extent.
+int run_chunks(soda_hip_periodic* h, void* const* outputs,
+               const void* const* inputs, int32_t iterate, void* stream,
+               const ChunkResidual* res = nullptr) {
+  soda_hip_program* p = h->prog;
+  return chunk_loop(
+      h, h->k, outputs, inputs, iterate, stream,
+      [&](void* const* dst, const void* const* src, int32_t n,
+          bool last) -> int {
+        RunRequest rq = {dst, src, h->t.p, n, stream};
+        ResidualRun riding;
+        if (res && last && !res->behind) {
+          riding = res->run;
+          riding.box = &res->box[0];
+          rq.residual = &riding;
+        }
+        if (int rc = run_core(p, rq)) return rc;
+        if (res && last && res->behind)
+          for (int b = 0; b < res->nbox; ++b)
+            if (int rc = residual_add(p, dst, src, h->t.p, res->run,
+                                      res->box[b], stream))
+              return rc;
+        return SODA_HIP_OK;
+      });
+}
+
+// The chunks of a fused run with strips: per chunk of n <= depth iterations
+// the strips gathered from the chunk's inputs and advanced n times, the
+// interior launched on P, the strips' rims scattered over its result (and the
+// frame filled, by the loop).  One stream, in that order.
+// `res`: the last chunk also takes the residual, each cell where it is made
+// right (DESIGN.md 4.14): the struct zeroed once ahead of the gather, the rims
+// behind every strip's last iteration, the trusted box in the interior's run.
+int fused_chunks(soda_hip_border_fused* f, void* const* outputs,
+                 const void* const* inputs, int32_t iterate, void* stream_,
+                 const ResidualRun* res) {
+  soda_hip_periodic* h = f->main;
+  soda_hip_program* p = h->prog;
+  const soda_hip_plan_t& plan = p->plan;
+  HIP_TRY(hipSetDevice(p->device));
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  const int nin = plan.num_inputs, nout = plan.num_outputs, dim = plan.dim;
+  std::vector<const void*> ssrc(inputs, inputs + nin + plan.num_params);
+  std::vector<void*> sin(nin), sout(nout);
+  std::vector<int32_t> ein(nin), eout(nout);
+  for (int i = 0; i < nin; ++i) ein[i] = plan.elem_size[i];
+  for (int o = 0; o < nout; ++o) eout[o] = plan.elem_size[nin + o];
+  return chunk_loop(
+      h, f->depth, outputs, inputs, iterate, stream_,
+      [&](void* const* dst, const void* const* src, int32_t n,
+          bool last) -> int {
+        const bool take = res && last;
+        ChunkResidual part;
+        if (take) {
+          if (int rc = residual_zero(p, *res, stream_)) return rc;
+          part.run = *res;
+          part.run.accumulate = true;
+        }
+        for (int k = 0; k < f->nstrips; ++k) {
+          const soda_hip_border_fused::Strip& s = f->strip[k];
+          Box box[2];
+          strip_boxes(f, s, true, &box[0], &box[1]);
+          for (int i = 0; i < nin; ++i) {
+            sin[i] = s.h->pad_in[i].ptr;
+            ssrc[i] = sin[i];
+          }
+          for (int o = 0; o < nout; ++o) sout[o] = s.h->pad_out[o].ptr;
+          if (int rc = box_launch(f->box, sin.data(), s.h->t.p, src, h->t.p,
+                                  ein.data(), nin, box, 2, dim, stream))
+            return rc;
+          if (int rc = wrap_launch(*s.h, kFill, sin.data(), ssrc.data(),
+                                   ein.data(), nin, stream))
+            return rc;
+          if (take) {
+            const soda_hip_border_rims_t& r = f->boxes.strip[k];
+            part.box[0] = resbox_of(s.h, r.lo[0], r.hi[0]);
+            part.box[1] = resbox_of(s.h, r.lo[1], r.hi[1]);
+            part.nbox = 2;
+            part.behind = true;
+          }
+          if (int rc = run_chunks(s.h, sout.data(), ssrc.data(), n, stream_,
+                                  take ? &part : nullptr))
+            return rc;
+        }
+        RunRequest rq = {dst, src, h->t.p, n, stream_};
+        if (take) {
+          part.box[0] = resbox_of(h, f->boxes.trusted_lo, f->boxes.trusted_hi);
+          part.run.box = &part.box[0];
+          rq.residual = &part.run;
+        }
+        if (int rc = run_core(p, rq)) return rc;
+        for (int k = 0; k < f->nstrips; ++k) {
+          const soda_hip_border_fused::Strip& s = f->strip[k];
+          Box box[2];
+          strip_boxes(f, s, false, &box[0], &box[1]);
+          for (int o = 0; o < nout; ++o) sout[o] = s.h->pad_out[o].ptr;
+          if (int rc = box_launch(f->box, dst, h->t.p,
+                                  const_cast<const void* const*>(sout.data()),
+                                  s.h->t.p, eout.data(), nout, box, 2, dim,
+                                  stream))
+            return rc;
+        }
+        return SODA_HIP_OK;
+      });
+}
+
+// What a run entry runs on: the handle on the domain -- its frame, its scratch
+// and its name in messages -- and, where its chunks run fused, the handle that
+// has it as `main`.
+struct Domain {
+  soda_hip_periodic* h;
+  soda_hip_border_fused* fused;
+
+  // The chunks of a run on padded arrays; `res`: with the residual of the
+  // last iteration over the whole domain.  A fused handle without strips (a
+  // torus, depth 1) runs the plain chunks of its main handle.
+  int chunks(void* const* outputs, const void* const* inputs, int32_t iterate,
+             void* stream, const ResidualRun* res = nullptr) const {
+    if (fused && fused->nstrips)
+      return fused_chunks(fused, outputs, inputs, iterate, stream, res);
+    if (!res) return run_chunks(h, outputs, inputs, iterate, stream);
+    const ChunkResidual whole = {*res, {interior_box(h), {}}, 1, false};
+    return run_chunks(h, outputs, inputs, iterate, stream, &whole);
+  }
+};
+
+Domain domain_of(soda_hip_periodic* h) { return {h, nullptr}; }
+Domain domain_of(soda_hip_border_fused* f) { return {f->main, f}; }
+
+// -- the run cores ------------------------------------------------------------
+
+// The device entry contract (include/soda_hip.h, soda_hip_run_device) on the
+// caller's arrays, each the dense array of `extent`: no output shares a byte
+// with an input, a param array or another output; inputs and outputs are
+// aligned to min(16, vec x cell size) bytes.
+int check_contract(const soda_hip_plan_t& plan, void* const* outputs,
+                   const void* const* inputs, const int32_t* extent,
+                   const char* who_) {
+  const std::string who(who_);
+  const int nin = plan.num_inputs, nout = plan.num_outputs;
+  const int prm0 = nin + nout + plan.num_locals;
+  for (int i = 0; i < nin + plan.num_params; ++i)
+    if (!inputs[i]) return fail(SODA_HIP_ERR_INVALID, who + ": NULL input");
+  for (int o = 0; o < nout; ++o)
+    if (!outputs[o]) return fail(SODA_HIP_ERR_INVALID, who + ": NULL output");
+  const uint64_t cells = (uint64_t)cells_of(extent, plan.dim);
+  auto overlap = [](const void* a, uint64_t na, const void* b, uint64_t nb) {
+    const uintptr_t a0 = reinterpret_cast<uintptr_t>(a);
+    const uintptr_t b0 = reinterpret_cast<uintptr_t>(b);
+    return a0 < b0 + nb && b0 < a0 + na;
+  };
+  for (int o = 0; o < nout; ++o) {
+    const uint64_t no = cells * plan.elem_size[nin + o];
+    for (int i = 0; i < nin; ++i)
+      if (overlap(outputs[o], no, inputs[i], cells * plan.elem_size[i]))
+        return fail(SODA_HIP_ERR_INVALID,
+                    who + ": an output overlaps an input; nothing was "
+                          "launched");
+    for (int k = 0; k < plan.num_params; ++k)
+      if (overlap(outputs[o], no, inputs[nin + k],
+                  (uint64_t)plan.param_elems[k] * plan.elem_size[prm0 + k]))
+        return fail(SODA_HIP_ERR_INVALID,
+                    who + ": an output overlaps a param array; nothing was "
+                          "launched");
+    for (int q = 0; q < o; ++q)
+      if (overlap(outputs[o], no, outputs[q],
+                  cells * plan.elem_size[nin + q]))
+        return fail(SODA_HIP_ERR_INVALID,
+                    who + ": two outputs overlap; nothing was launched");
+  }
+  const int32_t vec = plan_vec(plan);
+  for (int t = 0; t < nin + nout; ++t) {
+    const void* ptr = t < nin ? inputs[t] : outputs[t - nin];
+    int64_t align = (int64_t)vec * plan.elem_size[t];
+    if (align > 16) align = 16;
+    if (reinterpret_cast<uintptr_t>(ptr) % (uintptr_t)align) {
+      char buf[200];
+      snprintf(buf, sizeof buf,
+               ": %s %d at %p is not aligned to %d bytes; nothing was "
+               "launched", t < nin ? "input" : "output",
+               t < nin ? t : t - nin, ptr, (int)align);
+      return fail(SODA_HIP_ERR_INVALID, who + buf);
+    }
+  }
+  return SODA_HIP_OK;
+}
+
+int fill_core(soda_hip_periodic* h, void* const* arrays, int32_t count,
+              void* stream) {
+  const std::string who(h->kind->who);
+  const soda_hip_plan_t& plan = h->prog->plan;
+  if (count < 0 || count > plan.num_outputs)
+    return fail(SODA_HIP_ERR_INVALID,
+                who + "_fill: one array per output at most; nothing was "
+                      "launched");
+  int32_t elem[SODA_HIP_MAX_TENSORS];
+  for (int i = 0; i < count; ++i) {
+    elem[i] = plan.elem_size[plan.num_inputs + i];
+    if (!arrays[i] || reinterpret_cast<uintptr_t>(arrays[i]) % elem[i])
+      return fail(SODA_HIP_ERR_INVALID,
+                  who + "_fill: an array is NULL or not aligned to its cell "
+                        "size; nothing was launched");
+  }
+  HIP_TRY(hipSetDevice(h->prog->device));
+  return wrap_launch(*h, kFill, arrays,
+                     const_cast<const void* const*>(arrays), elem, count,
+                     static_cast<hipStream_t>(stream));
+}
+
+int run_padded_core(const Domain& dom, void* const* outputs,
+                    const void* const* inputs, int32_t iterate,
+                    void* stream) {
+  soda_hip_periodic* h = dom.h;
+  const std::string who = std::string(h->kind->who) + "_run_padded";
+  if (int rc = check_iterate(h->prog->plan, h->not_iterable, iterate,
+                             who.c_str()))
+    return rc;
+  if (int rc = check_contract(h->prog->plan, outputs, inputs, h->t.p,
+                              who.c_str()))
+    return rc;
+  return dom.chunks(outputs, inputs, iterate, stream);
+}
+
+// The dense entries' staging in the handle's padded scratch: `in` / `out` its
+// padded inputs / outputs, `src` what a run from `in` reads (then the
+// caller's param arrays).
+struct Staging {
+  soda_hip_periodic* h;
+  const void* const* inputs;
+  std::vector<void*> in, out;
+  std::vector<const void*> src;
+  std::vector<int32_t> ein, eout;
+
+  Staging(soda_hip_periodic* h_, const void* const* inputs_)
+      : h(h_), inputs(inputs_) {
+    const soda_hip_plan_t& plan = h->prog->plan;
+    const int nin = plan.num_inputs, nout = plan.num_outputs;
+    in.resize(nin);
+    ein.resize(nin);
+    out.resize(nout);
+    eout.resize(nout);
+    src.assign(inputs, inputs + nin + plan.num_params);
+    for (int i = 0; i < nin; ++i) {
+      in[i] = h->pad_in[i].ptr;
+      src[i] = in[i];
+      ein[i] = plan.elem_size[i];
+    }
+    for (int o = 0; o < nout; ++o) {
+      out[o] = h->pad_out[o].ptr;
+      eout[o] = plan.elem_size[nin + o];
+    }
+  }
+
+  // pad: every cell of the padded inputs, ghosts included
+  int pad(hipStream_t stream) {
+    return wrap_launch(*h, kPad, in.data(), inputs, ein.data(),
+                       (int)in.size(), stream);
+  }
+
+  // crop: the caller's dense outputs from the padded arrays `from`
+  int crop(void* const* outputs, void* const* from, hipStream_t stream) {
+    return wrap_launch(*h, kCrop, outputs,
+                       const_cast<const void* const*>(from), eout.data(),
+                       (int)out.size(), stream);
+  }
+};
+
+int run_device_core(const Domain& dom, void* const* outputs,
+                    const void* const* inputs, int32_t iterate,
+                    void* stream_) {
+  soda_hip_periodic* h = dom.h;
+  const std::string who = std::string(h->kind->who) + "_run_device";
+  const soda_hip_plan_t& plan = h->prog->plan;
+  if (int rc = check_iterate(plan, h->not_iterable, iterate, who.c_str()))
+    return rc;
+  // the device entry contract on the caller's dense arrays of N
+  if (int rc = check_contract(plan, outputs, inputs, h->t.n, who.c_str()))
+    return rc;
+  HIP_TRY(hipSetDevice(h->prog->device));
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  Staging st(h, inputs);
+  if (int rc = st.pad(stream)) return rc;
+  if (int rc = dom.chunks(st.out.data(), st.src.data(), iterate, stream_))
+    return rc;
+  return st.crop(outputs, st.out.data(), stream);
+}
+
+// <handle>_run_padded_residual / _run_padded_norms (`norms` != nullptr):
+// run_padded_core with the struct at `dev` filled (DESIGN.md 4.14).  Every
+// refusal comes before the first launch.
+int run_padded_residual_core(const Domain& dom, soda_hip_norms_handle* norms,
+                             void* const* outputs, const void* const* inputs,
+                             int32_t iterate, void* dev, void* stream) {
+  soda_hip_periodic* h = dom.h;
+  const std::string who = std::string(h->kind->who) +
+                          (norms ? "_run_padded_norms" : "_run_padded_residual");
+  soda_hip_program* p = h->prog;
+  for (int o = 0; o < p->plan.num_outputs; ++o)
+    if (!outputs[o]) return fail(SODA_HIP_ERR_INVALID, who + ": NULL output");
+  if (int rc = norms ? check_norms_request(p, norms, outputs, h->t.p, dev,
+                                           who.c_str())
+                     : check_residual_request(p, outputs, h->t.p, dev,
+                                              who.c_str()))
+    return rc;
+  if (int rc = check_iterate(p->plan, h->not_iterable, iterate, who.c_str()))
+    return rc;
+  if (int rc = check_contract(p->plan, outputs, inputs, h->t.p, who.c_str()))
+    return rc;
+  const ResidualRun run = {dev, 0, norms};
+  return dom.chunks(outputs, inputs, iterate, stream, &run);
+}
+
+// <handle>_run_until / _run_until_norm on DENSE arrays of N: pads once, runs
+// `check_every` iterations at a time on the handle's padded scratch until
+// `converged(&stop)` says so by the struct of the last chunk -- `host_bytes`
+// fetched into `host` -- or `max_iterate` iterations are done, crops.  The
+// first chunk goes from pad_in to pad_out, every later one back into the set
+// the one before it read (an iterable program's pad_in[i] is as large as its
+// pad_out[i]).  Synchronous.
+template <class Converged>
+int run_until_core(const Domain& dom, soda_hip_norms_handle* norms,
+                   void* const* outputs, const void* const* inputs,
+                   int32_t max_iterate, int32_t check_every, void* host,
+                   size_t host_bytes, Converged converged,
+                   int32_t* iterations_done, void* stream_) {
+  soda_hip_periodic* h = dom.h;
+  const std::string who = std::string(h->kind->who) +
+                          (norms ? "_run_until_norm" : "_run_until");
+  soda_hip_program* p = h->prog;
+  const soda_hip_plan_t& plan = p->plan;
+  const int nin = plan.num_inputs, nout = plan.num_outputs;
+  if (max_iterate < 1 || check_every < 1)
+    return fail(SODA_HIP_ERR_INVALID,
+                who + ": max_iterate and check_every must be >= 1");
+  for (int o = 0; o < nout; ++o)
+    if (!outputs[o]) return fail(SODA_HIP_ERR_INVALID, who + ": NULL output");
+  if (int rc = norms ? check_norms_request(p, norms, outputs, h->t.n, nullptr,
+                                           who.c_str())
+                     : check_residual_request(p, outputs, h->t.n, nullptr,
+                                              who.c_str()))
+    return rc;
+  if (int rc = check_iterate(plan, h->not_iterable, max_iterate, who.c_str()))
+    return rc;
+  if (int rc = check_contract(plan, outputs, inputs, h->t.n, who.c_str()))
+    return rc;
+  HIP_TRY(hipSetDevice(p->device));
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  hipStreamCaptureStatus capture = hipStreamCaptureStatusNone;
+  if (hipStreamIsCapturing(stream, &capture) != hipSuccess) {
+    (void)hipGetLastError();
+    capture = hipStreamCaptureStatusNone;
+  }
+  if (capture != hipStreamCaptureStatusNone)
+    return fail(SODA_HIP_ERR_INVALID,
+                who + ": synchronous, not for a stream that is being captured; "
+                      "nothing was launched");
+  if (int rc = ensure(p->until_struct, host_bytes)) return rc;
+  Staging st(h, inputs);
+  if (int rc = st.pad(stream)) return rc;
+  memset(host, 0, host_bytes);
+  const ResidualRun run = {p->until_struct.ptr, 0, norms};
+  void* const* dst = st.out.data();
+  int32_t done = 0;
+  for (int32_t chunk = 0; done < max_iterate; ++chunk) {
+    const int32_t n = chunk_len(max_iterate - done, check_every);
+    dst = chunk % 2 ? st.in.data() : st.out.data();
+    if (int rc = dom.chunks(dst, st.src.data(), n, stream_, &run)) return rc;
+    HIP_TRY(hipMemcpyAsync(host, p->until_struct.ptr, host_bytes,
+                           hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    done += n;
+    bool stop = false;
+    if (int rc = converged(&stop)) return rc;
+    if (stop) break;
+    // (another chunk follows: the program iterates, nin == nout)
+    for (int i = 0; i < nin; ++i) st.src[i] = dst[i];
+  }
+  if (int rc = st.crop(outputs, dst, stream)) return rc;
+  HIP_TRY(hipStreamSynchronize(stream));
+  if (iterations_done) *iterations_done = done;
+  return SODA_HIP_OK;
+}
+
+int until_residual(const Domain& dom, void* const* outputs,
+                   const void* const* inputs, int32_t max_iterate,
+                   int32_t check_every, double tol, uint64_t int_tol,
+                   soda_hip_residual_t* result_host, int32_t* iterations_done,
+                   void* stream) {
+  soda_hip_residual_t host;
+  auto converged = [&](bool* stop) {
+    *stop = residual_converged(host, tol, int_tol);
+    return (int)SODA_HIP_OK;
+  };
+  if (int rc = run_until_core(dom, nullptr, outputs, inputs, max_iterate,
+                              check_every, &host, sizeof host, converged,
+                              iterations_done, stream))
+    return rc;
+  if (result_host) *result_host = host;
+  return SODA_HIP_OK;
+}
+
+int until_norm(const Domain& dom, soda_hip_norms_handle* norms,
+               void* const* outputs, const void* const* inputs,
+               int32_t max_iterate, int32_t check_every, int32_t which,
+               double tol, soda_hip_norms_t* result_host,
+               int32_t* iterations_done, void* stream) {
+  const std::string who = std::string(dom.h->kind->who) + "_run_until_norm";
+  if (which != SODA_HIP_NORMS_WHICH_L1 && which != SODA_HIP_NORMS_WHICH_L2)
+    return fail(SODA_HIP_ERR_INVALID, who + ": bad `which`");
+  soda_hip_norms_t host;
+  auto converged = [&](bool* stop) {
+    if (!norms_converged(host, which, tol, stop))
+      return fail(SODA_HIP_ERR_RUNTIME,
+                  who + ": the struct fetched is of no kind");
+    return (int)SODA_HIP_OK;
+  };
+  if (int rc = run_until_core(dom, norms, outputs, inputs, max_iterate,
+                              check_every, &host, sizeof host, converged,
+                              iterations_done, stream))
+    return rc;
+  if (result_host) *result_host = host;
+  return SODA_HIP_OK;
+}
+
 }  // namespace
 
+// -- the exported entries -----------------------------------------------------
+
 extern "C" {
+
+int soda_hip_periodic_plan(const soda_hip_plan_t* plan,
+                           const soda_hip_periodic_desc_t* desc,
+                           int32_t iterate, soda_hip_periodic_info_t* info,
+                           int32_t capacity, int32_t* chunks, int32_t* count) {
+  return plan_core(kTorus, plan, desc, iterate, info, capacity, chunks, count);
+}
+
+int soda_hip_periodic_create(soda_hip_program_t* p,
+                             const soda_hip_periodic_desc_t* desc,
+                             const void* const* wrap_code,
+                             const size_t* wrap_code_size,
+                             soda_hip_periodic_t** handle) {
+  if (handle) *handle = nullptr;
+  if (!p || !desc || !wrap_code || !wrap_code_size || !handle)
+    return fail(SODA_HIP_ERR_INVALID, "periodic_create: NULL argument");
+  return create_core(kTorus, p, desc, nullptr, nullptr, wrap_code,
+                     wrap_code_size, handle);
+}
+
+int soda_hip_periodic_destroy(soda_hip_periodic_t* h) {
+  if (!h) return SODA_HIP_OK;
+  (void)hipSetDevice(h->prog->device);
+  for (auto* v : {&h->pad_in, &h->pad_out, &h->pong})
+    for (auto& b : *v)
+      if (b.ptr) (void)hipFree(b.ptr);
+  unload_helpers(&h->wrap);
+  delete h;
+  return SODA_HIP_OK;
+}
+
+int soda_hip_periodic_info(soda_hip_periodic_t* h,
+                           soda_hip_periodic_info_t* info) {
+  if (!h || !info)
+    return fail(SODA_HIP_ERR_INVALID,
+                std::string(h ? h->kind->who : "periodic") +
+                    "_info: NULL argument");
+  memset(info, 0, sizeof *info);
+  info->refill_every = h->k;
+  for (int d = 0; d < 4; ++d) {
+    info->ghost_lo[d] = h->t.glo[d];
+    info->ghost_hi[d] = h->t.ghi[d];
+    info->padded[d] = h->t.p[d];
+  }
+  for (const auto* v : {&h->pad_in, &h->pad_out, &h->pong})
+    for (const auto& b : *v) info->scratch_bytes += (int64_t)b.bytes;
+  return SODA_HIP_OK;
+}
+
+// -- bordered domains (DESIGN.md 4.12): the same handle behind its modes ----
+
+int soda_hip_border_plan(const soda_hip_plan_t* plan,
+                         const soda_hip_border_desc_t* desc, int32_t iterate,
+                         soda_hip_periodic_info_t* info, int32_t capacity,
+                         int32_t* chunks, int32_t* count) {
+  if (!plan || !desc)
+    return fail(SODA_HIP_ERR_INVALID, "border_plan: NULL argument");
+  bool all_wrap;
+  if (int rc = border_modes(plan, desc, &all_wrap)) return rc;
+  if (all_wrap)
+    return soda_hip_periodic_plan(plan, &desc->domain, iterate, info, capacity,
+                                  chunks, count);
+  soda_hip_periodic_desc_t domain = desc->domain;
+  if (domain.refill_every == 0) domain.refill_every = 1;
+  return plan_core(kBorder, plan, &domain, iterate, info, capacity, chunks,
+                   count);
+}
+
+int soda_hip_border_create(soda_hip_program_t* p,
+                           const soda_hip_border_desc_t* desc,
+                           const void* const* code, const size_t* code_size,
+                           soda_hip_border_t** handle) {
+  if (handle) *handle = nullptr;
+  if (!p || !desc || !code || !code_size || !handle)
+    return fail(SODA_HIP_ERR_INVALID, "border_create: NULL argument");
+  bool all_wrap;
+  if (int rc = border_modes(&p->plan, desc, &all_wrap)) return rc;
+  soda_hip_periodic_desc_t domain = desc->domain;
+  if (!all_wrap && domain.refill_every == 0) domain.refill_every = 1;
+  return create_core(kBorder, p, &domain, desc->mode, desc->constant, code,
+                     code_size, handle);
+}
+
+int soda_hip_border_destroy(soda_hip_border_t* h) {
+  return soda_hip_periodic_destroy(h);
+}
+
+int soda_hip_border_info(soda_hip_border_t* h,
+                         soda_hip_periodic_info_t* info) {
+  if (!h) return fail(SODA_HIP_ERR_INVALID, "border_info: NULL argument");
+  return soda_hip_periodic_info(h, info);
+}
+
+// -- bordered domains, fused away from the walls (DESIGN.md 4.13) -----------
 
 int soda_hip_border_fused_plan(const soda_hip_plan_t* plan,
                                const soda_hip_border_fused_desc_t* desc,
@@ -1474,19 +1381,11 @@ int soda_hip_border_fused_create(soda_hip_program_t* p,
   if (int rc = fused_plan_core(&plan, desc, 0, &info, 0, nullptr, nullptr,
                                &all_wrap))
     return rc;
-  bool need[4] = {false, false, false, false};
-  for (int s = 0; info.num_strips && s < plan.num_inputs + plan.num_outputs;
-       ++s) {
-    const int l = log2_elem(plan.elem_size[s]);
-    if (l < 0)
-      return fail(SODA_HIP_ERR_UNSUPPORTED,
-                  "border_fused: cells of 1, 2, 4 or 8 bytes only");
-    if (!box_code[l] || !box_code_size[l])
-      return fail(SODA_HIP_ERR_INVALID,
-                  "border_fused_create: the box module of a cell size of the "
-                  "program is missing");
-    need[l] = true;
-  }
+  bool need[4] = {false, false, false, false};   // box kernels: with strips
+  if (info.num_strips)
+    if (int rc = helpers_needed(plan, box_code, box_code_size, "border_fused",
+                                "box", need))
+      return rc;
   soda_hip_border_fused* f = new (std::nothrow) soda_hip_border_fused;
   if (!f) return fail(SODA_HIP_ERR_NOMEM, "new border_fused handle");
   f->depth = info.depth;
@@ -1509,21 +1408,9 @@ int soda_hip_border_fused_create(soda_hip_program_t* p,
     mine.take_hi = s.take_hi;
     f->nstrips = i + 1;
   }
-  for (int l = 0; l < 4 && !rc; ++l) {
-    if (!need[l]) continue;
-    hipError_t e = hipModuleLoadData(&f->box_module[l], box_code[l]);
-    if (e != hipSuccess) {
-      rc = hip_fail(e, "border_fused_create: hipModuleLoadData");
-      break;
-    }
-    char name[64];
-    snprintf(name, sizeof name, "soda_box_e%d_d%d", 1 << l, plan.dim);
-    e = hipModuleGetFunction(&f->box_fn[l], f->box_module[l], name);
-    if (e != hipSuccess)
-      rc = hip_fail(e, "border_fused_create: hipModuleGetFunction (is this "
-                       "the box module of the cell size and dimension "
-                       "count?)");
-  }
+  if (!rc)
+    rc = load_helpers(&f->box, need, box_code, "soda_box", plan.dim,
+                      "border_fused", "box");
   if (rc) {
     const std::string why = last_error_text();
     soda_hip_border_fused_destroy(f);
@@ -1538,8 +1425,7 @@ int soda_hip_border_fused_destroy(soda_hip_border_fused_t* f) {
   if (!f) return SODA_HIP_OK;
   for (auto& s : f->strip) soda_hip_periodic_destroy(s.h);
   if (f->main) (void)hipSetDevice(f->main->prog->device);
-  for (auto& m : f->box_module)
-    if (m) (void)hipModuleUnload(m);
+  unload_helpers(&f->box);
   soda_hip_periodic_destroy(f->main);
   delete f;
   return SODA_HIP_OK;
@@ -1597,31 +1483,11 @@ int soda_hip_border_fused_move(soda_hip_border_fused_t* f, int32_t strip,
   strip_boxes(f, s, gather != 0, &box[0], &box[1]);
   void* const* dst = gather ? strip_arrays : main_arrays;
   void* const* src = gather ? main_arrays : strip_arrays;
-  return box_launch(f, dst, gather ? s.h->t.p : f->main->t.p,
+  return box_launch(f->box, dst, gather ? s.h->t.p : f->main->t.p,
                     const_cast<const void* const*>(src),
                     gather ? f->main->t.p : s.h->t.p, elem, count, box, 2,
                     plan.dim, static_cast<hipStream_t>(stream));
 }
-
-int soda_hip_border_fused_run_padded(soda_hip_border_fused_t* f,
-                                     void* const* outputs,
-                                     const void* const* inputs,
-                                     int32_t iterate, void* stream) {
-  if (!f || !outputs || !inputs)
-    return fail(SODA_HIP_ERR_INVALID, "border_fused_run_padded: NULL argument");
-  return run_padded_core(f->main, outputs, inputs, iterate, stream, f);
-}
-
-int soda_hip_border_fused_run_device(soda_hip_border_fused_t* f,
-                                     void* const* outputs,
-                                     const void* const* inputs,
-                                     int32_t iterate, void* stream) {
-  if (!f || !outputs || !inputs)
-    return fail(SODA_HIP_ERR_INVALID, "border_fused_run_device: NULL argument");
-  return run_device_core(f->main, outputs, inputs, iterate, stream, f);
-}
-
-// -- residual, norms and run_until --------------------------
 
 int soda_hip_border_fused_residual_boxes(
     const soda_hip_plan_t* plan, const soda_hip_border_fused_desc_t* desc,
@@ -1638,60 +1504,88 @@ int soda_hip_border_fused_residual_boxes(
   return SODA_HIP_OK;
 }
 
-int soda_hip_border_fused_run_padded_residual(soda_hip_border_fused_t* f,
-                                              void* const* outputs,
-                                              const void* const* inputs,
-                                              int32_t iterate,
-                                              void* residual_dev,
-                                              void* stream) {
-  if (!f || !outputs || !inputs || !residual_dev)
-    return fail(SODA_HIP_ERR_INVALID,
-                "border_fused_run_padded_residual: NULL argument");
-  return run_padded_residual_core(f->main, nullptr, outputs, inputs, iterate,
-                                  residual_dev, stream, f);
-}
+// -- the entries every kind of handle has -----------
+// soda_hip_<KIND>_fill, and the six run entries of soda_hip_<KIND>_t: each its
+// NULL arguments refused under its own name, then the core on the handle's
+// Domain.
 
-int soda_hip_border_fused_run_padded_norms(soda_hip_border_fused_t* f,
-                                           soda_hip_norms_handle_t* norms,
-                                           void* const* outputs,
-                                           const void* const* inputs,
-                                           int32_t iterate, void* acc_dev,
-                                           void* stream) {
-  if (!f || !norms || !outputs || !inputs || !acc_dev)
-    return fail(SODA_HIP_ERR_INVALID,
-                "border_fused_run_padded_norms: NULL argument");
-  return run_padded_residual_core(f->main, norms, outputs, inputs, iterate,
-                                  acc_dev, stream, f);
-}
+#define SODA_DOMAIN_FILL_ENTRY(KIND)                                          \
+  int soda_hip_##KIND##_fill(soda_hip_##KIND##_t* h, void* const* arrays,     \
+                             int32_t count, void* stream) {                   \
+    if (!h || !arrays)                                                        \
+      return fail(SODA_HIP_ERR_INVALID, #KIND "_fill: NULL argument");        \
+    return fill_core(h, arrays, count, stream);                               \
+  }
 
-int soda_hip_border_fused_run_until(soda_hip_border_fused_t* f,
-                                    void* const* outputs,
-                                    const void* const* inputs,
-                                    int32_t max_iterate, int32_t check_every,
-                                    double tol, uint64_t int_tol,
-                                    soda_hip_residual_t* result_host,
-                                    int32_t* iterations_done, void* stream) {
-  if (!f || !outputs || !inputs)
-    return fail(SODA_HIP_ERR_INVALID, "border_fused_run_until: NULL argument");
-  return until_residual(f->main, outputs, inputs, max_iterate, check_every,
-                        tol, int_tol, result_host, iterations_done, stream, f);
-}
+#define SODA_DOMAIN_RUN_ENTRIES(KIND)                                         \
+  int soda_hip_##KIND##_run_padded(soda_hip_##KIND##_t* h,                    \
+                                   void* const* outputs,                      \
+                                   const void* const* inputs,                 \
+                                   int32_t iterate, void* stream) {           \
+    if (!h || !outputs || !inputs)                                            \
+      return fail(SODA_HIP_ERR_INVALID, #KIND "_run_padded: NULL argument");  \
+    return run_padded_core(domain_of(h), outputs, inputs, iterate, stream);   \
+  }                                                                           \
+  int soda_hip_##KIND##_run_device(soda_hip_##KIND##_t* h,                    \
+                                   void* const* outputs,                      \
+                                   const void* const* inputs,                 \
+                                   int32_t iterate, void* stream) {           \
+    if (!h || !outputs || !inputs)                                            \
+      return fail(SODA_HIP_ERR_INVALID, #KIND "_run_device: NULL argument");  \
+    return run_device_core(domain_of(h), outputs, inputs, iterate, stream);   \
+  }                                                                           \
+  int soda_hip_##KIND##_run_padded_residual(                                  \
+      soda_hip_##KIND##_t* h, void* const* outputs,                           \
+      const void* const* inputs, int32_t iterate, void* residual_dev,         \
+      void* stream) {                                                         \
+    if (!h || !outputs || !inputs || !residual_dev)                           \
+      return fail(SODA_HIP_ERR_INVALID,                                       \
+                  #KIND "_run_padded_residual: NULL argument");               \
+    return run_padded_residual_core(domain_of(h), nullptr, outputs, inputs,   \
+                                    iterate, residual_dev, stream);           \
+  }                                                                           \
+  int soda_hip_##KIND##_run_padded_norms(                                     \
+      soda_hip_##KIND##_t* h, soda_hip_norms_handle_t* norms,                 \
+      void* const* outputs, const void* const* inputs, int32_t iterate,       \
+      void* acc_dev, void* stream) {                                          \
+    if (!h || !norms || !outputs || !inputs || !acc_dev)                      \
+      return fail(SODA_HIP_ERR_INVALID,                                       \
+                  #KIND "_run_padded_norms: NULL argument");                  \
+    return run_padded_residual_core(domain_of(h), norms, outputs, inputs,     \
+                                    iterate, acc_dev, stream);                \
+  }                                                                           \
+  int soda_hip_##KIND##_run_until(                                            \
+      soda_hip_##KIND##_t* h, void* const* outputs,                           \
+      const void* const* inputs, int32_t max_iterate, int32_t check_every,    \
+      double tol, uint64_t int_tol, soda_hip_residual_t* result_host,         \
+      int32_t* iterations_done, void* stream) {                               \
+    if (!h || !outputs || !inputs)                                            \
+      return fail(SODA_HIP_ERR_INVALID, #KIND "_run_until: NULL argument");   \
+    return until_residual(domain_of(h), outputs, inputs, max_iterate,         \
+                          check_every, tol, int_tol, result_host,             \
+                          iterations_done, stream);                           \
+  }                                                                           \
+  int soda_hip_##KIND##_run_until_norm(                                       \
+      soda_hip_##KIND##_t* h, soda_hip_norms_handle_t* norms,                 \
+      void* const* outputs, const void* const* inputs, int32_t max_iterate,   \
+      int32_t check_every, int32_t which, double tol,                         \
+      soda_hip_norms_t* result_host, int32_t* iterations_done,                \
+      void* stream) {                                                         \
+    if (!h || !norms || !outputs || !inputs)                                  \
+      return fail(SODA_HIP_ERR_INVALID,                                       \
+                  #KIND "_run_until_norm: NULL argument");                    \
+    return until_norm(domain_of(h), norms, outputs, inputs, max_iterate,      \
+                      check_every, which, tol, result_host, iterations_done,  \
+                      stream);                                                \
+  }
 
-int soda_hip_border_fused_run_until_norm(soda_hip_border_fused_t* f,
-                                         soda_hip_norms_handle_t* norms,
-                                         void* const* outputs,
-                                         const void* const* inputs,
-                                         int32_t max_iterate,
-                                         int32_t check_every, int32_t which,
-                                         double tol,
-                                         soda_hip_norms_t* result_host,
-                                         int32_t* iterations_done,
-                                         void* stream) {
-  if (!f || !norms || !outputs || !inputs)
-    return fail(SODA_HIP_ERR_INVALID,
-                "border_fused_run_until_norm: NULL argument");
-  return until_norm(f->main, norms, outputs, inputs, max_iterate, check_every,
-                    which, tol, result_host, iterations_done, stream, f);
-}
+SODA_DOMAIN_FILL_ENTRY(periodic)
+SODA_DOMAIN_FILL_ENTRY(border)
+SODA_DOMAIN_RUN_ENTRIES(periodic)
+SODA_DOMAIN_RUN_ENTRIES(border)
+SODA_DOMAIN_RUN_ENTRIES(border_fused)
+
+#undef SODA_DOMAIN_FILL_ENTRY
+#undef SODA_DOMAIN_RUN_ENTRIES
 
 }  // extern "C"

@@ -412,12 +412,9 @@ API = {
         _vp, ctypes.POINTER(PeriodicDesc), _pvp,
         ctypes.POINTER(ctypes.c_size_t), _pvp
     ]),
-    'soda_hip_periodic_destroy': (ctypes.c_int, [_vp]),
     'soda_hip_periodic_info': (ctypes.c_int, [_vp,
                                               ctypes.POINTER(PeriodicInfo)]),
     'soda_hip_periodic_fill': (ctypes.c_int, [_vp, _pvp, _i32, _vp]),
-    'soda_hip_periodic_run_padded': (ctypes.c_int, [_vp, _pvp, _pvp, _i32,
-                                                    _vp]),
     'soda_hip_extend_host': (ctypes.c_int, [_vp, _i32, _i32, _pi32, _pi32,
                                             _pi32, _pi32, ctypes.c_uint64]),
     'soda_hip_border_plan': (ctypes.c_int, [
@@ -428,14 +425,9 @@ API = {
         _vp, ctypes.POINTER(BorderDesc), _pvp,
         ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(_vp)
     ]),
-    'soda_hip_border_destroy': (ctypes.c_int, [_vp]),
     'soda_hip_border_info': (ctypes.c_int, [_vp,
                                             ctypes.POINTER(PeriodicInfo)]),
     'soda_hip_border_fill': (ctypes.c_int, [_vp, _pvp, _i32, _vp]),
-    'soda_hip_border_run_padded': (ctypes.c_int, [_vp, _pvp, _pvp, _i32, _vp]),
-    'soda_hip_border_run_device': (ctypes.c_int, [_vp, _pvp, _pvp, _i32, _vp]),
-    'soda_hip_periodic_run_device': (ctypes.c_int, [_vp, _pvp, _pvp, _i32,
-                                                    _vp]),
     'soda_hip_box_host': (ctypes.c_int, [_vp, _pi32, _vp, _pi32, _i32, _i32,
                                          _i32, _pi32, _pi32, _pi32]),
     'soda_hip_border_fused_plan': (ctypes.c_int, [
@@ -447,16 +439,11 @@ API = {
         ctypes.POINTER(ctypes.c_size_t), _pvp, ctypes.POINTER(ctypes.c_size_t),
         ctypes.POINTER(_vp)
     ]),
-    'soda_hip_border_fused_destroy': (ctypes.c_int, [_vp]),
     'soda_hip_border_fused_info': (ctypes.c_int, [
         _vp, ctypes.POINTER(BorderFusedInfo)
     ]),
     'soda_hip_border_fused_move': (ctypes.c_int, [_vp, _i32, _i32, _pvp, _pvp,
                                                   _i32, _vp]),
-    'soda_hip_border_fused_run_padded': (ctypes.c_int, [_vp, _pvp, _pvp, _i32,
-                                                        _vp]),
-    'soda_hip_border_fused_run_device': (ctypes.c_int, [_vp, _pvp, _pvp, _i32,
-                                                        _vp]),
     'soda_hip_border_fused_residual_boxes': (ctypes.c_int, [
         ctypes.POINTER(Plan), ctypes.POINTER(BorderFusedDesc),
         ctypes.POINTER(BorderFusedBoxes)
@@ -465,6 +452,9 @@ API = {
         'soda_hip_%s_%s' % (handle, name): (ctypes.c_int, argtypes)
         for handle in ('periodic', 'border', 'border_fused')
         for name, argtypes in (
+            ('destroy', [_vp]),
+            ('run_padded', [_vp, _pvp, _pvp, _i32, _vp]),
+            ('run_device', [_vp, _pvp, _pvp, _i32, _vp]),
             ('run_padded_residual', [_vp, _pvp, _pvp, _i32, _vp, _vp]),
             ('run_padded_norms', [_vp, _vp, _pvp, _pvp, _i32, _vp, _vp]),
             ('run_until', [_vp, _pvp, _pvp, _i32, _i32, ctypes.c_double,
@@ -1418,30 +1408,39 @@ class Norms:
 
 
 # -- periodic domains: a program on a torus ------------------
+def _frame_args(arr, ghost_lo: Sequence[int], ghost_hi: Sequence[int],
+                who: str, domain: str):
+  """What soda_hip_wrap_host and soda_hip_extend_host take first -- address,
+  cell size, dimension count, extent, ghost_lo, ghost_hi -- of the padded numpy
+  array `arr`, checked; `who` and `domain` (what the ghosts leave) for the
+  refusals."""
+  import numpy as np
+  if not isinstance(arr, np.ndarray) or not arr.flags['C_CONTIGUOUS'] or \
+      not arr.flags['WRITEABLE']:
+    raise util.InputError('%s: a writable C-contiguous numpy array' % who)
+  dim = arr.ndim
+  if len(ghost_lo) != dim or len(ghost_hi) != dim:
+    raise util.InputError('%s: %d ghost widths per side' % (who, dim))
+  padded = arr.shape[::-1]
+  extent = [p - l - h for p, l, h in zip(padded, ghost_lo, ghost_hi)]
+  if arr.dtype.itemsize not in (1, 2, 4, 8) or not 1 <= dim <= MAX_DIM or \
+      min(extent) < 1 or min(ghost_lo) < 0 or min(ghost_hi) < 0:
+    raise util.InputError(
+        '%s: cells of 1, 2, 4 or 8 bytes, 1 to %d dimensions, ghosts '
+        '>= 0 that leave %s of at least one cell' % (who, MAX_DIM, domain))
+  return (arr.ctypes.data, arr.dtype.itemsize, dim,
+          (ctypes.c_int32 * dim)(*extent), (ctypes.c_int32 * dim)(*ghost_lo),
+          (ctypes.c_int32 * dim)(*ghost_hi))
+
+
 def wrap_host(arr, ghost_lo: Sequence[int], ghost_hi: Sequence[int]):
   """Refills the ghost frame of the padded numpy array `arr` IN PLACE from its
   interior, every ghost cell taking the interior cell it mirrors on the torus
   (soda_hip_wrap_host, plain C++; no GPU needed).  `ghost_lo` / `ghost_hi`:
   ghost cells below / above the torus per dimension, dimension 0 (the fastest,
   the LAST numpy axis) first.  Returns `arr`."""
-  import numpy as np
-  if not isinstance(arr, np.ndarray) or not arr.flags['C_CONTIGUOUS'] or \
-      not arr.flags['WRITEABLE']:
-    raise util.InputError('wrap_host: a writable C-contiguous numpy array')
-  dim = arr.ndim
-  if len(ghost_lo) != dim or len(ghost_hi) != dim:
-    raise util.InputError('wrap_host: %d ghost widths per side' % dim)
-  padded = arr.shape[::-1]
-  extent = [p - l - h for p, l, h in zip(padded, ghost_lo, ghost_hi)]
-  if arr.dtype.itemsize not in (1, 2, 4, 8) or not 1 <= dim <= MAX_DIM or \
-      min(extent) < 1 or min(ghost_lo) < 0 or min(ghost_hi) < 0:
-    raise util.InputError(
-        'wrap_host: cells of 1, 2, 4 or 8 bytes, 1 to %d dimensions, ghosts '
-        '>= 0 that leave a torus of at least one cell' % MAX_DIM)
-  check(library().soda_hip_wrap_host(
-      arr.ctypes.data, arr.dtype.itemsize, dim, (ctypes.c_int32 * dim)(*extent),
-      (ctypes.c_int32 * dim)(*ghost_lo), (ctypes.c_int32 * dim)(*ghost_hi)),
-        'wrap_host')
+  args = _frame_args(arr, ghost_lo, ghost_hi, 'wrap_host', 'a torus')
+  check(library().soda_hip_wrap_host(*args), 'wrap_host')
   return arr
 
 
@@ -1499,15 +1498,30 @@ def periodic_plan(plan: Plan, extent: Sequence[int], refill_every: int,
   the handle refuses (BackendError)."""
   desc = _periodic_desc(plan.dim, extent, refill_every, ghost_lo, ghost_hi,
                         preserve, not_iterable)
-  raw = PeriodicInfo()
+  raw, chunks = _plan_call('periodic_plan', plan, desc, PeriodicInfo(),
+                           iterate)
+  return _periodic_info(raw, plan.dim), chunks
+
+
+def _plan_call(what: str, plan: Plan, desc, raw, iterate: int):
+  """The plan entry soda_hip_<what> on `desc`: (`raw`, the info struct, filled;
+  the iterations of every chunk of a run of `iterate`)."""
   cap = max(1, iterate)
   chunks = (ctypes.c_int32 * cap)()
   n = ctypes.c_int32()
-  check(library().soda_hip_periodic_plan(ctypes.byref(plan),
-                                         ctypes.byref(desc), iterate,
-                                         ctypes.byref(raw), cap, chunks,
-                                         ctypes.byref(n)), 'periodic_plan')
-  return _periodic_info(raw, plan.dim), list(chunks[:n.value])
+  check(getattr(library(), 'soda_hip_' + what)(
+      ctypes.byref(plan), ctypes.byref(desc), iterate, ctypes.byref(raw), cap,
+      chunks, ctypes.byref(n)), what)
+  return raw, list(chunks[:n.value])
+
+
+def _helper_resources(module, stem: str, elem: int, dim: int):
+  """(code object, kernel_resources of it) of a helper module (wrap, extend,
+  box) of a cell size and dimension count: `module`.source is its text,
+  `stem` names its file."""
+  code = compile_source(module.source(elem, dim),
+                        '%s_e%d_%dd.hip' % (stem, elem, dim))
+  return code, kernel_resources(code)
 
 
 def wrap_resources(elem: int, dim: int):
@@ -1515,9 +1529,7 @@ def wrap_resources(elem: int, dim: int):
   and dimension count: JIT-built like every module, cached like them; needs
   no GPU."""
   from soda_amd.codegen.hip import wrap as _wrap
-  code = compile_source(_wrap.source(elem, dim),
-                        'wrap_e%d_%dd.hip' % (elem, dim))
-  return code, kernel_resources(code)
+  return _helper_resources(_wrap, 'wrap', elem, dim)
 
 
 class Periodic:
@@ -1532,24 +1544,51 @@ class Periodic:
   def _fn(self, name):
     return getattr(self._lib, self._entry + name)
 
-  def _codes_of(self, resources):
-    """(codes, sizes) for the create entry: the code object `resources(elem,
-    dim)` gives for every cell size among the inputs and outputs."""
+  def _codes_of(self, *resources):
+    """[codes, sizes, ...] for the create entry, a pair per function of
+    `resources`: the code object `resources[j](elem, dim)` gives for every
+    cell size among the inputs and outputs."""
     st = self.prog.stencil
-    codes = (ctypes.c_void_p * 4)()
-    sizes = (ctypes.c_size_t * 4)()
-    self._codes = []
-    if not st.preserve_border:      # (refused by create: nothing to build for)
-      sizes_needed = {t.size_in_bytes
-                      for t in list(st.input_types) + list(st.output_types)}
-      for elem in sorted(sizes_needed & {1, 2, 4, 8}):
-        code, _ = resources(elem, st.dim)
-        buf = ctypes.create_string_buffer(code, len(code))
-        self._codes.append(buf)
-        i = elem.bit_length() - 1
-        codes[i] = ctypes.cast(buf, ctypes.c_void_p)
-        sizes[i] = len(code)
-    return codes, sizes
+    self._codes = []                # (the buffers, kept alive with the handle)
+    args = []
+    for resource in resources:
+      codes = (ctypes.c_void_p * 4)()
+      sizes = (ctypes.c_size_t * 4)()
+      if not st.preserve_border:    # (refused by create: nothing to build for)
+        sizes_needed = {t.size_in_bytes
+                        for t in list(st.input_types) + list(st.output_types)}
+        for elem in sorted(sizes_needed & {1, 2, 4, 8}):
+          code, _ = resource(elem, st.dim)
+          buf = ctypes.create_string_buffer(code, len(code))
+          self._codes.append(buf)
+          i = elem.bit_length() - 1
+          codes[i] = ctypes.cast(buf, ctypes.c_void_p)
+          sizes[i] = len(code)
+      args += [codes, sizes]
+    return args
+
+  def _begin(self, prog: 'Program', extent: Sequence[int], modes=None) -> bool:
+    """What every constructor starts with: the extent checked and kept, the
+    `modes` of a bordered domain kept one name per dimension.  Returns the
+    `not_iterable` of the desc."""
+    st = prog.stencil
+    self.prog, self.extent = prog, tuple(int(e) for e in extent)
+    prog._check_extent(self.extent)
+    if modes is not None:
+      self.modes = tuple([modes] * st.dim if isinstance(modes, str) else modes)
+    return list(st.input_types) != list(st.output_types)
+
+  def _create(self, desc, resources, where: str) -> None:
+    """What every constructor ends with: the handle made by the library's
+    create entry from `desc` and the code objects of `resources`, and
+    registered with its program.  `where`: the domain, for a refusal."""
+    args = self._codes_of(*resources)
+    self._lib = library()
+    self._handle = ctypes.c_void_p()
+    check(self._fn('create')(self.prog._handle, ctypes.byref(desc), *args,
+                             ctypes.byref(self._handle)),
+          '`%s` on %s' % (self.prog.stencil.app_name, where))
+    self.prog._periodic.append(self)
 
   def __init__(self, prog: 'Program', extent: Sequence[int],
                refill_every: Optional[int] = None,
@@ -1558,27 +1597,18 @@ class Periodic:
     fusion depth of the program, so that a chunk is one launch).  `ghosts` =
     (lo, hi): the frame, for callers that size it themselves (default:
     periodic_ghosts)."""
+    not_iterable = self._begin(prog, extent)
     st = prog.stencil
-    self.prog, self.extent = prog, tuple(int(e) for e in extent)
-    prog._check_extent(self.extent)
     k = int(refill_every or 0)
     if k < 0:
       raise util.InputError('periodic: refill_every < 0')
     if not k:
       k = max(p.fused_iters for p in prog.module.passes)
     lo, hi = ghosts if ghosts is not None else periodic_ghosts(st, k)
-    desc = _periodic_desc(
-        st.dim, self.extent, k, lo, hi, st.preserve_border,
-        not_iterable=list(st.input_types) != list(st.output_types))
-    codes, sizes = self._codes_of(wrap_resources)
-    self._lib = library()
-    self._handle = ctypes.c_void_p()
-    check(self._lib.soda_hip_periodic_create(prog._handle, ctypes.byref(desc),
-                                             codes, sizes,
-                                             ctypes.byref(self._handle)),
-          '`%s` on a torus of %s' % (st.app_name, 'x'.join(
-              map(str, self.extent))))
-    prog._periodic.append(self)
+    desc = _periodic_desc(st.dim, self.extent, k, lo, hi, st.preserve_border,
+                          not_iterable)
+    self._create(desc, [wrap_resources],
+                 'a torus of %s' % 'x'.join(map(str, self.extent)))
 
   def close(self) -> None:
     if getattr(self, '_handle', None):
@@ -1615,14 +1645,18 @@ class Periodic:
     check(self._fn('fill')(self._handle, arr, len(arrays),
                            ctypes.c_void_p(stream)), '%s: fill' % self._what)
 
-  def _run(self, fn, what, outputs, inputs, iterate, stream):
+  def _check_counts(self, what, outputs, inputs):
     st = self.prog.stencil
-    iterate = st.iterate if iterate is None else iterate
     if len(outputs) != len(st.output_names) or \
         len(inputs) != len(st.input_names) + len(st.param_stmts):
       raise util.InputError('%s: %d outputs, %d inputs and param arrays' % (
           what, len(st.output_names),
           len(st.input_names) + len(st.param_stmts)))
+
+  def _run(self, fn, what, outputs, inputs, iterate, stream):
+    st = self.prog.stencil
+    iterate = st.iterate if iterate is None else iterate
+    self._check_counts(what, outputs, inputs)
     outs = (ctypes.c_void_p * len(outputs))(*outputs)
     ins = (ctypes.c_void_p * len(inputs))(*inputs)
     check(fn(self._handle, outs, ins, iterate, ctypes.c_void_p(stream)),
@@ -1673,12 +1707,7 @@ class Periodic:
     if norm not in (None, 'l1', 'l2'):
       raise util.InputError("run_until: norm is None, 'l1' or 'l2'")
     st = self.prog.stencil
-    if len(outputs) != len(st.output_names) or \
-        len(inputs) != len(st.input_names) + len(st.param_stmts):
-      raise util.InputError('%s run_until: %d outputs, %d inputs and param '
-                            'arrays' % (self._what, len(st.output_names),
-                                        len(st.input_names) +
-                                        len(st.param_stmts)))
+    self._check_counts('%s run_until' % self._what, outputs, inputs)
     outs = (ctypes.c_void_p * len(outputs))(*outputs)
     ins = (ctypes.c_void_p * len(inputs))(*inputs)
     done = ctypes.c_int32(0)
@@ -1753,27 +1782,13 @@ def extend_host(arr, ghost_lo: Sequence[int], ghost_hi: Sequence[int], modes,
   cell outside in a `constant` dimension, converted to the cell type.  Returns
   `arr`."""
   import numpy as np
-  if not isinstance(arr, np.ndarray) or not arr.flags['C_CONTIGUOUS'] or \
-      not arr.flags['WRITEABLE']:
-    raise util.InputError('extend_host: a writable C-contiguous numpy array')
-  dim = arr.ndim
-  if len(ghost_lo) != dim or len(ghost_hi) != dim:
-    raise util.InputError('extend_host: %d ghost widths per side' % dim)
-  padded = arr.shape[::-1]
-  extent = [p - l - h for p, l, h in zip(padded, ghost_lo, ghost_hi)]
-  if arr.dtype.itemsize not in (1, 2, 4, 8) or not 1 <= dim <= MAX_DIM or \
-      min(extent) < 1 or min(ghost_lo) < 0 or min(ghost_hi) < 0:
-    raise util.InputError(
-        'extend_host: cells of 1, 2, 4 or 8 bytes, 1 to %d dimensions, ghosts '
-        '>= 0 that leave a domain of at least one cell' % MAX_DIM)
+  args = _frame_args(arr, ghost_lo, ghost_hi, 'extend_host', 'a domain')
   bits = constant if isinstance(constant, (bytes, bytearray)) else \
       np.asarray(constant).astype(arr.dtype).tobytes()
   if len(bits) != arr.dtype.itemsize:
     raise util.InputError('extend_host: a constant of one cell')
   check(library().soda_hip_extend_host(
-      arr.ctypes.data, arr.dtype.itemsize, dim, (ctypes.c_int32 * dim)(*extent),
-      (ctypes.c_int32 * dim)(*ghost_lo), (ctypes.c_int32 * dim)(*ghost_hi),
-      (ctypes.c_int32 * dim)(*_border_modes(modes, dim)),
+      *args, (ctypes.c_int32 * arr.ndim)(*_border_modes(modes, arr.ndim)),
       int.from_bytes(bits, sys.byteorder)), 'extend_host')
   return arr
 
@@ -1807,21 +1822,24 @@ def border_plan(plan: Plan, extent: Sequence[int], modes,
   (which reach the library unchecked).  With a mode other than `wrap`,
   `refill_every` must be 0 or 1 and every chunk is one iteration; with all
   `wrap` this is periodic_plan."""
-  raw_modes = list(modes) if not isinstance(modes, str) and all(
-      isinstance(m, int) for m in modes) else _border_modes(modes, plan.dim)
-  if len(raw_modes) != plan.dim:
-    raise util.InputError('border: one mode per dimension (%d)' % plan.dim)
+  raw_modes = _raw_modes(modes, plan.dim)
   desc = _border_desc(_periodic_desc(
       plan.dim, extent, refill_every, ghost_lo, ghost_hi, preserve,
       not_iterable), raw_modes, ())
-  raw = PeriodicInfo()
-  cap = max(1, iterate)
-  chunks = (ctypes.c_int32 * cap)()
-  n = ctypes.c_int32()
-  check(library().soda_hip_border_plan(ctypes.byref(plan), ctypes.byref(desc),
-                                       iterate, ctypes.byref(raw), cap, chunks,
-                                       ctypes.byref(n)), 'border_plan')
-  return _periodic_info(raw, plan.dim), list(chunks[:n.value])
+  raw, chunks = _plan_call('border_plan', plan, desc, PeriodicInfo(), iterate)
+  return _periodic_info(raw, plan.dim), chunks
+
+
+def _raw_modes(modes, dim: int, *reaches):
+  """SODA_HIP_BORDER_* per dimension for a plan entry: `modes` as names
+  (_border_modes), or as raw numbers, which pass unchecked.  `reaches`: the
+  reach_lo and reach_hi of a fused request, which need `dim` entries too."""
+  raw = list(modes) if not isinstance(modes, str) and all(
+      isinstance(m, int) for m in modes) else _border_modes(modes, dim)
+  if any(len(v) != dim for v in (raw,) + reaches):
+    raise util.InputError('border: one mode%s per dimension (%d)' % (
+        ' and one reach per side' if reaches else '', dim))
+  return raw
 
 
 def extend_resources(elem: int, dim: int):
@@ -1829,9 +1847,7 @@ def extend_resources(elem: int, dim: int):
   and dimension count: JIT-built like every module, cached like them; needs
   no GPU."""
   from soda_amd.codegen.hip import extend as _extend
-  code = compile_source(_extend.source(elem, dim),
-                        'extend_e%d_%dd.hip' % (elem, dim))
-  return code, kernel_resources(code)
+  return _helper_resources(_extend, 'extend', elem, dim)
 
 
 class Bordered(Periodic):
@@ -1850,28 +1866,18 @@ class Bordered(Periodic):
     first, of wrap / clamp / mirror / mirror101 / constant.  `constants`: a
     scalar or {input: scalar}, converted to the cell type's bits (default
     zero); an output's ghost takes the constant of the input it replaces."""
+    not_iterable = self._begin(prog, extent, modes)
     st = prog.stencil
-    self.prog, self.extent = prog, tuple(int(e) for e in extent)
-    prog._check_extent(self.extent)
-    self.modes = tuple([modes] * st.dim if isinstance(modes, str) else modes)
     raw_modes = _border_modes(modes, st.dim)
     k = 1
     if not any(raw_modes):          # a torus: Periodic's default
       k = max(p.fused_iters for p in prog.module.passes)
     lo, hi = periodic_ghosts(st, k)
     desc = _border_desc(_periodic_desc(
-        st.dim, self.extent, k, lo, hi, st.preserve_border,
-        not_iterable=list(st.input_types) != list(st.output_types)),
+        st.dim, self.extent, k, lo, hi, st.preserve_border, not_iterable),
                         raw_modes, _border_constants(st, constants))
-    codes, sizes = self._codes_of(extend_resources)
-    self._lib = library()
-    self._handle = ctypes.c_void_p()
-    check(self._lib.soda_hip_border_create(prog._handle, ctypes.byref(desc),
-                                           codes, sizes,
-                                           ctypes.byref(self._handle)),
-          '`%s` on %s with borders %s' % (st.app_name, 'x'.join(
-              map(str, self.extent)), ', '.join(self.modes)))
-    prog._periodic.append(self)
+    self._create(desc, [extend_resources], '%s with borders %s' % (
+        'x'.join(map(str, self.extent)), ', '.join(self.modes)))
 
 
 # -- bordered domains, fused away from the walls (DESIGN.md 4.13) -------------
@@ -1914,8 +1920,7 @@ def box_resources(elem: int, dim: int):
   and dimension count: JIT-built like every module, cached like them; needs
   no GPU."""
   from soda_amd.codegen.hip import box as _box
-  code = compile_source(_box.source(elem, dim), 'box_e%d_%dd.hip' % (elem, dim))
-  return code, kernel_resources(code)
+  return _helper_resources(_box, 'box', elem, dim)
 
 
 def border_fused_ghosts(stencil: core.Stencil, modes, depth: int):
@@ -1974,23 +1979,13 @@ def border_fused_plan(plan: Plan, extent: Sequence[int], modes, depth: int,
   """border_plan for the fused form (soda_hip_border_fused_plan; no GPU
   needed): (info, chunks), info as BorderedFused.info().  `depth` 0: the
   plan's deepest pass."""
-  raw_modes = list(modes) if not isinstance(modes, str) and all(
-      isinstance(m, int) for m in modes) else _border_modes(modes, plan.dim)
-  if len(raw_modes) != plan.dim or len(reach_lo) != plan.dim or \
-      len(reach_hi) != plan.dim:
-    raise util.InputError('border: one mode and one reach per side per '
-                          'dimension (%d)' % plan.dim)
+  raw_modes = _raw_modes(modes, plan.dim, reach_lo, reach_hi)
   desc = _border_fused_desc(_border_desc(_periodic_desc(
       plan.dim, extent, refill_every, ghost_lo, ghost_hi, preserve,
       not_iterable), raw_modes, ()), depth, reach_lo, reach_hi)
-  raw = BorderFusedInfo()
-  cap = max(1, iterate)
-  chunks = (ctypes.c_int32 * cap)()
-  n = ctypes.c_int32()
-  check(library().soda_hip_border_fused_plan(
-      ctypes.byref(plan), ctypes.byref(desc), iterate, ctypes.byref(raw), cap,
-      chunks, ctypes.byref(n)), 'border_fused_plan')
-  return _border_fused_info(raw, plan.dim), list(chunks[:n.value])
+  raw, chunks = _plan_call('border_fused_plan', plan, desc, BorderFusedInfo(),
+                           iterate)
+  return _border_fused_info(raw, plan.dim), chunks
 
 
 def border_fused_residual_boxes(plan: Plan, extent: Sequence[int], modes,
@@ -2006,12 +2001,7 @@ def border_fused_residual_boxes(plan: Plan, extent: Sequence[int], modes,
   coordinates of the domain, 'strips': [{'dim', 'low': (lo, hi), 'high': (lo,
   hi)}] in each strip's own padded coordinates}, dimension 0 first.  At depth
   1 and on a torus there are no strips and the trusted box is the domain."""
-  raw_modes = list(modes) if not isinstance(modes, str) and all(
-      isinstance(m, int) for m in modes) else _border_modes(modes, plan.dim)
-  if len(raw_modes) != plan.dim or len(reach_lo) != plan.dim or \
-      len(reach_hi) != plan.dim:
-    raise util.InputError('border: one mode and one reach per side per '
-                          'dimension (%d)' % plan.dim)
+  raw_modes = _raw_modes(modes, plan.dim, reach_lo, reach_hi)
   desc = _border_fused_desc(_border_desc(_periodic_desc(
       plan.dim, extent, 0, ghost_lo, ghost_hi, preserve, not_iterable),
                                          raw_modes, ()), depth, reach_lo,
@@ -2048,10 +2038,8 @@ class BorderedFused(Bordered):
     (DESIGN.md 4.13 has heat3d at depth 2).  info()['depth'] is the depth as
     resolved: 1, and Bordered's loop, where the program cannot iterate or a
     wall dimension is narrower than the two parts of its strip."""
+    not_iterable = self._begin(prog, extent, modes)
     st = prog.stencil
-    self.prog, self.extent = prog, tuple(int(e) for e in extent)
-    prog._check_extent(self.extent)
-    self.modes = tuple([modes] * st.dim if isinstance(modes, str) else modes)
     raw_modes = _border_modes(modes, st.dim)
     depth = int(depth)
     if depth < 0:
@@ -2060,24 +2048,14 @@ class BorderedFused(Bordered):
       depth = max(p.fused_iters for p in prog.module.passes)
     rlo, rhi, lo, hi = border_fused_ghosts(st, modes, depth)
     desc = _border_fused_desc(_border_desc(_periodic_desc(
-        st.dim, self.extent, 0, lo, hi, st.preserve_border,
-        not_iterable=list(st.input_types) != list(st.output_types)),
+        st.dim, self.extent, 0, lo, hi, st.preserve_border, not_iterable),
                                            raw_modes,
                                            _border_constants(st, constants)),
                               depth, rlo, rhi)
-    codes, sizes = self._codes_of(extend_resources)
-    extend_codes = self._codes
-    box_codes, box_sizes = self._codes_of(box_resources)
-    self._codes = extend_codes + self._codes
-    self._lib = library()
-    self._handle = ctypes.c_void_p()
-    check(self._lib.soda_hip_border_fused_create(
-        prog._handle, ctypes.byref(desc), codes, sizes, box_codes, box_sizes,
-        ctypes.byref(self._handle)),
-          '`%s` on %s with borders %s, fused %d deep' % (
-              st.app_name, 'x'.join(map(str, self.extent)),
-              ', '.join(self.modes), depth))
-    prog._periodic.append(self)
+    self._create(desc, [extend_resources, box_resources],
+                 '%s with borders %s, fused %d deep' % (
+                     'x'.join(map(str, self.extent)), ', '.join(self.modes),
+                     depth))
 
   def info(self) -> dict:
     """Bordered.info() of the handle on the domain, and: 'depth' as resolved,
@@ -2602,23 +2580,8 @@ class Program:
     """`run` on a torus: numpy arrays of the domain in (shape = extent
     reversed; params as in `run`), the outputs out, EVERY cell of them
     defined.  A plain allocate / copy in / Periodic.run_device / copy out."""
-    import numpy as np
-    st = self.stencil
-    lib = self._lib
-    iterate = st.iterate if iterate is None else iterate
-    first = np.asarray(inputs[st.input_names[0]])
-    extent = tuple(first.shape[::-1])
-    self._check_extent(extent)
-    host_in = _host_inputs(st, inputs, first.shape)
-    result = {n: np.empty(first.shape, dtype=np.dtype(t.np_name))
-              for n, t in zip(st.output_names, st.output_types)}
-    dense = list(result.values())
-    with self.periodic(extent, refill_every) as per, \
-        _staged(lib, self.device, host_in, dense, 'run_periodic',
-                synchronize=True) as (dev_in, dev_out):
-      per.run_device(dev_out, dev_in, iterate)
-      _copy_out(lib, dense, dev_out, 'run_periodic')
-    return result
+    return self._run_domain(lambda extent: self.periodic(extent, refill_every),
+                            'run_periodic', inputs, iterate)
 
   # -- bordered domains ------------------------------------------------------
   def bordered(self, extent: Sequence[int], modes, constants=None,
@@ -2641,6 +2604,13 @@ class Program:
     `modes` (one name, or one per dimension, dimension 0 first) and
     `constants` (a scalar or {input: scalar}; default zero).  A plain allocate
     / copy in / Bordered.run_device / copy out.  `depth`: as for `bordered`."""
+    return self._run_domain(
+        lambda extent: self.bordered(extent, modes, constants, depth),
+        'run_bordered', inputs, iterate)
+
+  def _run_domain(self, handle_of, what, inputs, iterate):
+    """run's numpy plumbing around `handle_of(extent)`.run_device; the handle
+    is made once the inputs are checked, and closed here."""
     import numpy as np
     st = self.stencil
     lib = self._lib
@@ -2652,11 +2622,11 @@ class Program:
     result = {n: np.empty(first.shape, dtype=np.dtype(t.np_name))
               for n, t in zip(st.output_names, st.output_types)}
     dense = list(result.values())
-    with self.bordered(extent, modes, constants, depth) as bor, \
-        _staged(lib, self.device, host_in, dense, 'run_bordered',
+    with handle_of(extent) as dom, \
+        _staged(lib, self.device, host_in, dense, what,
                 synchronize=True) as (dev_in, dev_out):
-      bor.run_device(dev_out, dev_in, iterate)
-      _copy_out(lib, dense, dev_out, 'run_bordered')
+      dom.run_device(dev_out, dev_in, iterate)
+      _copy_out(lib, dense, dev_out, what)
     return result
 
   def _run_domain_until(self, handle, what, inputs, tol, max_iterate,
