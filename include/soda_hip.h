@@ -802,7 +802,8 @@ int soda_hip_run_device_until_norm(soda_hip_program_t* program,
  * on k, bit for bit.
  * Residuals, norms and runs until converged: the block "residual, norms and
  * run_until on a domain" below.
- * Not served on a torus: slabs, groups, ranks, batches, the wire format,
+ * Batches of tori: the block "batched domains" below.
+ * Not served on a torus: slabs, groups, ranks, the wire format,
  * `border: preserve` (a torus has no border). */
 typedef struct soda_hip_periodic_desc {
   int32_t extent[SODA_HIP_MAX_DIM];    /* N, the torus */
@@ -938,8 +939,9 @@ int soda_hip_periodic_run_device(soda_hip_periodic_t* handle,
  * refill_every, bit for bit.
  * Residuals, norms and runs until converged: the block "residual, norms and
  * run_until on a domain" below.
- * Not served on a bordered domain: slabs, groups, ranks, batches, the wire
- * format, `border: preserve`. */
+ * Batches of bordered domains: the block "batched domains" below.
+ * Not served on a bordered domain: slabs, groups, ranks, the wire format,
+ * `border: preserve`. */
 #define SODA_HIP_BORDER_WRAP 0
 #define SODA_HIP_BORDER_CLAMP 1
 #define SODA_HIP_BORDER_MIRROR 2
@@ -1025,6 +1027,62 @@ int soda_hip_border_run_padded(soda_hip_border_t* handle, void* const* outputs,
 int soda_hip_border_run_device(soda_hip_border_t* handle, void* const* outputs,
                                const void* const* inputs, int32_t iterate,
                                void* stream);
+
+/* -- batched domains: many tori or bordered grids at once -- */
+/* The two blocks above over `batch` independent domains of ONE extent, for a
+ * program whose plan is batched (LowerOptions.batch): every array -- the
+ * caller's dense or padded ones, the handle's scratch -- is `batch` items one
+ * behind the other like a contiguous [batch, ...] array, every item is wrapped
+ * or extended on its own, and each chunk, fill, pad and crop is ONE launch per
+ * kernel for all items (the helper kernels' `_bt` forms take the item from
+ * blockIdx.z; the program's kernels run as in soda_hip_run_device_batch).
+ * Per item the semantics and the bits are those of an unbatched handle on
+ * that item alone.  Param arrays are shared by all items.
+ *
+ * The plan entries: pure functions.  P, the ghosts, k and the chunks are what
+ * soda_hip_periodic_plan / soda_hip_border_plan give for the same plan built
+ * without `batch`; scratch_bytes is that figure times `batch`; the geometry is
+ * checked by soda_hip_plan_geometry_batch on P.  They refuse what those
+ * entries refuse, but for a batched plan, and with SODA_HIP_ERR_INVALID:
+ * `batch` outside 1..SODA_HIP_MAX_BATCH, a plan that is not batched (the
+ * entries never fall back to a loop of launches). */
+int soda_hip_periodic_plan_batch(const soda_hip_plan_t* plan,
+                                 const soda_hip_periodic_desc_t* desc,
+                                 int32_t batch, int32_t iterate,
+                                 soda_hip_periodic_info_t* info,
+                                 int32_t capacity, int32_t* chunks,
+                                 int32_t* count);
+int soda_hip_border_plan_batch(const soda_hip_plan_t* plan,
+                               const soda_hip_border_desc_t* desc,
+                               int32_t batch, int32_t iterate,
+                               soda_hip_periodic_info_t* info,
+                               int32_t capacity, int32_t* chunks,
+                               int32_t* count);
+/* A handle of the types above, fixed to one (extent, batch).  code[i]: the
+ * code object of the BATCHED wrap resp. extend module (codegen/hip/wrap.py,
+ * extend.py with batch=True) of 1 << i byte cells.  All scratch -- [batch,
+ * P...] per array -- is allocated here; a refusal (the plan entries') launches
+ * and allocates nothing.
+ * soda_hip_<kind>_info, _fill, _run_padded, _run_device and _destroy serve
+ * such a handle under their contracts as written, each array taken as `batch`
+ * items long: the device entry contract on the whole arrays, asynchronous,
+ * never allocating in the handle, capturable after the first eager call (which
+ * sizes the program's scratch and calibrates for (P, batch)).
+ * SODA_HIP_ERR_UNSUPPORTED on such a handle, nothing launched:
+ * _run_padded_residual, _run_padded_norms, _run_until, _run_until_norm (the
+ * residual of a batch is not served).  soda_hip_border_fused_* has no batched
+ * form and keeps refusing a batched plan. */
+int soda_hip_periodic_create_batch(soda_hip_program_t* program,
+                                   const soda_hip_periodic_desc_t* desc,
+                                   int32_t batch,
+                                   const void* const* wrap_code,
+                                   const size_t* wrap_code_size,
+                                   soda_hip_periodic_t** handle);
+int soda_hip_border_create_batch(soda_hip_program_t* program,
+                                 const soda_hip_border_desc_t* desc,
+                                 int32_t batch, const void* const* code,
+                                 const size_t* code_size,
+                                 soda_hip_border_t** handle);
 
 /* -- bordered domains, fused away from the walls ----------- */
 /* The block above advances one iteration per launch.  Here a chunk of n <= T

@@ -22,10 +22,17 @@
 // a fused handle counts each cell where it is made right -- the interior run
 // a trusted box, every strip its two rims.
 //
+// Batched domains (soda_hip_periodic_create_batch,
+// soda_hip_border_create_batch): the same handle over a batched program, fixed
+// to one (extent, batch).  Every array is `batch` items one behind the other;
+// the batch is a field of the frame, one more launch dimension of the helper
+// kernels (their `_bt` forms) and the `batch` of the chunks' RunRequest.
+//
 // Top to bottom: the helper kernels' launchers and loader, planning, the two
 // handle structs, the chunk loop, the run cores, the exported entries.
 #include "soda_internal.h"
 
+#include <cstddef>
 #include <cstring>
 #include <new>
 
@@ -65,6 +72,19 @@ struct ExtendArgs {
   int32_t mode[4];
   uint64_t constant[16];
 };
+
+// a batched wrap or extend kernel's (soda_rt_domain_batch.h): its unbatched
+// block, then the cells from an item to the next in the destination and in
+// the source.  Room for the steps behind either block
+struct DomainArgs {
+  ExtendArgs e;
+  uint64_t steps[2];
+};
+// (the kernels' struct puts the steps at the block's size: no padding)
+static_assert(sizeof(WrapArgs) % alignof(uint64_t) == 0 &&
+                  sizeof(ExtendArgs) % alignof(uint64_t) == 0 &&
+                  offsetof(DomainArgs, steps) == sizeof(ExtendArgs),
+              "the item steps lie right behind either block");
 
 // the box kernel's one argument, as soda_rt_box.h declares it
 struct BoxArgs {
@@ -116,6 +136,10 @@ struct Frame {
   uint64_t constant[SODA_HIP_MAX_TENSORS] = {};   // ... and per input
   Torus t;
   Helpers wrap;                        // the wrap or the extend kernels
+  int32_t batch = 0;                   // > 0: a batched handle, every array
+                                       // that many items, `wrap` the _bt
+                                       // kernels
+  int32_t items() const { return batch ? batch : 1; }
 };
 
 int log2_elem(int elem) {
@@ -187,10 +211,11 @@ bool wrap_regions(const Torus& t, WrapJob job, int elem, WrapArgs* a) {
 // of elem[i] bytes.  `prepare(size, tensor, m, &args, &total)` fills the
 // kernel's argument for the `m` tensors tensor[0..m) of that size and says
 // how many items the launch has (0: none, it is skipped), or refuses.  `bytes`
-// of `args` reach the kernel.
+// of `args` reach the kernel; `batch` is the grid's z: the domains of a
+// batched handle, 1 elsewhere.
 template <class Args, class Prepare>
 int launch_by_size(const Helpers& kernels, const char* who, const char* what,
-                   const int32_t* elem, int count, size_t bytes,
+                   const int32_t* elem, int count, size_t bytes, int32_t batch,
                    hipStream_t stream, Prepare prepare) {
   for (int size = 1; size <= 8; size *= 2) {
     int tensor[16], m = 0;
@@ -211,25 +236,33 @@ int launch_by_size(const Helpers& kernels, const char* who, const char* what,
     void* extra[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &args,
                      HIP_LAUNCH_PARAM_BUFFER_SIZE, &bytes,
                      HIP_LAUNCH_PARAM_END};
-    HIP_TRY(hipModuleLaunchKernel(fn, (unsigned)blocks, (unsigned)m, 1,
-                                  kHelperBlock, 1, 1, 0, stream, nullptr,
-                                  extra));
+    HIP_TRY(hipModuleLaunchKernel(fn, (unsigned)blocks, (unsigned)m,
+                                  (unsigned)batch, kHelperBlock, 1, 1, 0,
+                                  stream, nullptr, extra));
   }
   return SODA_HIP_OK;
 }
 
 // One job on `count` tensors: dst[i] / src[i] with cells of elem[i] bytes (a
 // bordered domain: and the constant of input i); one launch per cell size
-// among them (no ghost cells: nothing to fill, no launch).
+// among them (no ghost cells: nothing to fill, no launch).  A batched handle:
+// the job on every item of the arrays, in the same launches.
 int wrap_launch(const Frame& f, WrapJob job, void* const* dst,
                 const void* const* src, const int32_t* elem, int count,
                 hipStream_t stream) {
-  // the wrap kernel takes the block without the border behind it
-  const size_t bytes = f.kind->extend ? sizeof(ExtendArgs) : sizeof(WrapArgs);
-  return launch_by_size<ExtendArgs>(
-      f.wrap, f.kind->who, "wrap", elem, count, bytes, stream,
-      [&](int size, const int* tensor, int m, ExtendArgs* args,
+  // the wrap kernel takes the block without the border behind it, a batched
+  // kernel the item steps behind its block
+  const size_t block = f.kind->extend ? sizeof(ExtendArgs) : sizeof(WrapArgs);
+  const uint64_t padded = (uint64_t)cells_of(f.t.p, f.t.dim);
+  const uint64_t dense = (uint64_t)cells_of(f.t.n, f.t.dim);
+  const uint64_t steps[2] = {job == kCrop ? dense : padded,
+                             job == kPad ? dense : padded};
+  return launch_by_size<DomainArgs>(
+      f.wrap, f.kind->who, "wrap", elem, count,
+      block + (f.batch ? sizeof steps : 0), f.items(), stream,
+      [&](int size, const int* tensor, int m, DomainArgs* all,
           uint64_t* total) -> int {
+        ExtendArgs* args = &all->e;
         for (int j = 0; j < m; ++j) {
           args->w.dst[j] = dst[tensor[j]];
           args->w.src[j] = src[tensor[j]];
@@ -240,6 +273,8 @@ int wrap_launch(const Frame& f, WrapJob job, void* const* dst,
           return fail(SODA_HIP_ERR_INVALID,
                       std::string(f.kind->who) +
                           ": 2^31 rows or more; nothing was launched");
+        if (f.batch)      // (behind the wrap kernel's block: over the border)
+          memcpy(reinterpret_cast<char*>(all) + block, steps, sizeof steps);
         *total = args->w.total;
         return SODA_HIP_OK;
       });
@@ -263,7 +298,7 @@ int box_launch(const Helpers& kernels, void* const* dst, const int32_t* dext,
                     "launched");
     }
   return launch_by_size<BoxArgs>(
-      kernels, "border_fused", "box", elem, count, sizeof(BoxArgs), stream,
+      kernels, "border_fused", "box", elem, count, sizeof(BoxArgs), 1, stream,
       [&](int size, const int* tensor, int m, BoxArgs* a,
           uint64_t* total) -> int {
         for (int j = 0; j < m; ++j) {
@@ -327,22 +362,24 @@ int helpers_needed(const soda_hip_plan_t& plan, const void* const* code,
 }
 
 // The module of every needed cell size loaded from `code`, and its kernel
-// `<kernel>_e<bytes>_d<dim>` looked up.
+// `<kernel>_e<bytes>_d<dim>` looked up (`batch`: `..._bt`, the batched one).
 int load_helpers(Helpers* out, const bool need[4], const void* const* code,
                  const char* kernel, int dim, const std::string& who,
-                 const char* what) {
+                 const char* what, bool batch = false) {
   for (int l = 0; l < 4; ++l) {
     if (!need[l]) continue;
     hipError_t e = hipModuleLoadData(&out->module[l], code[l]);
     if (e != hipSuccess)
       return hip_fail(e, (who + "_create: hipModuleLoadData").c_str());
     char name[64];
-    snprintf(name, sizeof name, "%s_e%d_d%d", kernel, 1 << l, dim);
+    snprintf(name, sizeof name, "%s_e%d_d%d%s", kernel, 1 << l, dim,
+             batch ? "_bt" : "");
     e = hipModuleGetFunction(&out->fn[l], out->module[l], name);
     if (e != hipSuccess)
       return hip_fail(e, (who + "_create: hipModuleGetFunction (is this the " +
-                          what + " module of the cell size and dimension "
-                                 "count?)").c_str());
+                          (batch ? "batched " : "") + what +
+                          " module of the cell size and dimension "
+                          "count?)").c_str());
   }
   return SODA_HIP_OK;
 }
@@ -397,11 +434,31 @@ void list_chunks(int32_t iterate, int32_t k, int32_t capacity, int32_t* chunks,
   if (count) *count = n;
 }
 
-// soda_hip_periodic_plan, and soda_hip_border_plan behind its modes
+// a handle's batch as the _batch entries take it: 1..SODA_HIP_MAX_BATCH, over
+// a batched plan only -- never a loop of launches in its place
+int check_domain_batch(const soda_hip_plan_t& plan, int32_t batch,
+                       const std::string& who) {
+  if (batch < 1 || batch > SODA_HIP_MAX_BATCH) {
+    char buf[160];
+    snprintf(buf, sizeof buf, ": batch = %d, must be 1 to %d (the grid's z "
+             "dimension); nothing was launched", batch, SODA_HIP_MAX_BATCH);
+    return fail(SODA_HIP_ERR_INVALID, who + buf);
+  }
+  if (!plan.batched)
+    return fail(SODA_HIP_ERR_INVALID,
+                who + ": the program's kernels are not batched (build it with "
+                      "LowerOptions.batch / sodac --hip-batch); nothing was "
+                      "launched");
+  return SODA_HIP_OK;
+}
+
+// soda_hip_periodic_plan, and soda_hip_border_plan behind its modes; `batch`
+// > 0: their _batch forms, the batch checked by check_domain_batch (0: the
+// unbatched entries, which refuse a batched plan)
 int plan_core(const Kind& kind, const soda_hip_plan_t* plan,
               const soda_hip_periodic_desc_t* desc, int32_t iterate,
               soda_hip_periodic_info_t* info, int32_t capacity,
-              int32_t* chunks, int32_t* count) {
+              int32_t* chunks, int32_t* count, int32_t batch = 0) {
   const std::string who(kind.who);
   if (!plan || !desc)
     return fail(SODA_HIP_ERR_INVALID, who + "_plan: NULL argument");
@@ -413,7 +470,7 @@ int plan_core(const Kind& kind, const soda_hip_plan_t* plan,
     return fail(SODA_HIP_ERR_UNSUPPORTED,
                 who + ": a program with `border: preserve` pins its border, "
                       "and " + kind.domain + " has none; nothing was launched");
-  if (plan->batched)
+  if (plan->batched && !batch)
     return fail(SODA_HIP_ERR_UNSUPPORTED,
                 who + ": batched plans are not served on " + kind.domain +
                     "; nothing was launched");
@@ -467,8 +524,11 @@ int plan_core(const Kind& kind, const soda_hip_plan_t* plan,
                                kind.who))
       return rc;
   // what the kernels ask of the padded extent: row length, max_extent0, the
-  // 1 GiB window of a plane
-  if (int rc = soda_hip_plan_geometry(plan, out.padded, nullptr, nullptr))
+  // 1 GiB window of a plane (of an item's)
+  if (int rc = batch ? soda_hip_plan_geometry_batch(plan, out.padded, batch,
+                                                    nullptr, nullptr)
+                     : soda_hip_plan_geometry(plan, out.padded, nullptr,
+                                              nullptr))
     return rc;
   const int nin = plan->num_inputs, nout = plan->num_outputs;
   for (int i = 0; i < nin; ++i)
@@ -477,6 +537,7 @@ int plan_core(const Kind& kind, const soda_hip_plan_t* plan,
     out.scratch_bytes +=
         cells * plan->elem_size[nin + o] *
         (can_iterate(*plan, desc->not_iterable != 0) ? 2 : 1);
+  if (batch) out.scratch_bytes *= batch;
   if (info) *info = out;
   list_chunks(iterate, k, capacity, chunks, count);
   return SODA_HIP_OK;
@@ -678,7 +739,8 @@ namespace {
 int create_core(const Kind& kind, soda_hip_program_t* p,
                 const soda_hip_periodic_desc_t* desc, const int32_t* mode,
                 const uint64_t* constant, const void* const* code,
-                const size_t* code_size, soda_hip_periodic** handle) {
+                const size_t* code_size, soda_hip_periodic** handle,
+                int32_t batch = 0) {
   const std::string who(kind.who);
   const soda_hip_plan_t& plan = p->plan;
   if (p->bank_tensors)
@@ -686,7 +748,8 @@ int create_core(const Kind& kind, soda_hip_program_t* p,
                 who + ": programs on wire-format banks are not served on " +
                     kind.domain + "; nothing was launched");
   soda_hip_periodic_info_t info;
-  if (int rc = plan_core(kind, &plan, desc, 0, &info, 0, nullptr, nullptr))
+  if (int rc = plan_core(kind, &plan, desc, 0, &info, 0, nullptr, nullptr,
+                         batch))
     return rc;
   const int nin = plan.num_inputs, nout = plan.num_outputs;
   bool need[4] = {false, false, false, false};
@@ -697,6 +760,7 @@ int create_core(const Kind& kind, soda_hip_program_t* p,
   if (!h) return fail(SODA_HIP_ERR_NOMEM, "new " + who + " handle");
   h->prog = p;
   h->kind = &kind;
+  h->batch = batch;
   h->k = info.refill_every;
   h->not_iterable = desc->not_iterable != 0;
   const bool iterates = can_iterate(plan, h->not_iterable);
@@ -711,8 +775,9 @@ int create_core(const Kind& kind, soda_hip_program_t* p,
   if (constant)
     for (int i = 0; i < nin; ++i) h->constant[i] = constant[i];
   int rc = load_helpers(&h->wrap, need, code, kind.kernel, plan.dim, who,
-                        "wrap");
-  const int64_t cells = cells_of(h->t.p, plan.dim);
+                        "wrap", batch > 0);
+  // (a batched handle: every array [batch, P...])
+  const int64_t cells = cells_of(h->t.p, plan.dim) * h->items();
   h->pad_in.resize(nin);
   h->pad_out.resize(nout);
   h->pong.resize(iterates ? nout : 0);
@@ -839,6 +904,7 @@ int run_chunks(soda_hip_periodic* h, void* const* outputs,
       [&](void* const* dst, const void* const* src, int32_t n,
           bool last) -> int {
         RunRequest rq = {dst, src, h->t.p, n, stream};
+        rq.batch = h->items();
         ResidualRun riding;
         if (res && last && !res->behind) {
           riding = res->run;
@@ -961,12 +1027,12 @@ Domain domain_of(soda_hip_border_fused* f) { return {f->main, f}; }
 // -- the run cores ------------------------------------------------------------
 
 // The device entry contract (include/soda_hip.h, soda_hip_run_device) on the
-// caller's arrays, each the dense array of `extent`: no output shares a byte
-// with an input, a param array or another output; inputs and outputs are
-// aligned to min(16, vec x cell size) bytes.
+// caller's arrays, each the dense array of `batch` items of `extent`: no output
+// shares a byte with an input, a param array or another output; inputs and
+// outputs are aligned to min(16, vec x cell size) bytes.
 int check_contract(const soda_hip_plan_t& plan, void* const* outputs,
                    const void* const* inputs, const int32_t* extent,
-                   const char* who_) {
+                   int32_t batch, const char* who_) {
   const std::string who(who_);
   const int nin = plan.num_inputs, nout = plan.num_outputs;
   const int prm0 = nin + nout + plan.num_locals;
@@ -974,7 +1040,7 @@ int check_contract(const soda_hip_plan_t& plan, void* const* outputs,
     if (!inputs[i]) return fail(SODA_HIP_ERR_INVALID, who + ": NULL input");
   for (int o = 0; o < nout; ++o)
     if (!outputs[o]) return fail(SODA_HIP_ERR_INVALID, who + ": NULL output");
-  const uint64_t cells = (uint64_t)cells_of(extent, plan.dim);
+  const uint64_t cells = (uint64_t)cells_of(extent, plan.dim) * batch;
   auto overlap = [](const void* a, uint64_t na, const void* b, uint64_t nb) {
     const uintptr_t a0 = reinterpret_cast<uintptr_t>(a);
     const uintptr_t b0 = reinterpret_cast<uintptr_t>(b);
@@ -1047,7 +1113,7 @@ int run_padded_core(const Domain& dom, void* const* outputs,
                              who.c_str()))
     return rc;
   if (int rc = check_contract(h->prog->plan, outputs, inputs, h->t.p,
-                              who.c_str()))
+                              h->items(), who.c_str()))
     return rc;
   return dom.chunks(outputs, inputs, iterate, stream);
 }
@@ -1105,7 +1171,8 @@ int run_device_core(const Domain& dom, void* const* outputs,
   if (int rc = check_iterate(plan, h->not_iterable, iterate, who.c_str()))
     return rc;
   // the device entry contract on the caller's dense arrays of N
-  if (int rc = check_contract(plan, outputs, inputs, h->t.n, who.c_str()))
+  if (int rc = check_contract(plan, outputs, inputs, h->t.n, h->items(),
+                              who.c_str()))
     return rc;
   HIP_TRY(hipSetDevice(h->prog->device));
   hipStream_t stream = static_cast<hipStream_t>(stream_);
@@ -1114,6 +1181,15 @@ int run_device_core(const Domain& dom, void* const* outputs,
   if (int rc = dom.chunks(st.out.data(), st.src.data(), iterate, stream_))
     return rc;
   return st.crop(outputs, st.out.data(), stream);
+}
+
+// The residual of a batch is not served: the entries that
+// take one refuse a batched handle before anything else.
+int refuse_batched(const soda_hip_periodic* h, const std::string& who) {
+  if (!h->batch) return SODA_HIP_OK;
+  return fail(SODA_HIP_ERR_UNSUPPORTED,
+              who + ": residuals, norms and runs until converged are not "
+                    "served on a batched handle; nothing was launched");
 }
 
 // <handle>_run_padded_residual / _run_padded_norms (`norms` != nullptr):
@@ -1126,6 +1202,7 @@ int run_padded_residual_core(const Domain& dom, soda_hip_norms_handle* norms,
   const std::string who = std::string(h->kind->who) +
                           (norms ? "_run_padded_norms" : "_run_padded_residual");
   soda_hip_program* p = h->prog;
+  if (int rc = refuse_batched(h, who)) return rc;
   for (int o = 0; o < p->plan.num_outputs; ++o)
     if (!outputs[o]) return fail(SODA_HIP_ERR_INVALID, who + ": NULL output");
   if (int rc = norms ? check_norms_request(p, norms, outputs, h->t.p, dev,
@@ -1135,7 +1212,8 @@ int run_padded_residual_core(const Domain& dom, soda_hip_norms_handle* norms,
     return rc;
   if (int rc = check_iterate(p->plan, h->not_iterable, iterate, who.c_str()))
     return rc;
-  if (int rc = check_contract(p->plan, outputs, inputs, h->t.p, who.c_str()))
+  if (int rc = check_contract(p->plan, outputs, inputs, h->t.p, 1,
+                              who.c_str()))
     return rc;
   const ResidualRun run = {dev, 0, norms};
   return dom.chunks(outputs, inputs, iterate, stream, &run);
@@ -1160,6 +1238,7 @@ int run_until_core(const Domain& dom, soda_hip_norms_handle* norms,
   soda_hip_program* p = h->prog;
   const soda_hip_plan_t& plan = p->plan;
   const int nin = plan.num_inputs, nout = plan.num_outputs;
+  if (int rc = refuse_batched(h, who)) return rc;
   if (max_iterate < 1 || check_every < 1)
     return fail(SODA_HIP_ERR_INVALID,
                 who + ": max_iterate and check_every must be >= 1");
@@ -1172,7 +1251,7 @@ int run_until_core(const Domain& dom, soda_hip_norms_handle* norms,
     return rc;
   if (int rc = check_iterate(plan, h->not_iterable, max_iterate, who.c_str()))
     return rc;
-  if (int rc = check_contract(plan, outputs, inputs, h->t.n, who.c_str()))
+  if (int rc = check_contract(plan, outputs, inputs, h->t.n, 1, who.c_str()))
     return rc;
   HIP_TRY(hipSetDevice(p->device));
   hipStream_t stream = static_cast<hipStream_t>(stream_);
@@ -1276,6 +1355,73 @@ int soda_hip_periodic_create(soda_hip_program_t* p,
     return fail(SODA_HIP_ERR_INVALID, "periodic_create: NULL argument");
   return create_core(kTorus, p, desc, nullptr, nullptr, wrap_code,
                      wrap_code_size, handle);
+}
+
+// -- batched domains: the entries above over a batch --------
+
+int soda_hip_periodic_plan_batch(const soda_hip_plan_t* plan,
+                                 const soda_hip_periodic_desc_t* desc,
+                                 int32_t batch, int32_t iterate,
+                                 soda_hip_periodic_info_t* info,
+                                 int32_t capacity, int32_t* chunks,
+                                 int32_t* count) {
+  if (!plan || !desc)
+    return fail(SODA_HIP_ERR_INVALID, "periodic_plan_batch: NULL argument");
+  if (int rc = check_domain_batch(*plan, batch, "periodic_plan_batch"))
+    return rc;
+  return plan_core(kTorus, plan, desc, iterate, info, capacity, chunks, count,
+                   batch);
+}
+
+int soda_hip_periodic_create_batch(soda_hip_program_t* p,
+                                   const soda_hip_periodic_desc_t* desc,
+                                   int32_t batch,
+                                   const void* const* wrap_code,
+                                   const size_t* wrap_code_size,
+                                   soda_hip_periodic_t** handle) {
+  if (handle) *handle = nullptr;
+  if (!p || !desc || !wrap_code || !wrap_code_size || !handle)
+    return fail(SODA_HIP_ERR_INVALID, "periodic_create_batch: NULL argument");
+  if (int rc = check_domain_batch(p->plan, batch, "periodic_create_batch"))
+    return rc;
+  return create_core(kTorus, p, desc, nullptr, nullptr, wrap_code,
+                     wrap_code_size, handle, batch);
+}
+
+int soda_hip_border_plan_batch(const soda_hip_plan_t* plan,
+                               const soda_hip_border_desc_t* desc,
+                               int32_t batch, int32_t iterate,
+                               soda_hip_periodic_info_t* info,
+                               int32_t capacity, int32_t* chunks,
+                               int32_t* count) {
+  if (!plan || !desc)
+    return fail(SODA_HIP_ERR_INVALID, "border_plan_batch: NULL argument");
+  if (int rc = check_domain_batch(*plan, batch, "border_plan_batch"))
+    return rc;
+  bool all_wrap;
+  if (int rc = border_modes(plan, desc, &all_wrap)) return rc;
+  soda_hip_periodic_desc_t domain = desc->domain;
+  if (!all_wrap && domain.refill_every == 0) domain.refill_every = 1;
+  return plan_core(all_wrap ? kTorus : kBorder, plan, &domain, iterate, info,
+                   capacity, chunks, count, batch);
+}
+
+int soda_hip_border_create_batch(soda_hip_program_t* p,
+                                 const soda_hip_border_desc_t* desc,
+                                 int32_t batch, const void* const* code,
+                                 const size_t* code_size,
+                                 soda_hip_border_t** handle) {
+  if (handle) *handle = nullptr;
+  if (!p || !desc || !code || !code_size || !handle)
+    return fail(SODA_HIP_ERR_INVALID, "border_create_batch: NULL argument");
+  if (int rc = check_domain_batch(p->plan, batch, "border_create_batch"))
+    return rc;
+  bool all_wrap;
+  if (int rc = border_modes(&p->plan, desc, &all_wrap)) return rc;
+  soda_hip_periodic_desc_t domain = desc->domain;
+  if (!all_wrap && domain.refill_every == 0) domain.refill_every = 1;
+  return create_core(kBorder, p, &domain, desc->mode, desc->constant, code,
+                     code_size, handle, batch);
 }
 
 int soda_hip_periodic_destroy(soda_hip_periodic_t* h) {

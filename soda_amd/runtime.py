@@ -13,6 +13,7 @@ raises `util.BackendError`.
 import contextlib
 import ctypes
 import dataclasses
+import functools
 import hashlib
 import os
 import sys
@@ -428,6 +429,22 @@ API = {
     'soda_hip_border_info': (ctypes.c_int, [_vp,
                                             ctypes.POINTER(PeriodicInfo)]),
     'soda_hip_border_fill': (ctypes.c_int, [_vp, _pvp, _i32, _vp]),
+    'soda_hip_periodic_plan_batch': (ctypes.c_int, [
+        ctypes.POINTER(Plan), ctypes.POINTER(PeriodicDesc), _i32, _i32,
+        ctypes.POINTER(PeriodicInfo), _i32, _pi32, _pi32
+    ]),
+    'soda_hip_periodic_create_batch': (ctypes.c_int, [
+        _vp, ctypes.POINTER(PeriodicDesc), _i32, _pvp,
+        ctypes.POINTER(ctypes.c_size_t), _pvp
+    ]),
+    'soda_hip_border_plan_batch': (ctypes.c_int, [
+        ctypes.POINTER(Plan), ctypes.POINTER(BorderDesc), _i32, _i32,
+        ctypes.POINTER(PeriodicInfo), _i32, _pi32, _pi32
+    ]),
+    'soda_hip_border_create_batch': (ctypes.c_int, [
+        _vp, ctypes.POINTER(BorderDesc), _i32, _pvp,
+        ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(_vp)
+    ]),
     'soda_hip_box_host': (ctypes.c_int, [_vp, _pi32, _vp, _pi32, _i32, _i32,
                                          _i32, _pi32, _pi32, _pi32]),
     'soda_hip_border_fused_plan': (ctypes.c_int, [
@@ -1491,45 +1508,57 @@ def _periodic_info(raw: PeriodicInfo, dim: int) -> dict:
 def periodic_plan(plan: Plan, extent: Sequence[int], refill_every: int,
                   ghost_lo: Sequence[int], ghost_hi: Sequence[int],
                   iterate: int = 0, preserve: bool = False,
-                  not_iterable: bool = False):
+                  not_iterable: bool = False, batch: Optional[int] = None):
   """(info, chunks) a periodic handle over `plan` would use for a torus of
   `extent` (soda_hip_periodic_plan; no GPU needed): info as Periodic.info(),
   chunks the iterations of every chunk of a run of `iterate`.  Refuses what
-  the handle refuses (BackendError)."""
+  the handle refuses (BackendError).  `batch` = N: of a batched handle over N
+  tori (soda_hip_periodic_plan_batch)."""
   desc = _periodic_desc(plan.dim, extent, refill_every, ghost_lo, ghost_hi,
                         preserve, not_iterable)
   raw, chunks = _plan_call('periodic_plan', plan, desc, PeriodicInfo(),
-                           iterate)
+                           iterate, batch)
   return _periodic_info(raw, plan.dim), chunks
 
 
-def _plan_call(what: str, plan: Plan, desc, raw, iterate: int):
-  """The plan entry soda_hip_<what> on `desc`: (`raw`, the info struct, filled;
-  the iterations of every chunk of a run of `iterate`)."""
+def _plan_call(what: str, plan: Plan, desc, raw, iterate: int,
+               batch: Optional[int] = None):
+  """The plan entry soda_hip_<what> on `desc` -- `batch` an integer:
+  soda_hip_<what>_batch -- : (`raw`, the info struct, filled; the iterations
+  of every chunk of a run of `iterate`)."""
   cap = max(1, iterate)
   chunks = (ctypes.c_int32 * cap)()
   n = ctypes.c_int32()
-  check(getattr(library(), 'soda_hip_' + what)(
-      ctypes.byref(plan), ctypes.byref(desc), iterate, ctypes.byref(raw), cap,
-      chunks, ctypes.byref(n)), what)
+  if batch is not None:
+    what += '_batch'
+  fn = getattr(library(), 'soda_hip_' + what)
+  head = (ctypes.byref(plan), ctypes.byref(desc)) + (
+      () if batch is None else (int(batch),))
+  check(fn(*head, iterate, ctypes.byref(raw), cap, chunks, ctypes.byref(n)),
+        what)
   return raw, list(chunks[:n.value])
 
 
-def _helper_resources(module, stem: str, elem: int, dim: int):
+def _helper_resources(module, stem: str, elem: int, dim: int,
+                      batch: bool = False):
   """(code object, kernel_resources of it) of a helper module (wrap, extend,
   box) of a cell size and dimension count: `module`.source is its text,
-  `stem` names its file."""
-  code = compile_source(module.source(elem, dim),
-                        '%s_e%d_%dd.hip' % (stem, elem, dim))
+  `stem` names its file.  `batch`: the batched module (wrap, extend)."""
+  if batch:
+    code = compile_source(module.source(elem, dim, batch=True),
+                          '%s_bt_e%d_%dd.hip' % (stem, elem, dim))
+  else:
+    code = compile_source(module.source(elem, dim),
+                          '%s_e%d_%dd.hip' % (stem, elem, dim))
   return code, kernel_resources(code)
 
 
-def wrap_resources(elem: int, dim: int):
+def wrap_resources(elem: int, dim: int, batch: bool = False):
   """(code object, kernel_resources of it) of the wrap module of a cell size
-  and dimension count: JIT-built like every module, cached like them; needs
-  no GPU."""
+  and dimension count -- `batch`: of the batched one --
+  JIT-built like every module, cached like them; needs no GPU."""
   from soda_amd.codegen.hip import wrap as _wrap
-  return _helper_resources(_wrap, 'wrap', elem, dim)
+  return _helper_resources(_wrap, 'wrap', elem, dim, batch)
 
 
 class Periodic:
@@ -1567,12 +1596,15 @@ class Periodic:
       args += [codes, sizes]
     return args
 
-  def _begin(self, prog: 'Program', extent: Sequence[int], modes=None) -> bool:
+  def _begin(self, prog: 'Program', extent: Sequence[int], modes=None,
+             batch: Optional[int] = None) -> bool:
     """What every constructor starts with: the extent checked and kept, the
-    `modes` of a bordered domain kept one name per dimension.  Returns the
+    `modes` of a bordered domain kept one name per dimension, `batch` (None:
+    an unbatched handle; N: one over N domains).  Returns the
     `not_iterable` of the desc."""
     st = prog.stencil
     self.prog, self.extent = prog, tuple(int(e) for e in extent)
+    self.batch = None if batch is None else int(batch)
     prog._check_extent(self.extent)
     if modes is not None:
       self.modes = tuple([modes] * st.dim if isinstance(modes, str) else modes)
@@ -1582,22 +1614,32 @@ class Periodic:
     """What every constructor ends with: the handle made by the library's
     create entry from `desc` and the code objects of `resources`, and
     registered with its program.  `where`: the domain, for a refusal."""
-    args = self._codes_of(*resources)
     self._lib = library()
     self._handle = ctypes.c_void_p()
-    check(self._fn('create')(self.prog._handle, ctypes.byref(desc), *args,
-                             ctypes.byref(self._handle)),
-          '`%s` on %s' % (self.prog.stencil.app_name, where))
+    if self.batch is None:
+      args = self._codes_of(*resources)
+      status = self._fn('create')(self.prog._handle, ctypes.byref(desc), *args,
+                                  ctypes.byref(self._handle))
+    else:                           # the batched modules, the _batch entry
+      args = self._codes_of(*[functools.partial(r, batch=True)
+                              for r in resources])
+      status = self._fn('create_batch')(
+          self.prog._handle, ctypes.byref(desc), self.batch, *args,
+          ctypes.byref(self._handle))
+      where = '%d x %s' % (self.batch, where)
+    check(status, '`%s` on %s' % (self.prog.stencil.app_name, where))
     self.prog._periodic.append(self)
 
   def __init__(self, prog: 'Program', extent: Sequence[int],
                refill_every: Optional[int] = None,
-               ghosts: Optional[Sequence[Sequence[int]]] = None):
+               ghosts: Optional[Sequence[Sequence[int]]] = None,
+               batch: Optional[int] = None):
     """`refill_every`: iterations between two refills (default: the deepest
     fusion depth of the program, so that a chunk is one launch).  `ghosts` =
     (lo, hi): the frame, for callers that size it themselves (default:
-    periodic_ghosts)."""
-    not_iterable = self._begin(prog, extent)
+    periodic_ghosts).  `batch` = N: a handle over N tori of `extent`, every
+    array [N, ...] (soda_hip_periodic_create_batch)."""
+    not_iterable = self._begin(prog, extent, batch=batch)
     st = prog.stencil
     k = int(refill_every or 0)
     if k < 0:
@@ -1816,17 +1858,20 @@ def _border_desc(domain: PeriodicDesc, modes,
 def border_plan(plan: Plan, extent: Sequence[int], modes,
                 ghost_lo: Sequence[int], ghost_hi: Sequence[int],
                 iterate: int = 0, refill_every: int = 0,
-                preserve: bool = False, not_iterable: bool = False):
+                preserve: bool = False, not_iterable: bool = False,
+                batch: Optional[int] = None):
   """periodic_plan for a bordered domain (soda_hip_border_plan; no GPU
   needed): (info, chunks).  `modes`: names, or raw SODA_HIP_BORDER_* numbers
   (which reach the library unchecked).  With a mode other than `wrap`,
   `refill_every` must be 0 or 1 and every chunk is one iteration; with all
-  `wrap` this is periodic_plan."""
+  `wrap` this is periodic_plan.  `batch` = N: of a batched handle over N
+  domains (soda_hip_border_plan_batch)."""
   raw_modes = _raw_modes(modes, plan.dim)
   desc = _border_desc(_periodic_desc(
       plan.dim, extent, refill_every, ghost_lo, ghost_hi, preserve,
       not_iterable), raw_modes, ())
-  raw, chunks = _plan_call('border_plan', plan, desc, PeriodicInfo(), iterate)
+  raw, chunks = _plan_call('border_plan', plan, desc, PeriodicInfo(), iterate,
+                           batch)
   return _periodic_info(raw, plan.dim), chunks
 
 
@@ -1842,12 +1887,12 @@ def _raw_modes(modes, dim: int, *reaches):
   return raw
 
 
-def extend_resources(elem: int, dim: int):
+def extend_resources(elem: int, dim: int, batch: bool = False):
   """(code object, kernel_resources of it) of the extend module of a cell size
-  and dimension count: JIT-built like every module, cached like them; needs
-  no GPU."""
+  and dimension count -- `batch`: of the batched one --
+  JIT-built like every module, cached like them; needs no GPU."""
   from soda_amd.codegen.hip import extend as _extend
-  return _helper_resources(_extend, 'extend', elem, dim)
+  return _helper_resources(_extend, 'extend', elem, dim, batch)
 
 
 class Bordered(Periodic):
@@ -1861,12 +1906,14 @@ class Bordered(Periodic):
   _what = 'border'
 
   def __init__(self, prog: 'Program', extent: Sequence[int], modes,
-               constants=None):
+               constants=None, batch: Optional[int] = None):
     """`modes`: one name for all dimensions or one per dimension, dimension 0
     first, of wrap / clamp / mirror / mirror101 / constant.  `constants`: a
     scalar or {input: scalar}, converted to the cell type's bits (default
-    zero); an output's ghost takes the constant of the input it replaces."""
-    not_iterable = self._begin(prog, extent, modes)
+    zero); an output's ghost takes the constant of the input it replaces.
+    `batch` = N: a handle over N domains of `extent`, every array [N, ...]
+    (soda_hip_border_create_batch)."""
+    not_iterable = self._begin(prog, extent, modes, batch)
     st = prog.stencil
     raw_modes = _border_modes(modes, st.dim)
     k = 1
@@ -2568,10 +2615,13 @@ class Program:
   # -- periodic domains ------------------------------------------------------
   def periodic(self, extent: Sequence[int],
                refill_every: Optional[int] = None,
-               ghosts: Optional[Sequence[Sequence[int]]] = None) -> Periodic:
-    """This program on a torus of `extent` (runtime.Periodic).
-    The handle is closed with the program at the latest."""
-    return Periodic(self, extent, refill_every, ghosts)
+               ghosts: Optional[Sequence[Sequence[int]]] = None,
+               batch: Optional[int] = None) -> Periodic:
+    """This program on a torus of `extent` (runtime.Periodic)
+    -- `batch` = N: on N tori at once, every array [N, ...] (DESIGN.md 4.15;
+    needs a program built with LowerOptions.batch).  The handle is closed
+    with the program at the latest."""
+    return Periodic(self, extent, refill_every, ghosts, batch)
 
   def run_periodic(self, inputs: Dict[str, 'numpy.ndarray'],
                    iterate: Optional[int] = None,
@@ -2585,15 +2635,21 @@ class Program:
 
   # -- bordered domains ------------------------------------------------------
   def bordered(self, extent: Sequence[int], modes, constants=None,
-               depth: int = 1) -> Bordered:
+               depth: int = 1, batch: Optional[int] = None) -> Bordered:
     """This program on a domain of `extent` with a border mode per dimension
     (runtime.Bordered).  `depth` other than 1: fused away from
     the walls in chunks of `depth` iterations, 0 for the program's deepest
     (runtime.BorderedFused) -- the same bits, faster where the
-    program fuses deep.  The handle is closed with the program
-    at the latest."""
+    program fuses deep.  `batch` = N: on N domains at once, every array
+    [N, ...] (DESIGN.md 4.15; needs a program built with LowerOptions.batch;
+    the fused form has no batch: with `depth` other than 1 the library's
+    refusal of a batched plan is raised).  The handle is closed with the
+    program at the latest."""
     if depth == 1:
-      return Bordered(self, extent, modes, constants)
+      return Bordered(self, extent, modes, constants, batch)
+    if batch is not None and not self.plan.batched:
+      raise util.InputError('bordered: `batch` needs a program built with '
+                            'LowerOptions.batch')
     return BorderedFused(self, extent, modes, constants, depth)
 
   def run_bordered(self, inputs: Dict[str, 'numpy.ndarray'], modes,
@@ -2706,6 +2762,53 @@ class Program:
       self.run_device(dev_out, dev_in, extent, iterate, batch=batch)
       _copy_out(lib, dense, dev_out, 'run_batch')
     return _valid_boxes(st, extent, iterate, dense, batched=True)
+
+  # -- batched domains ---------------------------------------
+  def run_periodic_batch(self, inputs: Dict[str, 'numpy.ndarray'],
+                         iterate: Optional[int] = None,
+                         refill_every: Optional[int] = None
+                         ) -> Dict[str, 'numpy.ndarray']:
+    """`run_periodic` on N independent tori in one launch per kernel: numpy
+    arrays of shape (N,) + extent reversed in, the same out, EVERY cell of
+    every item defined; params as in `run`, shared by all items.  Needs a
+    program built with LowerOptions.batch."""
+    return self._run_domain_batch(
+        lambda extent, n: self.periodic(extent, refill_every, batch=n),
+        'run_periodic_batch', inputs, iterate)
+
+  def run_bordered_batch(self, inputs: Dict[str, 'numpy.ndarray'], modes,
+                         constants=None, iterate: Optional[int] = None
+                         ) -> Dict[str, 'numpy.ndarray']:
+    """`run_bordered` on N independent domains in one launch per kernel: numpy
+    arrays of shape (N,) + extent reversed in, the same out, EVERY cell of
+    every item defined -- each item extended by `modes` and `constants` on its
+    own.  Needs a program built with LowerOptions.batch."""
+    return self._run_domain_batch(
+        lambda extent, n: self.bordered(extent, modes, constants, batch=n),
+        'run_bordered_batch', inputs, iterate)
+
+  def _run_domain_batch(self, handle_of, what, inputs, iterate):
+    """run_batch's numpy plumbing around `handle_of(extent, N)`.run_device; the
+    handle is made once the inputs are checked, and closed here."""
+    import numpy as np
+    st = self.stencil
+    lib = self._lib
+    iterate = st.iterate if iterate is None else iterate
+    first = np.asarray(inputs[st.input_names[0]])
+    if first.ndim != st.dim + 1 or first.shape[0] < 1:
+      raise util.InputError('%s: arrays of shape (N,) + extent[::-1]' % what)
+    extent = tuple(first.shape[:0:-1])
+    self._check_extent(extent)
+    host_in = _host_inputs(st, inputs, first.shape)
+    result = {n: np.empty(first.shape, dtype=np.dtype(t.np_name))
+              for n, t in zip(st.output_names, st.output_types)}
+    dense = list(result.values())
+    with handle_of(extent, int(first.shape[0])) as dom, \
+        _staged(lib, self.device, host_in, dense, what,
+                synchronize=True) as (dev_in, dev_out):
+      dom.run_device(dev_out, dev_in, iterate)
+      _copy_out(lib, dense, dev_out, what)
+    return result
 
 
 def _host_param(st, inputs, pstmt):
