@@ -27,6 +27,14 @@ contiguous taps, several stages), `rich` (select over comparisons and logic,
 unary minus, casts, float division, %, &, |, ^, 64-bit detours, abs).  Only
 constructs whose C++ meaning does not depend on a library overload choice are
 generated (min / max of equal types; sqrt only as a whole float statement).
+
+Domains (tests/test_fuzz_domains.py).  `run_torus` is a
+nest of its own in which every index is taken modulo N -- no frame, no boxes,
+no margins; `run_bordered` extends every input in every iteration by the closed
+forms of the border modes, restated here (`mode_index`, `extend`), over a
+margin counted from the tree, runs the one-iteration nest on that open box and
+cuts the domain out; `reach` is what the tree's own boxes say k iterations
+look at.  None of them takes a number from the product.
 """
 import ctypes
 import hashlib
@@ -272,8 +280,9 @@ class Program:
     return '\n'.join(lines) + '\n'
 
   # ---- boxes from the tap lists ---------------------------------------------
-  def margins(self):
-    """[(iteration, stmt, lo, margin)] in execution order: the nest of a
+  def margins(self, iterate=None):
+    """[(iteration, stmt, lo, margin)] in execution order (of `iterate`
+    iterations; default: the program's own count): the nest of a
     tensor runs over [lo, N - margin) per dimension -- the cells for which
     EVERY load, at every level down to the program inputs, lies inside the
     grid.  By interval propagation: an input is defined on the whole grid; a
@@ -290,7 +299,7 @@ class Program:
     zero = tuple([0] * dim)
     box = {n: (zero, zero) for n, _ in self.inputs}     # name -> (lo, margin)
     order = []
-    for k in range(self.iterate):
+    for k in range(self.iterate if iterate is None else iterate):
       for s in self.stmts:
         lo, margin = [0] * dim, [0] * dim
         for r in s.refs():
@@ -424,6 +433,213 @@ class Program:
     if lib.nest(c_ins, c_outs, n) != 0:
       raise MemoryError('nest: calloc failed')
     return {s.name: a for s, a in zip(self.outputs, outs)}
+
+  # ---- domains: every cell of every output defined ---------------------------
+  def iterable(self):
+    """Outputs can become inputs by position: as many, of the same types."""
+    return [t for _, t in self.inputs] == [s.typ for s in self.outputs]
+
+  def _paired_inputs(self, ins):
+    return {s.name: np.array(ins[i], copy=True)
+            for (i, _), s in zip(self.inputs, self.outputs)}
+
+  def reach(self, k=1):
+    """(lo, hi) per dimension: the most `margins()` of `k` iterations gives
+    below and above over all outputs -- how far k iterations of this tree
+    look, by this file's own boxes."""
+    last = [(lo, margin) for it, s, lo, margin in self.margins(k)
+            if it == k - 1 and s.kind == 'output']
+    return ([max(lo[d] for lo, _ in last) for d in range(self.dim)],
+            [max(m[d] for _, m in last) for d in range(self.dim)])
+
+  def torus_text(self):
+    """The nest of a torus: no frame, no boxes, no margins.  In every
+    iteration and for every statement in file order ALL cells are computed; a
+    load at cell x reads the cell ((x + load index - store index) mod N) of
+    every dimension, the modulo the mathematical one, in int64; locals are
+    whole periodic arrays; outputs become inputs by position."""
+    dim = self.dim
+    out = ['#include <algorithm>', '#include <cmath>', '#include <cstdint>',
+           '#include <cstdlib>', '#include <cstring>', '',
+           'static inline int64_t wrapped(int64_t i, int64_t n) {',
+           '  return ((i % n) + n) % n;', '}', '',
+           'extern "C" int torus(const void* const* ins, void* const* outs, '
+           'const int64_t* N, int64_t iterate) {']
+    out.append('  const int64_t cells = %s;' %
+               ' * '.join('N[%d]' % d for d in range(dim)))
+    arrays = [(n, t) for n, t in self.inputs] + \
+        [(s.name, s.typ) for s in self.stmts]
+    for n, t in arrays:
+      out.append('  %s* %s = (%s*)calloc(cells, sizeof(%s));' %
+                 (CTYPES[t], n, CTYPES[t], CTYPES[t]))
+      out.append('  if (!%s) return 1;' % n)
+    for i, (n, t) in enumerate(self.inputs):
+      out.append('  memcpy(%s, ins[%d], cells * sizeof(%s));' %
+                 (n, i, CTYPES[t]))
+    out.append('  for (int64_t it = 0; it < iterate; ++it) {')
+    for s in self.stmts:
+      pad = '    '
+      for d in reversed(range(dim)):
+        out.append('%sfor (int64_t x%d = 0; x%d < N[%d]; ++x%d) {' %
+                   (pad, d, d, d, d))
+        pad += '  '
+
+      def load(r, _s=s):
+        idx = None
+        for d in reversed(range(dim)):
+          term = 'wrapped(x%d + (%d), N[%d])' % (d, r.idx[d] - _s.store[d], d)
+          idx = term if idx is None else '(%s + N[%d] * %s)' % (term, d, idx)
+        return '%s[%s]' % (r.name, idx)
+
+      for lt, ln, le in s.lets:
+        out.append('%sconst %s %s = (%s)(%s);' %
+                   (pad, CTYPES[lt], ln, CTYPES[lt], le.cpp(load)))
+      here = None
+      for d in reversed(range(dim)):
+        here = 'x%d' % d if here is None else '(x%d + N[%d] * %s)' % (d, d, here)
+      out.append('%s%s[%s] = (%s)(%s);' %
+                 (pad, s.name, here, CTYPES[s.typ], s.expr.cpp(load)))
+      for d in range(dim):
+        pad = pad[:-2]
+        out.append('%s}' % pad)
+    if self.iterable():
+      out.append('    if (it + 1 < iterate) {')
+      for (n, t), o in zip(self.inputs, self.outputs):
+        out.append('      memcpy(%s, %s, cells * sizeof(%s));' %
+                   (n, o.name, CTYPES[t]))
+      out.append('    }')
+    out.append('  }')
+    for i, s in enumerate(self.outputs):
+      out.append('  memcpy(outs[%d], %s, cells * sizeof(%s));' %
+                 (i, s.name, CTYPES[s.typ]))
+    for n, _ in arrays:
+      out.append('  free((void*)%s);' % n)
+    out.append('  return 0;')
+    out.append('}')
+    return '\n'.join(out) + '\n'
+
+  def run_torus(self, inputs, extent, iterate=None, with_previous=False):
+    """{output: array of the torus} after `iterate` iterations (default: the
+    program's own count) by `torus_text`.  `with_previous`: (that, the outputs
+    after iterate - 1 iterations -- for iterate = 1 the paired inputs)."""
+    iterate = self.iterate if iterate is None else int(iterate)
+    assert iterate >= 1 and (iterate == 1 or self.iterable())
+    assert len(extent) == self.dim and all(n >= 1 for n in extent)
+    lib = _compile(self.torus_text())
+    shape = tuple(extent[::-1])
+    ins = [np.ascontiguousarray(inputs[n], dtype=NPTYPES[t])
+           for n, t in self.inputs]
+    assert all(a.shape == shape for a in ins)
+    c_ins = (ctypes.c_void_p * len(ins))(*[a.ctypes.data for a in ins])
+    n = (ctypes.c_int64 * self.dim)(*extent)
+    lib.torus.restype = ctypes.c_int
+    lib.torus.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                          ctypes.c_int64]
+
+    def after(k):
+      outs = [np.empty(shape, dtype=NPTYPES[s.typ]) for s in self.outputs]
+      c_outs = (ctypes.c_void_p * len(outs))(*[a.ctypes.data for a in outs])
+      if lib.torus(c_ins, c_outs, n, k) != 0:
+        raise MemoryError('torus nest: calloc failed')
+      return {s.name: a for s, a in zip(self.outputs, outs)}
+
+    cur = after(iterate)
+    if not with_previous:
+      return cur
+    return cur, (after(iterate - 1) if iterate > 1 else
+                 self._paired_inputs(inputs))
+
+  def pad_margin(self):
+    """Per dimension, the sum over statements of the largest |load index -
+    store index|: at least what one iteration reaches on either side, whatever
+    the chain of locals."""
+    return [sum(max(abs(r.idx[d] - s.store[d]) for r in s.refs())
+                for s in self.stmts) for d in range(self.dim)]
+
+  def run_bordered(self, inputs, extent, modes, constants, iterate=None,
+                   with_previous=False):
+    """{output: array of the domain} after `iterate` bordered iterations
+    (default: the program's own count).  In EVERY iteration each input is
+    extended by `extend` (mode per dimension, dimension 0 first; `constants`:
+    {input: scalar}) over `pad_margin()` on either side; the one-iteration
+    nest runs on that enlarged open box -- locals are NOT extended, they are
+    computed wherever the extended inputs allow --; the domain is cut out;
+    outputs become inputs by position.  `with_previous`: as `run_torus`."""
+    iterate = self.iterate if iterate is None else int(iterate)
+    assert iterate >= 1 and (iterate == 1 or self.iterable())
+    modes = [modes] * self.dim if isinstance(modes, str) else list(modes)
+    assert len(modes) == self.dim and len(extent) == self.dim
+    m = self.pad_margin()
+    big = tuple(n + 2 * w for n, w in zip(extent, m))
+    one = Program(self.name, self.dim, 1, self.inputs, self.stmts)
+    for s in one.outputs:          # the nest's own box holds the domain
+      lo, hi = one.valid_box(big, s.name)
+      assert all(l <= w and w + n <= h
+                 for l, h, w, n in zip(lo, hi, m, extent)), (s.name, lo, hi, m)
+    cut = tuple(slice(w, w + n) for w, n in zip(m[::-1], extent[::-1]))
+    state = {n: np.ascontiguousarray(inputs[n], dtype=NPTYPES[t])
+             for n, t in self.inputs}
+    cur = prev = None
+    for it in range(iterate):
+      if it == iterate - 1:
+        prev = cur if it else self._paired_inputs(state)
+      padded = {n: extend(state[n], m, m, modes, constants[n])
+                for n, _ in self.inputs}
+      whole = one.run(padded, big)
+      cur = {o: np.ascontiguousarray(a[cut]) for o, a in whole.items()}
+      if it + 1 < iterate:
+        state = {n: cur[o.name]
+                 for (n, _), o in zip(self.inputs, self.outputs)}
+    return (cur, prev) if with_previous else cur
+
+
+# border modes, dimension by dimension (restated here in integer arithmetic:
+# this file shares no line with the product or with tests/borders.py)
+MODES = ('clamp', 'constant', 'mirror', 'mirror101', 'wrap')
+
+
+def mode_index(mode, n, lo, hi):
+  """For j = -lo .. n + hi - 1 the cell of [0, n) that position j of the
+  extended axis takes; -1: none (`constant`, outside).  int64 throughout; `%`
+  on numpy integers is the mathematical modulo."""
+  j = np.arange(-int(lo), int(n) + int(hi), dtype=np.int64)
+  n = np.int64(n)
+  if mode == 'wrap':
+    return j % n
+  if mode == 'clamp':
+    return np.minimum(np.maximum(j, 0), n - 1)
+  if mode == 'mirror':
+    t = j % (2 * n)
+    return np.where(t < n, t, 2 * n - 1 - t)
+  if mode == 'mirror101':
+    if n == 1:
+      return np.zeros_like(j)
+    t = j % (2 * n - 2)
+    return np.where(t < n, t, 2 * n - 2 - t)
+  if mode == 'constant':
+    return np.where((j < 0) | (j >= n), np.int64(-1), j)
+  raise ValueError(mode)
+
+
+def extend(arr, lo, hi, modes, constant):
+  """`arr` (shaped extent[::-1]) extended by lo / hi cells per dimension
+  (dimension 0, the LAST axis, first): a cell outside in ANY `constant`
+  dimension takes `constant`, every other cell the interior cell the maps of
+  all dimensions give at once."""
+  dim = arr.ndim
+  out = arr
+  outside = np.zeros((), bool)
+  for d in range(dim):
+    axis = dim - 1 - d
+    idx = mode_index(modes[d], arr.shape[axis], lo[d], hi[d])
+    out = np.take(out, np.maximum(idx, 0), axis=axis)
+    shape = [1] * dim
+    shape[axis] = len(idx)
+    outside = outside | (idx < 0).reshape(shape)
+  out = np.array(out, copy=True)
+  out[np.broadcast_to(outside, out.shape)] = np.array(constant).astype(
+      arr.dtype)
+  return np.ascontiguousarray(out)
 
 
 _BUILD_DIR = None

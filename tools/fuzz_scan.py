@@ -7,7 +7,9 @@ bit; `group`: the same programs cut into virtual slabs (group_scan).
 `wire`: behind the reference host's stream format (wire_scan).
 `deep`: 8-26 iterations at fusion depths up to 13 (deep_scan).
 `ranks`: thread-ranks with the overlapped exchange under skew (ranks_scan).
-Usage: python tools/fuzz_scan.py window|generic|rich|group|options|wire|deep|ranks|wide FIRST LAST"""
+`domains`: tori and bordered domains, depth 1 and fused, against the
+independent nests (domains_scan).
+Usage: python tools/fuzz_scan.py window|generic|rich|group|options|wire|deep|ranks|wide|domains FIRST LAST"""
 import os
 import sys
 import time
@@ -566,7 +568,84 @@ def deep_scan(first, last):
   return 1 if failed else 0
 
 
+def domains_scan(first, last):
+  """Random programs on tori and bordered domains (tests/test_fuzz_domains.py
+  parts A - C on seeds of any range, its shapes, modes and constants): the
+  torus at the default refill interval and at 1, walls at depth 1 under a mode
+  per dimension and with `wrap` mixed in, walls fused at depth 0 with every
+  wall dimension exactly L + H wide -- against the independent nests of
+  tests/fuzz_nest.py, bit for bit.  A refusal is printed and counted; an error
+  that is no refusal ends the scan."""
+  import fuzz_nest
+  import test_fuzz_domains as cases
+  from soda_amd import core, runtime, util
+  ran = failed = refused = 0
+  t0 = time.time()
+
+  def compare(what, text, got, want):
+    bad = [o for o in want if not cases._same(got[o], want[o])]
+    if bad:
+      print('%s: outputs %s differ\n%s' % (what, bad, text), flush=True)
+    return 1 if bad else 0
+
+  for seed in range(first, last):
+    for family in cases.FAMILIES:
+      prog, _ = fuzz_nest.program(seed, family)
+      text = prog.soda_text()
+      stencil = core.from_text(text)
+      dim = prog.dim
+      extent = cases._gpu_extent(seed, family, dim)
+      ins = fuzz_nest.inputs_for(prog, extent, seed)
+      cst = cases._constants(prog)
+      what = 'seed %d %s extent %s' % (seed, family, extent)
+      try:
+        with runtime.Program(stencil, cases._opts(fuse=(2,))) as hip:
+          want = prog.run_torus(ins, extent)
+          for k in (None, 1):
+            failed += compare('%s torus, refill every %s' % (what, k), text,
+                              hip.run_periodic(ins, refill_every=k), want)
+          for modes in (cases._modes(seed, family, dim),
+                        cases._mixed(seed, family, dim)):
+            failed += compare('%s walls %s' % (what, modes), text,
+                              hip.run_bordered(ins, modes, cst),
+                              prog.run_bordered(ins, extent, modes, cst))
+          if prog.iterable() and prog.iterate >= 2:
+            deepest = max(p.fused_iters for p in hip.module.passes)
+            found = cases._fused_geometry(stencil, hip.plan, seed, family,
+                                          deepest, cases.GPU_CELLS)
+            if found is None:
+              refused += 1
+            else:
+              modes, wide, _ = found
+              wins = fuzz_nest.inputs_for(prog, wide, seed)
+              n = 2 * deepest - 1 if seed % 2 else deepest + 1
+              with hip.bordered(wide, modes, cst, depth=0) as handle:
+                got = cases._dense(hip, handle, wins, n)
+              failed += compare(
+                  'seed %d %s fused %d deep, %s %s, %d iterations' % (
+                      seed, family, deepest, wide, modes, n), text, got,
+                  prog.run_bordered(wins, wide, modes, cst, iterate=n))
+      except util.SodaError as e:
+        print('%s: %s: %s\n%s' % (what, type(e).__name__, str(e)[:300], text),
+              flush=True)
+        if not any(w in str(e) for w in ('unsupported', 'invalid', 'cannot',
+                                         'not served')):
+          print('domains: no refusal; the scan ends here', flush=True)
+          return 2
+        refused += 1
+        continue
+      ran += 1
+      if ran % 25 == 0:
+        print('... %d programs, %d failures, %d refused, %.0f s' %
+              (ran, failed, refused, time.time() - t0), flush=True)
+  print('domains seeds [%d, %d): %d programs run, %d refused, %d failures' %
+        (first, last, ran, refused, failed))
+  return 1 if failed else 0
+
+
 if __name__ == '__main__':
+  if sys.argv[1] == 'domains':
+    sys.exit(domains_scan(int(sys.argv[2]), int(sys.argv[3])))
   if sys.argv[1] == 'wide':
     sys.exit(wide_scan(int(sys.argv[2]), int(sys.argv[3])))
   if sys.argv[1] == 'ranks':
