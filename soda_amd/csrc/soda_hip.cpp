@@ -1290,6 +1290,19 @@ static bool scratch_grows(const soda_hip_program* p, bool need_locals,
   return false;
 }
 
+int program_grows(soda_hip_program* p, const int32_t* ext, int32_t iterate,
+                  bool* grows) {
+  int32_t count[SODA_HIP_MAX_PASSES];
+  if (int rc = soda_hip_program_schedule(p, ext, iterate, count)) return rc;
+  int32_t total = 0;
+  int64_t cells = 1;
+  for (int i = 0; i < p->plan.num_passes; ++i) total += count[i];
+  for (int d = 0; d < p->plan.dim; ++d) cells *= ext[d];
+  if (scratch_grows(p, locals_in_memory(p->plan, count), total, false, cells, 1))
+    *grows = true;
+  return SODA_HIP_OK;
+}
+
 // ---- a run, step by step (run_core below) -----------------------------------
 
 // The kernel arguments that hold for every launch of the run -- extent,
@@ -2592,624 +2605,6 @@ int soda_hip_program_scratch(soda_hip_program_t* p, int64_t* bytes,
   if (regrown) *regrown = 0;
   for (const auto* v : {&p->locals, &p->temps, &p->temps2, &p->until_tmp})
     add_scratch(*v, bytes, regrown);
-  return SODA_HIP_OK;
-}
-
-// -- wire format: <app>_kernel on banked streams -------------------------------
-
-struct soda_hip_stream {
-  soda_hip_stream_desc_t desc;
-  soda_hip_program* dense = nullptr;
-  std::vector<soda_hip_program*> linear, unwire, wire;
-  std::vector<DeviceBuffer> dense_in, dense_out;   // de-interleaved streams
-  std::vector<DeviceBuffer> host_banks;            // run_host staging
-  bool dense_failed = false;
-  int last_mode = 0;
-  // Device-resident banks narrower than this run the linear form even where
-  // the dense view exists: narrow tiles leave most of a 64-lane x V-wide
-  // marching strip idle (heat3d 32 x 32 tiles: 0.50 vs 0.79 ms).  Host banks
-  // take the dense view whenever there is one -- there the copies dominate and
-  // the dense view is what lets them overlap in bands.
-  int device_dense_min_tile0 = 256;
-  // The banked form of the dense program (soda_hip_stream_set_banked): one
-  // kernel that runs all `iterate` iterations and addresses the banks of the
-  // tensors marked in `in_kernel` itself -- to run_core a one-pass program of
-  // one iteration with every such bank a tensor of its own.  So it meets
-  // neither of run_core's one-shape-per-tensor assumptions: a stream run has
-  // no slab, hence no row-range offset, and iterate is 1 there.
-  soda_hip_program* banked = nullptr;
-  std::vector<int32_t> in_kernel;     // per tensor, inputs first
-  // Two-iteration programs (soda_hip_stream_set_banked_pair): the
-  // one-iteration kernel with the in_kernel INPUTS bank by bank, and with the
-  // in_kernel OUTPUTS bank by bank.  Where the dense program's schedule for
-  // the stream's extent is two one-iteration launches, these two run instead
-  // of `banked`, a dense temporary per output between them: the banked path
-  // then computes every cell of the dense view -- the array's border cells
-  // included, which a fused kernel and two launches do not agree on -- as the
-  // dense program does.
-  soda_hip_program* banked_first = nullptr;
-  soda_hip_program* banked_last = nullptr;
-  std::vector<DeviceBuffer> banked_tmp;
-  // (stream length, banked launches) of the device runs that went through:
-  // the staging arrays and the scratch of every program such a call runs are
-  // in place, a repeat allocates nothing and skips the look-ahead
-  // (stream_grows).  Emptied by whatever changes the path a length takes.
-  std::vector<std::pair<int32_t, int>> warm;
-};
-
-int soda_hip_stream_create(const soda_hip_stream_desc_t* desc,
-                           soda_hip_program_t* dense,
-                           soda_hip_program_t* const* linear,
-                           soda_hip_program_t* const* unwire,
-                           soda_hip_program_t* const* wire,
-                           soda_hip_stream_t** stream) {
-  if (!desc || !linear || !wire || !stream)
-    return fail(SODA_HIP_ERR_INVALID, "stream_create: NULL argument");
-  *stream = nullptr;
-  const int nt = desc->num_inputs + desc->num_outputs;
-  if (desc->dim < 1 || desc->dim > SODA_HIP_MAX_DIM || desc->num_inputs < 1 ||
-      desc->num_outputs < 1 || nt > SODA_HIP_MAX_TENSORS || desc->iterate < 1 ||
-      desc->num_linear < 1 || desc->num_linear > 4 ||
-      desc->linear_vec[desc->num_linear - 1] != 1)
-    return fail(SODA_HIP_ERR_INVALID, "stream_create: bad description");
-  for (int t = 0; t < nt; ++t)
-    if (desc->banks[t] < 1 || desc->elem_size[t] < 1 ||
-        desc->elems_per_cycle[t] < 1 || desc->shift[t] < 0)
-      return fail(SODA_HIP_ERR_INVALID, "stream_create: bad tensor entry");
-  for (int t = 1; t < nt; ++t)
-    if (desc->elems_per_cycle[t] != desc->elems_per_cycle[0])
-      return fail(SODA_HIP_ERR_UNSUPPORTED,
-                  "stream mode needs every tensor to move the same number of "
-                  "elements per cycle (burst width / element width x banks)");
-  for (int i = 0; i < desc->num_inputs; ++i)
-    if ((desc->banks[i] > 1 || desc->shift[i]) && (!unwire || !unwire[i]))
-      return fail(SODA_HIP_ERR_INVALID, "stream_create: missing unwire kernel");
-  for (int k = 0; k < desc->num_linear; ++k)
-    if (!linear[k]) return fail(SODA_HIP_ERR_INVALID, "stream_create: NULL linear");
-  // an output on one bank that the program stores at its wire position (shift
-  // 0) needs no copy kernel: the program writes the caller's bank
-  for (int o = 0; o < desc->num_outputs; ++o) {
-    const int t = desc->num_inputs + o;
-    if (!wire[o] && (desc->banks[t] > 1 || desc->shift[t]))
-      return fail(SODA_HIP_ERR_INVALID, "stream_create: missing wire kernel");
-  }
-  soda_hip_stream* s = new (std::nothrow) soda_hip_stream;
-  if (!s) return fail(SODA_HIP_ERR_NOMEM, "new stream");
-  s->desc = *desc;
-  s->dense = dense;
-  s->dense_failed = dense == nullptr;
-  s->linear.assign(linear, linear + desc->num_linear);
-  s->unwire.resize(desc->num_inputs, nullptr);
-  for (int i = 0; unwire && i < desc->num_inputs; ++i) s->unwire[i] = unwire[i];
-  s->wire.assign(wire, wire + desc->num_outputs);
-  for (soda_hip_program* c : s->unwire) if (c) c->bank_tensors = true;
-  for (soda_hip_program* c : s->wire) if (c) c->bank_tensors = true;
-  s->dense_in.resize(desc->num_inputs);
-  s->dense_out.resize(desc->num_outputs);
-  *stream = s;
-  return SODA_HIP_OK;
-}
-
-int soda_hip_stream_destroy(soda_hip_stream_t* s) {
-  if (!s) return SODA_HIP_OK;
-  for (auto* v : {&s->dense_in, &s->dense_out, &s->host_banks, &s->banked_tmp})
-    for (auto& b : *v)
-      if (b.ptr) (void)hipFree(b.ptr);
-  delete s;
-  return SODA_HIP_OK;
-}
-
-int soda_hip_stream_last_mode(soda_hip_stream_t* s) { return s ? s->last_mode : 0; }
-
-int soda_hip_stream_set_device_dense_min_tile(soda_hip_stream_t* s,
-                                              int32_t min_tile0) {
-  if (!s || min_tile0 < 0)
-    return fail(SODA_HIP_ERR_INVALID, "stream_set_device_dense_min_tile");
-  s->device_dense_min_tile0 = min_tile0;
-  s->warm.clear();
-  return SODA_HIP_OK;
-}
-
-int soda_hip_stream_set_banked(soda_hip_stream_t* s, soda_hip_program_t* program,
-                               const int32_t* in_kernel) {
-  if (!s) return fail(SODA_HIP_ERR_INVALID, "stream_set_banked: NULL stream");
-  s->warm.clear();
-  if (!program) {
-    s->banked = s->banked_first = s->banked_last = nullptr;
-    s->in_kernel.clear();
-    if (s->dense) s->dense->auto_calibrate = !getenv("SODA_HIP_NO_CALIBRATE");
-    return SODA_HIP_OK;
-  }
-  if (!in_kernel)
-    return fail(SODA_HIP_ERR_INVALID, "stream_set_banked: NULL mask");
-  const soda_hip_stream_desc_t& d = s->desc;
-  const soda_hip_plan_t& plan = program->plan;
-  int ins = 0, outs = 0;
-  bool any = false;
-  for (int t = 0; t < d.num_inputs + d.num_outputs; ++t) {
-    const bool input = t < d.num_inputs;
-    const int nb = d.banks[t];
-    if (in_kernel[t]) {
-      // fragments start on bank-group boundaries only if NB divides the tile
-      // row; a delay is undone by starting shift / NB elements into each bank
-      if ((nb != 2 && nb != 4) || d.tile[0] % nb || d.shift[t] % nb ||
-          (!input && d.shift[t]))
-        return fail(SODA_HIP_ERR_INVALID,
-                    "stream_set_banked: a tensor the program cannot address "
-                    "bank by bank");
-      any = true;
-    } else if (!input && !s->wire[t - d.num_inputs] && nb != 1) {
-      return fail(SODA_HIP_ERR_INVALID, "stream_set_banked: missing wire kernel");
-    }
-    (input ? ins : outs) += in_kernel[t] ? nb : 1;
-  }
-  if (!any || d.dim < 2 || plan.dim != d.dim || plan.num_inputs != ins ||
-      plan.num_outputs != outs || plan.num_passes != 1 ||
-      plan.passes[0].num_kernels != 1 ||
-      plan.kernels[plan.passes[0].kernel[0]].march_dim != plan.dim ||
-      ins + outs >= SODA_HIP_MAX_TENSORS)
-    return fail(SODA_HIP_ERR_INVALID,
-                "stream_set_banked: not the one-launch banked form of this "
-                "stream's program");
-  s->banked = program;
-  program->bank_tensors = true;
-  s->banked_first = s->banked_last = nullptr;
-  s->in_kernel.assign(in_kernel, in_kernel + d.num_inputs + d.num_outputs);
-  // one source for both paths of this stream: which launches a run takes is
-  // asked of the dense program's MODEL schedule (banked_launches), so the
-  // copy path of the same stream must not re-schedule from the clock
-  if (s->dense) s->dense->auto_calibrate = false;
-  return SODA_HIP_OK;
-}
-
-int soda_hip_stream_set_banked_pair(soda_hip_stream_t* s,
-                                    soda_hip_program_t* first,
-                                    soda_hip_program_t* last) {
-  if (!s || !s->banked)
-    return fail(SODA_HIP_ERR_INVALID,
-                "stream_set_banked_pair: no banked program is set");
-  s->warm.clear();
-  if (!first && !last) {
-    s->banked_first = s->banked_last = nullptr;
-    return SODA_HIP_OK;
-  }
-  const soda_hip_stream_desc_t& d = s->desc;
-  const soda_hip_plan_t& whole = s->banked->plan;
-  auto one_kernel = [&](const soda_hip_plan_t& plan) {
-    return plan.dim == d.dim && plan.num_passes == 1 &&
-           plan.passes[0].num_kernels == 1 &&
-           plan.kernels[plan.passes[0].kernel[0]].march_dim == plan.dim;
-  };
-  if (d.iterate != 2 || d.num_inputs != d.num_outputs || !first || !last ||
-      !one_kernel(first->plan) || !one_kernel(last->plan) ||
-      first->plan.num_inputs != whole.num_inputs ||
-      first->plan.num_outputs != d.num_outputs ||
-      last->plan.num_inputs != d.num_inputs ||
-      last->plan.num_outputs != whole.num_outputs)
-    return fail(SODA_HIP_ERR_INVALID,
-                "stream_set_banked_pair: not the two one-iteration launches of "
-                "this stream's two-iteration program");
-  for (int o = 0; o < d.num_outputs; ++o)
-    if (d.elem_size[o] != d.elem_size[d.num_inputs + o])
-      return fail(SODA_HIP_ERR_INVALID,
-                  "stream_set_banked_pair: input and output cell sizes differ");
-  s->banked_first = first;
-  s->banked_last = last;
-  first->bank_tensors = last->bank_tensors = true;
-  s->banked_tmp.resize(d.num_outputs);
-  return SODA_HIP_OK;
-}
-
-// Dense view: a stream of n elements is an array of extent (tile..., rows) iff
-// every tile starts on a row-block boundary -- a tile occupies
-// round_up(block * extent_last, epc) elements (frt/host.py:137-142), so for any
-// extent iff block % epc == 0 -- and the void tail (kStencilDistance elements,
-// :151-162) covers the partial last row the view drops.
-static bool dense_view(const soda_hip_stream* s, int64_t n, int32_t* ext) {
-  const soda_hip_stream_desc_t& d = s->desc;
-  if (s->dense_failed || d.dim < 2) return false;
-  int64_t block = 1;
-  for (int t = 0; t < d.dim - 1; ++t) block *= d.tile[t];
-  const int64_t rows = n / block;
-  if (rows < 1 || d.stencil_distance < block ||
-      block % d.elems_per_cycle[0] != 0)
-    return false;
-  for (int t = 0; t < SODA_HIP_MAX_DIM; ++t) ext[t] = 1;
-  for (int t = 0; t < d.dim - 1; ++t) ext[t] = d.tile[t];
-  ext[d.dim - 1] = (int32_t)rows;
-  return true;
-}
-
-// Does this call run the banked form of the dense program?  Every reason not
-// to is found HERE, before anything is launched: no dense view, a tile the
-// device-dense rule keeps on the linear form, a bank of an in_kernel tensor
-// that is not 16-byte aligned, an extent the kernels refuse, a schedule of the
-// dense program that the banked programs do not cover.  *launches: 0 = no (the
-// call runs as without a banked program), 1 = `banked`, 2 = `banked_first`
-// then `banked_last`.
-//
-// The schedule is the MODEL's (soda_hip_stream_set_banked turns the clock's
-// calibration of the stream's dense program off, so the copy path of the same
-// stream is scheduled from the same source): the one fused launch, or -- two
-// iterations -- two launches of the one-iteration kernel.
-static int banked_launches(soda_hip_stream* s, void* const* out_banks,
-                           const void* const* in_banks, int32_t n, int32_t* ext,
-                           int* launches) {
-  const soda_hip_stream_desc_t& d = s->desc;
-  *launches = 0;
-  if (!s->banked || d.tile[0] < s->device_dense_min_tile0 ||
-      !dense_view(s, n, ext))
-    return SODA_HIP_OK;
-  int want = 1;
-  if (d.iterate > 1) {
-    if (!s->dense) return SODA_HIP_OK;
-    int32_t count[SODA_HIP_MAX_PASSES];
-    const int rc = soda_hip_program_schedule(s->dense, ext, d.iterate, count);
-    if (rc == SODA_HIP_ERR_INVALID) return SODA_HIP_OK;   // no dense run either
-    if (rc) return rc;
-    const soda_hip_plan_t& dp = s->dense->plan;
-    int total = 0, deepest = 0;
-    for (int i = 0; i < dp.num_passes; ++i) {
-      total += count[i];
-      if (count[i] && !deepest) deepest = dp.passes[i].fused_iters;
-    }
-    if (total == 1 && deepest == d.iterate)
-      want = 1;
-    else if (total == 2 && deepest == 1 && s->banked_first && s->banked_last)
-      want = 2;
-    else
-      return SODA_HIP_OK;
-  }
-  for (soda_hip_program* p : {want == 1 ? s->banked : s->banked_first,
-                              want == 1 ? s->banked : s->banked_last}) {
-    const int rc = plan_geometry_c(&p->plan, ext, nullptr, nullptr);
-    if (rc == SODA_HIP_ERR_INVALID) return SODA_HIP_OK;
-    if (rc) return rc;
-  }
-  int bank0 = 0;
-  for (int i = 0; i < d.num_inputs; bank0 += d.banks[i], ++i)
-    for (int b = 0; s->in_kernel[i] && b < d.banks[i]; ++b)
-      if (!in_banks[bank0 + b] ||
-          (reinterpret_cast<uintptr_t>(in_banks[bank0 + b]) & 15))
-        return SODA_HIP_OK;      // (a NULL bank: the path below says so)
-  bank0 = 0;
-  for (int o = 0; o < d.num_outputs; bank0 += d.banks[d.num_inputs + o], ++o)
-    for (int b = 0; s->in_kernel[d.num_inputs + o] &&
-                    b < d.banks[d.num_inputs + o]; ++b)
-      if (!out_banks[bank0 + b] ||
-          (reinterpret_cast<uintptr_t>(out_banks[bank0 + b]) & 15))
-        return SODA_HIP_OK;
-  *launches = want;
-  return SODA_HIP_OK;
-}
-
-// Would a plain run of `iterate` iterations on `ext` grow the scratch of `p`?
-// By the schedule run_core itself would take on a capturing stream (measured
-// times where there are any, never a calibration).
-static int program_grows(soda_hip_program* p, const int32_t* ext,
-                         int32_t iterate, bool* grows) {
-  int32_t count[SODA_HIP_MAX_PASSES];
-  if (int rc = soda_hip_program_schedule(p, ext, iterate, count)) return rc;
-  int32_t total = 0;
-  int64_t cells = 1;
-  for (int i = 0; i < p->plan.num_passes; ++i) total += count[i];
-  for (int d = 0; d < p->plan.dim; ++d) cells *= ext[d];
-  if (scratch_grows(p, locals_in_memory(p->plan, count), total, false, cells, 1))
-    *grows = true;
-  return SODA_HIP_OK;
-}
-
-// The look-ahead of soda_hip_stream_run_device: its ensure() calls lie between
-// its launches, so whether this call allocates anything -- a staging array, the
-// temporary of the two-launch banked form, scratch of a program it runs -- is
-// worked out here, before the first of them, following the same decisions.
-static int stream_grows(soda_hip_stream* s, int32_t n, int banked,
-                        const int32_t* bext, bool* grows) {
-  const soda_hip_stream_desc_t& d = s->desc;
-  const int32_t* kern = banked ? s->in_kernel.data() : nullptr;
-  const int32_t ext1[1] = {n};
-  *grows = false;
-  for (int i = 0; i < d.num_inputs; ++i) {
-    if ((kern && kern[i]) || (d.banks[i] == 1 && d.shift[i] == 0)) continue;
-    if (too_small(s->dense_in[i], (size_t)n * d.elem_size[i])) *grows = true;
-    if (int rc = program_grows(s->unwire[i], ext1, 1, grows)) return rc;
-  }
-  for (int o = 0; o < d.num_outputs; ++o) {
-    if ((kern && kern[d.num_inputs + o]) || !s->wire[o]) continue;
-    if (too_small(s->dense_out[o], (size_t)n * d.elem_size[d.num_inputs + o]))
-      *grows = true;
-    if (int rc = program_grows(s->wire[o], ext1, 1, grows)) return rc;
-  }
-  if (banked == 2) {
-    for (int o = 0; o < d.num_outputs; ++o)
-      if (too_small(s->banked_tmp[o], (size_t)n * d.elem_size[d.num_inputs + o]))
-        *grows = true;
-    if (int rc = program_grows(s->banked_first, bext, 1, grows)) return rc;
-    return program_grows(s->banked_last, bext, 1, grows);
-  }
-  if (banked == 1) return program_grows(s->banked, bext, 1, grows);
-  int32_t ext[SODA_HIP_MAX_DIM];
-  if (d.tile[0] >= s->device_dense_min_tile0 && dense_view(s, n, ext)) {
-    const int rc = program_grows(s->dense, ext, d.iterate, grows);
-    if (rc != SODA_HIP_ERR_INVALID) return rc;
-    // INVALID: this extent does not suit the dense kernels; the call goes linear
-  }
-  int pick = d.num_linear - 1;
-  for (int k = 0; k < d.num_linear; ++k)
-    if (n % d.linear_vec[k] == 0) { pick = k; break; }
-  return program_grows(s->linear[pick], ext1, d.iterate, grows);
-}
-
-int soda_hip_stream_run_device(soda_hip_stream_t* s, void* const* out_banks,
-                               const void* const* in_banks,
-                               uint64_t coalesced_data_num, void* hip_stream) {
-  if (!s || !out_banks || !in_banks)
-    return fail(SODA_HIP_ERR_INVALID, "stream_run: NULL argument");
-  const soda_hip_stream_desc_t& d = s->desc;
-  const uint64_t n64 = coalesced_data_num * (uint64_t)d.elems_per_cycle[0];
-  if (n64 < 1 || n64 >= (1ull << 31))
-    return fail(SODA_HIP_ERR_INVALID, "stream_run: stream length out of range");
-  const int32_t n = (int32_t)n64;
-  const int32_t ext1[1] = {n};
-  HIP_TRY(hipSetDevice(s->linear.back()->device));
-  // the banked form of the dense program: the tensors marked in_kernel go to
-  // it bank by bank -- no copy kernel, no staging array -- every other tensor
-  // as always (`kern` stays NULL where the call does not take the form)
-  int32_t bext[SODA_HIP_MAX_DIM];
-  int banked = 0;
-  if (s->banked)
-    if (int rc = banked_launches(s, out_banks, in_banks, n, bext, &banked))
-      return rc;
-  const int32_t* kern = banked ? s->in_kernel.data() : nullptr;
-  // A length that has not run this way before may allocate.  On a stream that
-  // is being captured that is refused here, before the first launch (whatever
-  // else is wrong with the call is found and said below, as ever).
-  const std::pair<int32_t, int> key(n, banked);
-  const bool warm =
-      std::find(s->warm.begin(), s->warm.end(), key) != s->warm.end();
-  if (!warm) {
-    bool grows = false;
-    if (stream_grows(s, n, banked, bext, &grows) == SODA_HIP_OK && grows)
-      if (int rc = refuse_growth_while_capturing(hip_stream, "stream_run"))
-        return rc;
-  }
-  // 1. un-interleave (and un-delay) the inputs
-  std::vector<const void*> din;     // one entry per tensor, NB per in_kernel one
-  int bank0 = 0;
-  for (int i = 0; i < d.num_inputs; ++i) {
-    const int nb = d.banks[i];
-    for (int b = 0; b < nb; ++b)
-      if (!in_banks[bank0 + b])
-        return fail(SODA_HIP_ERR_INVALID, "stream_run: NULL input bank");
-    if (kern && kern[i]) {
-      din.insert(din.end(), in_banks + bank0, in_banks + bank0 + nb);
-    } else if (nb == 1 && d.shift[i] == 0) {
-      if (reinterpret_cast<uintptr_t>(in_banks[bank0]) & 15)
-        return fail(SODA_HIP_ERR_INVALID,
-                    "stream_run: a bank the program reads in place must be "
-                    "16-byte aligned");
-      din.push_back(in_banks[bank0]);     // the bank IS the dense stream
-    } else {
-      if (int rc = ensure(s->dense_in[i], (size_t)n * d.elem_size[i])) return rc;
-      void* outs[1] = {s->dense_in[i].ptr};
-      if (int rc = soda_hip_run_device(s->unwire[i], outs, in_banks + bank0, ext1,
-                                       1, hip_stream))
-        return rc;
-      din.push_back(s->dense_in[i].ptr);
-    }
-    bank0 += nb;
-  }
-  std::vector<void*> dout;          // likewise
-  std::vector<void*> staged(d.num_outputs, nullptr);   // what wire_<o> reads
-  bank0 = 0;
-  for (int o = 0; o < d.num_outputs; bank0 += d.banks[d.num_inputs + o], ++o) {
-    const int nb = d.banks[d.num_inputs + o];
-    for (int b = 0; b < nb; ++b)
-      if (!out_banks[bank0 + b])
-        return fail(SODA_HIP_ERR_INVALID, "stream_run: NULL output bank");
-    if (kern && kern[d.num_inputs + o]) {
-      dout.insert(dout.end(), out_banks + bank0, out_banks + bank0 + nb);
-      continue;
-    }
-    if (!s->wire[o]) {
-      if (reinterpret_cast<uintptr_t>(out_banks[bank0]) & 15)
-        return fail(SODA_HIP_ERR_INVALID,
-                    "stream_run: a bank the program writes in place must be "
-                    "16-byte aligned");
-      dout.push_back(out_banks[bank0]);   // born at its wire position, in place
-      continue;
-    }
-    const size_t bytes = (size_t)n * d.elem_size[d.num_inputs + o];
-    const void* before = s->dense_out[o].ptr;
-    if (int rc = ensure(s->dense_out[o], bytes)) return rc;
-    // new memory: the dense view drops the partial last row, whose bytes would
-    // otherwise reach the caller's banks uninitialised through wire_<out>
-    if (s->dense_out[o].ptr != before)
-      HIP_TRY(hipMemsetAsync(s->dense_out[o].ptr, 0, s->dense_out[o].bytes,
-                             static_cast<hipStream_t>(hip_stream)));
-    dout.push_back(s->dense_out[o].ptr);
-    staged[o] = s->dense_out[o].ptr;
-  }
-  // 2. the program, on the dense view where there is one
-  bool done = false;
-  if (banked == 2) {
-    // two one-iteration launches, a dense temporary per output between them
-    std::vector<void*> tmp(d.num_outputs);
-    for (int o = 0; o < d.num_outputs; ++o) {
-      if (int rc = ensure(s->banked_tmp[o],
-                          (size_t)n * d.elem_size[d.num_inputs + o]))
-        return rc;
-      tmp[o] = s->banked_tmp[o].ptr;
-    }
-    s->banked_first->stream_elems = n;
-    if (int rc = soda_hip_run_device(s->banked_first, tmp.data(), din.data(),
-                                     bext, 1, hip_stream))
-      return rc;
-    std::vector<const void*> from(tmp.begin(), tmp.end());
-    s->banked_last->stream_elems = n;
-    if (int rc = soda_hip_run_device(s->banked_last, dout.data(), from.data(),
-                                     bext, 1, hip_stream))
-      return rc;
-    done = true;
-    s->last_mode = 3;
-  } else if (banked == 1) {
-    s->banked->stream_elems = n;
-    if (int rc = soda_hip_run_device(s->banked, dout.data(), din.data(), bext, 1,
-                                     hip_stream))
-      return rc;
-    done = true;
-    s->last_mode = 3;
-  } else {
-    int32_t ext[SODA_HIP_MAX_DIM];
-    if (d.tile[0] >= s->device_dense_min_tile0 && dense_view(s, n, ext)) {
-      int rc = soda_hip_run_device(s->dense, dout.data(), din.data(), ext,
-                                   d.iterate, hip_stream);
-      if (rc == SODA_HIP_OK) {
-        done = true;
-        s->last_mode = 1;
-      } else if (rc != SODA_HIP_ERR_INVALID) {
-        return rc;
-      }   // INVALID: this extent does not suit the dense kernels; go linear
-    }
-  }
-  if (!done) {
-    int pick = d.num_linear - 1;
-    for (int k = 0; k < d.num_linear; ++k)
-      if (n % d.linear_vec[k] == 0) { pick = k; break; }
-    if (int rc = soda_hip_run_device(s->linear[pick], dout.data(), din.data(),
-                                     ext1, d.iterate, hip_stream))
-      return rc;
-    s->last_mode = 2;
-  }
-  // 3. outputs: shifted by the stencil offset, re-interleaved
-  bank0 = 0;
-  for (int o = 0; o < d.num_outputs; bank0 += d.banks[d.num_inputs + o], ++o) {
-    if (!staged[o]) continue;
-    const void* ins[1] = {staged[o]};
-    if (int rc = soda_hip_run_device(s->wire[o], out_banks + bank0, ins, ext1, 1,
-                                     hip_stream))
-      return rc;
-  }
-  if (!warm) {
-    if (s->warm.size() >= 64) s->warm.clear();
-    s->warm.push_back(key);
-  }
-  return SODA_HIP_OK;
-}
-
-int soda_hip_stream_run_host(soda_hip_stream_t* s, void* const* out_banks,
-                             const void* const* in_banks,
-                             uint64_t coalesced_data_num) {
-  if (!s || !out_banks || !in_banks)
-    return fail(SODA_HIP_ERR_INVALID, "stream_run_host: NULL argument");
-  const soda_hip_stream_desc_t& d = s->desc;
-  // Every tensor on one bank that the program reads / writes in place, and the
-  // stream a dense array of rows: the caller's banks ARE host arrays of the
-  // n-D program, and the call is the host-array entry's (soda_host.cpp) --
-  // copy-in, kernels and copy-out overlapped in bands along the rows.  The
-  // elements of the partial last row stay as the caller left them (void tail).
-  // Banked tensors ride along: their (de)interleave is done by the host
-  // threads in the pack / unpack step instead of by copy kernels on the GPU.
-  {
-    bool in_place = !getenv("SODA_HIP_STREAM_NO_BANDS");
-    // (a delayed input on ONE bank is un-delayed in the pack step as well)
-    for (int t = 0; t < d.num_inputs + d.num_outputs; ++t)
-      in_place = in_place && (d.shift[t] == 0 ||
-                              (t < d.num_inputs && d.banks[t] == 1));
-    const uint64_t n64 = coalesced_data_num * (uint64_t)d.elems_per_cycle[0];
-    int32_t ext[SODA_HIP_MAX_DIM];
-    if (in_place && n64 >= 1 && n64 < (1ull << 31) &&
-        dense_view(s, (int64_t)n64, ext)) {
-      int32_t stride[SODA_HIP_MAX_DIM];
-      int64_t run = 1;
-      for (int t = 0; t < SODA_HIP_MAX_DIM; ++t) {
-        stride[t] = run > INT32_MAX ? INT32_MAX : (int32_t)run;   // (t >= dim: unread)
-        run *= ext[t];
-      }
-      std::vector<soda_hip_host_tensor_t> tin(d.num_inputs), tout(d.num_outputs);
-      bool null_bank = false;
-      int bank = 0;
-      for (int i = 0; i < d.num_inputs; bank += d.banks[i], ++i) {
-        for (int b = 0; b < d.banks[i]; ++b)
-          null_bank = null_bank || !in_banks[bank + b];
-        // one bank: the array itself; several: the list of them
-        tin[i] = {d.banks[i] == 1
-                      ? const_cast<void*>(in_banks[bank])
-                      : const_cast<void*>(static_cast<const void*>(in_banks + bank)),
-                  ext, stride, nullptr};
-      }
-      bank = 0;
-      for (int o = 0; o < d.num_outputs; bank += d.banks[d.num_inputs + o], ++o) {
-        for (int b = 0; b < d.banks[d.num_inputs + o]; ++b)
-          null_bank = null_bank || !out_banks[bank + b];
-        tout[o] = {d.banks[d.num_inputs + o] == 1
-                       ? out_banks[bank]
-                       : const_cast<void*>(static_cast<const void*>(out_banks + bank)),
-                   ext, stride, nullptr};
-      }
-      if (null_bank)
-        return fail(SODA_HIP_ERR_INVALID, "stream_run_host: NULL bank");
-      int rc = run_host_call(s->dense, tin.data(), tout.data(), d.iterate,
-                             nullptr, nullptr, d.banks, d.shift, (int64_t)n64);
-      if (rc == SODA_HIP_OK) {
-        s->last_mode = 1;
-        return rc;
-      }
-      if (rc != SODA_HIP_ERR_INVALID) return rc;
-      // INVALID: this extent does not suit the dense kernels; the long way
-    }
-  }
-  // Otherwise the banks -- the generated host's pageable `aligned_alloc`
-  // buffers (ref frt/host.py:165-178) -- travel whole through the pinned rings
-  // and the worker threads of the host-array entry, on one stream with the
-  // kernels.
-  soda_hip_program* owner = s->linear.back();
-  hipStream_t stream = nullptr;
-  if (int rc = host_stream(owner, &stream)) return rc;
-  int total = 0;
-  for (int t = 0; t < d.num_inputs + d.num_outputs; ++t) total += d.banks[t];
-  s->host_banks.resize(total);
-  std::vector<const void*> dev_in;
-  std::vector<void*> dev_out;
-  int slot = 0, bank = 0;
-  for (int i = 0; i < d.num_inputs; ++i)
-    for (int b = 0; b < d.banks[i]; ++b, ++slot, ++bank) {
-      const size_t bytes = (size_t)coalesced_data_num * d.elems_per_cycle[i] /
-                           d.banks[i] * d.elem_size[i];
-      if (!in_banks[bank])
-        return fail(SODA_HIP_ERR_INVALID, "stream_run_host: NULL input bank");
-      if (int rc = ensure(s->host_banks[slot], bytes)) return rc;
-      if (int rc = ring_send(owner, s->host_banks[slot].ptr, in_banks[bank],
-                             bytes, stream))
-        return rc;
-      dev_in.push_back(s->host_banks[slot].ptr);
-    }
-  std::vector<size_t> out_bytes;
-  for (int o = 0; o < d.num_outputs; ++o)
-    for (int b = 0; b < d.banks[d.num_inputs + o]; ++b, ++slot) {
-      const int t = d.num_inputs + o;
-      const size_t bytes = (size_t)coalesced_data_num * d.elems_per_cycle[t] /
-                           d.banks[t] * d.elem_size[t];
-      const void* before = s->host_banks[slot].ptr;
-      if (int rc = ensure(s->host_banks[slot], bytes)) return rc;
-      // void positions a program writing in place never touches: the same
-      // bytes for the caller run after run
-      if (s->host_banks[slot].ptr != before)
-        HIP_TRY(hipMemsetAsync(s->host_banks[slot].ptr, 0, bytes, stream));
-      dev_out.push_back(s->host_banks[slot].ptr);
-      out_bytes.push_back(bytes);
-    }
-  for (size_t k = 0; k < dev_out.size(); ++k)
-    if (!out_banks[k])
-      return fail(SODA_HIP_ERR_INVALID, "stream_run_host: NULL output bank");
-  if (int rc = soda_hip_stream_run_device(s, dev_out.data(), dev_in.data(),
-                                          coalesced_data_num, stream))
-    return rc;
-  for (size_t k = 0; k < dev_out.size(); ++k)
-    if (int rc = ring_fetch(owner, out_banks[k], dev_out[k], out_bytes[k],
-                            stream))
-      return rc;
-  HIP_TRY(hipStreamSynchronize(stream));
   return SODA_HIP_OK;
 }
 

@@ -1,5 +1,6 @@
 // soda_internal.h -- what the translation units of libsoda_hip.so share
-// (soda_hip.cpp: programs, launch geometry, runs; soda_group.cpp: slab groups).
+// (soda_hip.cpp: programs, launch geometry, runs; soda_group.cpp: slab groups;
+// soda_stream.cpp: the wire-format stream object, with soda_stream.h; ...).
 // Nothing here crosses the C ABI (include/soda_hip.h).
 #ifndef SODA_INTERNAL_H_
 #define SODA_INTERNAL_H_
@@ -216,6 +217,12 @@ struct RunRequest {
   const ResidualRun* residual = nullptr;
 };
 int run_core(soda_hip_program* p, const RunRequest& rq);
+// Would a plain run of `iterate` iterations on `ext` grow the scratch of `p`
+// (sets *grows, never clears it)?  By the schedule run_core itself would take
+// on a capturing stream (measured times where there are any, never a
+// calibration).
+int program_grows(soda_hip_program* p, const int32_t* ext, int32_t iterate,
+                  bool* grows);
 
 // The pieces of a residual that several runs and boxes fill (ResidualRun's
 // `accumulate`), each one launch on `stream`.  residual_zero: the struct

@@ -694,9 +694,12 @@ def _wire_tensors(case, real):
   return t
 
 
-def test_warm_capture_replay_of_a_dense_wire_stream(built):
+@pytest.mark.parametrize('name', sorted(WIRE))
+def test_warm_capture_replay_of_a_dense_wire_stream(built, name):
+  """Every form a call's route takes -- dense view, linear, copy kernels
+  around the dense view, banked -- captured warm and replayed."""
   import torch
-  case = _Wire('two_banks')
+  case = _Wire(name)
   S = torch.cuda.Stream()
   try:
     case.open()
@@ -714,7 +717,7 @@ def test_warm_capture_replay_of_a_dense_wire_stream(built):
       t.fill(real)
       g.replay()
       case.assert_same(t.read(), ref, 'replay, seed %d' % seed)
-    assert case.prog.last_mode == 'dense'
+    assert case.prog.last_mode == case.mode
     torch.cuda.synchronize()
     del g
   finally:

@@ -260,6 +260,26 @@ def test_run_tensor_checks_under_a_sanitizer(tmp_path):
       'run tensor checks: clean'), run.stdout + run.stderr
 
 
+def test_stream_routes_under_a_sanitizer(tmp_path):
+  """tests/host/stream_route_main.cpp: the route a wire stream object takes
+  per call (stream_route, soda_amd/csrc/soda_stream.h) -- form, roles, buffers
+  and launches -- against routes written out by hand: tensors in place on wide
+  and narrow tiles, streams without a dense view, the linear pick, two banks
+  staged, the banked form with aligned, misaligned and NULL banks, the two
+  schedules of a two-iteration program with and without the banked pair; the
+  look-ahead walks exactly that route.  Its own main, the library's sources,
+  ASan + UBSan (`make stream_route_asan`); no GPU, nothing loaded into
+  Python."""
+  out = str(tmp_path)
+  subprocess.run(['make', '-C', os.path.join(ROOT, 'soda_amd', 'csrc'),
+                  'stream_route_asan', 'OUT=' + out], check=True,
+                 capture_output=True)
+  run = subprocess.run([os.path.join(out, 'stream_route_asan')],
+                       capture_output=True, text=True, timeout=300)
+  assert run.returncode == 0 and run.stdout.startswith(
+      'stream routes: clean'), run.stdout + run.stderr
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize('main,soda', WIRE_HOSTS)
 def test_wire_kernels_under_independent_hosts(built, tmp_path, main, soda):

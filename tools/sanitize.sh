@@ -29,7 +29,7 @@ lib=$PWD/soda_amd/_sanitize
 fail=0
 {
   echo "# tools/sanitize.sh, $(date -u +%FT%TZ), $(gcc --version | head -1)"
-  make -C soda_amd/csrc asan tsan plan_asan 2>&1 | tail -3 || fail=1
+  make -C soda_amd/csrc asan tsan plan_asan stream_route_asan 2>&1 | tail -3 || fail=1
   # the product library up to date BEFORE a sanitizer runtime is preloaded (the
   # tests' `built` fixture would otherwise run hipcc under it)
   python -c "import __graft_entry__ as g; g.build_library()" || fail=1
@@ -61,6 +61,8 @@ fail=0
   # (a program with its own main: no runtime preloaded, no interpreter)
   run "residual planning, ASan + UBSan, stand-alone: slab boxes partition the global box, launches of a residual slab run" \
       "" $lib/libsoda_hip_asan.so $lib/residual_slab_box_asan
+  run "wire stream routes, ASan + UBSan, stand-alone: form, roles, buffers and launches of a call" \
+      "" $lib/libsoda_hip_asan.so $lib/stream_route_asan
   run "libsoda_hip, TSan: the worker pool of the host-array entry (pack / unpack on 8 threads)" \
       "$tsan" $lib/libsoda_hip_tsan.so \
       python -m pytest -q -m "not gpu" -p no:cacheprovider tests/test_host.py -k "pack_and_unpack"
