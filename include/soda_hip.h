@@ -78,7 +78,9 @@ extern "C" {
  * _fill / _run_padded / _run_device with soda_hip_border_desc_t; and their
  * fused form -- soda_hip_box_host, soda_hip_border_fused_plan / _create /
  * _destroy / _info / _move / _run_padded / _run_device with
- * soda_hip_border_fused_desc_t. */
+ * soda_hip_border_fused_desc_t; and a border mode and a constant per face --
+ * soda_hip_border_faces_t with soda_hip_extend_faces_host and the `_faces`
+ * twin of every entry that takes a bordered or a fused bordered request. */
 #define SODA_HIP_ABI_VERSION 9
 #define SODA_HIP_MAX_DIM 4
 #define SODA_HIP_MAX_TENSORS 16
@@ -311,8 +313,8 @@ int soda_hip_device_count(int* count);
  * 4 host_tensor, 5 stream_desc, 6 slab_run, 7 group_desc, 8 slab_info,
  * 9 group_stats, 10 launch_info, 11 residual, 12 resbox, 14 norms,
  * 15 periodic_desc, 16 periodic_info, 17 border_desc, 18 border_fused_desc,
- * 19 border_strip, 20 border_fused_info; 0 for anything else (13 among
- * them). */
+ * 19 border_strip, 20 border_fused_info, 21 border_fused_boxes,
+ * 22 border_faces; 0 for anything else (13 among them). */
 size_t soda_hip_sizeof(int which);
 
 /* -- JIT: HIP source text -> gfx950 code object (hiprtc; needs no GPU) ---- */
@@ -1377,6 +1379,128 @@ int soda_hip_border_fused_run_until_norm(soda_hip_border_fused_t* handle,
                                          soda_hip_norms_t* result_host,
                                          int32_t* iterations_done,
                                          void* stream);
+
+/* -- bordered domains: a mode and a constant per FACE ------ */
+/* The bordered blocks above give a dimension's low and high wall one mode and
+ * every `constant` wall of a tensor one value.  This extension lifts both:
+ * every dimension d has a mode for its LOW face (desc->mode[d]) and one for its
+ * HIGH face (faces->mode_hi[d]), every input tensor a constant per face.  With
+ * g = ghost_lo[d], j = i - g and m_X the closed form of mode X as stated under
+ * "bordered domains", padded index i takes m_lo(j) where j < 0, m_hi(j) where
+ * j >= N, and j elsewhere (the forms are total: a frame wider than the domain
+ * bounces as before).  CONSTANT as a face mode means none: the cell takes a
+ * constant.  WRAP is served as the pair (WRAP, WRAP) only.
+ * The map stays separable, with one rule for the constants: a ghost cell that
+ * is outside through a CONSTANT face in one or more dimensions takes the
+ * constant of the HIGHEST such dimension, and of that face; every other ghost
+ * cell takes the interior cell given by the maps of all dimensions at once.
+ * That is what extending the array dimension by dimension gives, dimension 0
+ * first, each dimension's two sides taken from the array as it stood before
+ * that dimension.
+ * A wall dimension is one whose faces are not (WRAP, WRAP): it keeps a frame
+ * of one iteration's reach, refilled after every iteration.  The output's
+ * ghost takes the constants of the input it replaces.  Bits are moved, never
+ * computed with.
+ * Only a CONSTANT face ever shows its constant, so a tensor's constants count
+ * as equal where those of its CONSTANT faces are.
+ * A request whose faces are equal pairwise and whose constants are equal per
+ * tensor -- and faces == NULL -- is the request of the blocks above: every
+ * `_faces` entry below then IS the entry it is named after, with its
+ * launches, its kernels (the extend module's) and its scratch.  Only an
+ * asymmetric request loads and launches the FACES module
+ * (codegen/hip/faces.py; soda_faces_e<bytes>_d<dim>, `_bt` on a batch). */
+typedef struct soda_hip_border_faces {
+  int32_t mode_hi[SODA_HIP_MAX_DIM];   /* SODA_HIP_BORDER_* of the HIGH face per
+                                          dimension; desc->mode[] is the LOW
+                                          face */
+  int32_t per_face_constants;          /* 0: desc->constant[] on every face */
+  int32_t reserved[3];
+  uint64_t constant[SODA_HIP_MAX_TENSORS][SODA_HIP_MAX_DIM][2];
+                                       /* [input][dimension][0 low, 1 high]: the
+                                          cell's bit pattern in the low bytes */
+} soda_hip_border_faces_t;             /* soda_hip_sizeof(22) */
+/* soda_hip_extend_host with a mode per face and a constant per (dimension,
+ * side): constants[2 * d + side].  With equal pairs and one constant it is
+ * soda_hip_extend_host.  SODA_HIP_ERR_INVALID, the array untouched: a mode
+ * that is none of SODA_HIP_BORDER_*, a dimension that wraps on one face. */
+int soda_hip_extend_faces_host(void* array, int32_t elem_bytes, int32_t dim,
+                               const int32_t* extent, const int32_t* ghost_lo,
+                               const int32_t* ghost_hi,
+                               const int32_t* modes_lo,
+                               const int32_t* modes_hi,
+                               const uint64_t* constants);
+/* The twins.  Each has the signature of the entry it is named after plus
+ * `faces` (NULL: that entry) behind the desc and, where that entry takes code
+ * objects, faces_code[i] / faces_code_size[i] behind them: the code object of
+ * the FACES module of 1 << i byte cells and the program's dimension count (the
+ * batched one for _create_batch_faces), needed for every cell size among the
+ * program's inputs and outputs when the request is asymmetric, never looked at
+ * otherwise (NULL will do); an asymmetric request in turn never looks at
+ * `code`, the extend module's.  The handles are those of the blocks above, and
+ * _info, _fill, _run_padded, _run_device, _run_padded_residual,
+ * _run_padded_norms, _run_until, _run_until_norm and _destroy serve them under
+ * their contracts as written.  The geometry -- ghosts, padded extent, chunks,
+ * depth, strips, residual boxes -- is that of the symmetric request with the
+ * same wall dimensions; a strip of the fused form is a bordered domain with
+ * the request's faces and constants.  On top of the refusals of the entries
+ * they are named after, nothing launched and nothing allocated:
+ *   SODA_HIP_ERR_INVALID      a dimension that wraps on one face only;
+ *                             a face mode that is none of SODA_HIP_BORDER_*;
+ *                             refill_every > 1 unless every pair is
+ *                             (WRAP, WRAP).
+ * A batched faces handle refuses residuals, norms and runs until converged
+ * like every batched handle (SODA_HIP_ERR_UNSUPPORTED), the fused twins a
+ * batched plan. */
+int soda_hip_border_plan_faces(const soda_hip_plan_t* plan,
+                               const soda_hip_border_desc_t* desc,
+                               const soda_hip_border_faces_t* faces,
+                               int32_t iterate, soda_hip_periodic_info_t* info,
+                               int32_t capacity, int32_t* chunks,
+                               int32_t* count);
+int soda_hip_border_plan_batch_faces(const soda_hip_plan_t* plan,
+                                     const soda_hip_border_desc_t* desc,
+                                     const soda_hip_border_faces_t* faces,
+                                     int32_t batch, int32_t iterate,
+                                     soda_hip_periodic_info_t* info,
+                                     int32_t capacity, int32_t* chunks,
+                                     int32_t* count);
+int soda_hip_border_create_faces(soda_hip_program_t* program,
+                                 const soda_hip_border_desc_t* desc,
+                                 const soda_hip_border_faces_t* faces,
+                                 const void* const* code,
+                                 const size_t* code_size,
+                                 const void* const* faces_code,
+                                 const size_t* faces_code_size,
+                                 soda_hip_border_t** handle);
+int soda_hip_border_create_batch_faces(soda_hip_program_t* program,
+                                       const soda_hip_border_desc_t* desc,
+                                       const soda_hip_border_faces_t* faces,
+                                       int32_t batch, const void* const* code,
+                                       const size_t* code_size,
+                                       const void* const* faces_code,
+                                       const size_t* faces_code_size,
+                                       soda_hip_border_t** handle);
+int soda_hip_border_fused_plan_faces(const soda_hip_plan_t* plan,
+                                     const soda_hip_border_fused_desc_t* desc,
+                                     const soda_hip_border_faces_t* faces,
+                                     int32_t iterate,
+                                     soda_hip_border_fused_info_t* info,
+                                     int32_t capacity, int32_t* chunks,
+                                     int32_t* count);
+int soda_hip_border_fused_create_faces(
+    soda_hip_program_t* program, const soda_hip_border_fused_desc_t* desc,
+    const soda_hip_border_faces_t* faces, const void* const* code,
+    const size_t* code_size, const void* const* box_code,
+    const size_t* box_code_size, const void* const* faces_code,
+    const size_t* faces_code_size, soda_hip_border_fused_t** handle);
+int soda_hip_border_fused_residual_boxes_faces(
+    const soda_hip_plan_t* plan, const soda_hip_border_fused_desc_t* desc,
+    const soda_hip_border_faces_t* faces,
+    soda_hip_border_fused_boxes_t* boxes);
+/* A/B runs only: with SODA_HIP_FACES_FORCE=1 in the environment (read once per
+ * handle, when it is made) a `_create*_faces` entry that is given the faces
+ * module serves a SYMMETRIC request with the faces kernels as well -- the same
+ * bits, the other kernel (tools/faces_ab.py). */
 
 /* Replaces soda::app::<app>(): host arrays described by (ptr, extent, stride,
  * min) per tensor, inputs then outputs; copies in, runs, copies the outputs

@@ -14,8 +14,10 @@ opencl.py:55-142).  This module slots into the same place:
                       nothing by itself (the oracle lives in tests/); prints
                       one JSON line with timing.  --hip-periodic: on a torus.
                       --hip-border MODE[,MODE...]: with a border mode per
-                      dimension; --hip-border-depth T: fused away from the
-                      walls.
+                      dimension, LOW/HIGH for one per face;
+                      --hip-border-values V[/V][,V[/V]...]: the constants per
+                      dimension and side; --hip-border-depth T: fused away
+                      from the walls.
 """
 import argparse
 import json
@@ -26,6 +28,29 @@ import time
 
 from soda_amd import core, util
 from soda_amd.codegen.hip import lower
+
+
+def parse_border(text: str, dim: int):
+  """--hip-border's MODE[,MODE...]: one name, or a list with one entry per
+  dimension (one for all), an entry LOW/HIGH a pair of names."""
+  entries = [m.strip() for m in text.split(',')]
+  entries = [tuple(f.strip() for f in m.split('/')) if '/' in m else m
+             for m in entries]
+  if len(entries) == 1:
+    return entries[0] if isinstance(entries[0], str) else entries * dim
+  return entries
+
+
+def parse_border_values(text: str, dim: int):
+  """--hip-border-values' V[/V][,V[/V]...]: one entry per dimension (one for
+  all), an entry LOW/HIGH a pair of values."""
+  try:
+    entries = [tuple(float(v) for v in e.split('/')) if '/' in e else float(e)
+               for e in text.split(',')]
+  except ValueError:
+    raise util.InputError('--hip-border-values: numbers, V or LOW/HIGH per '
+                          'dimension')
+  return entries * dim if len(entries) == 1 else entries
 
 
 def add_arguments(parser) -> None:
@@ -125,13 +150,23 @@ def add_arguments(parser) -> None:
                       help='--hip-backend: run with borders -- every iteration '
                       'sees its inputs extended by wrap, clamp, mirror, '
                       'mirror101 or constant (one mode for all dimensions or '
-                      'one per dimension, dimension 0 first), every cell of '
+                      'one per dimension, dimension 0 first; LOW/HIGH in any '
+                      'position gives the two faces of a dimension a mode '
+                      'each), every cell of '
                       'the outputs is defined (soda_hip_border_run_device; one '
                       'GPU, no --hip-until, no --hip-periodic)')
   parser.add_argument('--hip-border-value', type=float,
                       dest='hip_border_value', default=0.0, metavar='V',
                       help='with --hip-border: the value outside the grid in a '
                       '`constant` dimension (default 0)')
+  parser.add_argument('--hip-border-values', dest='hip_border_values',
+                      default=None, metavar='V[/V][,V[/V]...]',
+                      help='with --hip-border: the values outside the grid per '
+                      'dimension, dimension 0 first, LOW/HIGH for one per '
+                      'face (one entry for all dimensions or one per '
+                      'dimension; one list for all inputs; instead of '
+                      '--hip-border-value: a value other than 0 there is '
+                      'refused beside this option)')
   parser.add_argument('--hip-border-depth', type=int,
                       dest='hip_border_depth', default=None, metavar='T',
                       help='with --hip-border: fuse away from the walls in '
@@ -275,11 +310,21 @@ def run(stencil: core.Stencil, args: argparse.Namespace) -> None:
                           'residuals are not served on a bordered domain yet)')
   if border is None and getattr(args, 'hip_border_depth', None) is not None:
     raise util.InputError('--hip-border-depth needs --hip-border')
+  border_values = getattr(args, 'hip_border_values', None)
+  if border is None and border_values is not None:
+    raise util.InputError('--hip-border-values needs --hip-border')
+  if border_values is not None and getattr(args, 'hip_border_value', 0.0):
+    raise util.InputError('--hip-border-value or --hip-border-values, not '
+                          'both')
   if border is not None:
-    border = [m.strip() for m in border.split(',')]
-    border = border * stencil.dim if len(border) == 1 else border
-    runtime._border_modes(border, stencil.dim)     # an InputError, before any
+    border = parse_border(border, stencil.dim)
+    if isinstance(border, str):
+      border = [border] * stencil.dim
+    runtime._border_faces(border, stencil.dim)     # an InputError, before any
                                                    # kernel is built
+    border_values = getattr(args, 'hip_border_value', 0.0) \
+        if border_values is None else parse_border_values(border_values,
+                                                          stencil.dim)
   if gpus > 1:
     # one host thread, N GPUs: slabs along the streamed dimension
     devices = ([args.hip_device] * gpus if getattr(args, 'hip_virtual', False)
@@ -346,8 +391,7 @@ def run(stencil: core.Stencil, args: argparse.Namespace) -> None:
           p.fused_iters for p in prog.module.passes)}
     elif border is not None:
       depth = getattr(args, 'hip_border_depth', None)
-      outputs = prog.run_bordered(inputs, border,
-                                  getattr(args, 'hip_border_value', 0.0),
+      outputs = prog.run_bordered(inputs, border, border_values,
                                   depth=1 if depth is None else depth)
       extra = {'border': border, 'border_depth': 1 if depth is None else depth}
     else:

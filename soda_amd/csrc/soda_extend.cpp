@@ -87,4 +87,80 @@ int soda_hip_extend_host(void* array, int32_t elem_bytes, int32_t dim,
   return SODA_HIP_OK;
 }
 
+// The same with a mode per FACE and a constant per (dimension, side)
+// (DESIGN.md 4.16): below the domain the map of the dimension's low face,
+// above it that of its high face; a cell outside through constant faces takes
+// the constant of the HIGHEST such dimension, and of that face.
+int soda_hip_extend_faces_host(void* array, int32_t elem_bytes, int32_t dim,
+                               const int32_t* extent, const int32_t* ghost_lo,
+                               const int32_t* ghost_hi,
+                               const int32_t* modes_lo,
+                               const int32_t* modes_hi,
+                               const uint64_t* constants) {
+  if (!array || !extent || !ghost_lo || !ghost_hi || !modes_lo || !modes_hi ||
+      !constants || dim < 1 || dim > SODA_HIP_MAX_DIM ||
+      (elem_bytes != 1 && elem_bytes != 2 && elem_bytes != 4 &&
+       elem_bytes != 8))
+    return SODA_HIP_ERR_INVALID;
+  int64_t n[SODA_HIP_MAX_DIM] = {1, 1, 1, 1}, lo[SODA_HIP_MAX_DIM] = {0, 0, 0, 0};
+  int64_t p[SODA_HIP_MAX_DIM] = {1, 1, 1, 1};
+  int32_t ml[SODA_HIP_MAX_DIM] = {0, 0, 0, 0}, mh[SODA_HIP_MAX_DIM] = {0, 0, 0, 0};
+  // the cells' bytes, lowest first, whatever the host's byte order
+  unsigned char cst[SODA_HIP_MAX_DIM][2][8] = {};
+  for (int d = 0; d < dim; ++d) {
+    if (extent[d] < 1 || ghost_lo[d] < 0 || ghost_hi[d] < 0 ||
+        modes_lo[d] < SODA_HIP_BORDER_WRAP ||
+        modes_lo[d] > SODA_HIP_BORDER_CONSTANT ||
+        modes_hi[d] < SODA_HIP_BORDER_WRAP ||
+        modes_hi[d] > SODA_HIP_BORDER_CONSTANT ||
+        // a dimension wraps on both faces or on none
+        (modes_lo[d] == SODA_HIP_BORDER_WRAP) !=
+            (modes_hi[d] == SODA_HIP_BORDER_WRAP))
+      return SODA_HIP_ERR_INVALID;
+    n[d] = extent[d];
+    lo[d] = ghost_lo[d];
+    p[d] = lo[d] + n[d] + ghost_hi[d];
+    ml[d] = modes_lo[d];
+    mh[d] = modes_hi[d];
+    for (int side = 0; side < 2; ++side)
+      for (int b = 0; b < 8; ++b)
+        cst[d][side][b] = (unsigned char)(constants[2 * d + side] >> (8 * b));
+  }
+  auto face = [&](int d, int64_t c) {
+    const int64_t j = c - lo[d];
+    return map(j, n[d], j < 0 ? ml[d] : mh[d]);
+  };
+  char* base = static_cast<char*>(array);
+  for (int64_t c3 = 0; c3 < p[3]; ++c3)
+    for (int64_t c2 = 0; c2 < p[2]; ++c2)
+      for (int64_t c1 = 0; c1 < p[1]; ++c1) {
+        const int64_t c[4] = {0, c1, c2, c3};
+        int64_t s[4] = {0, 0, 0, 0};
+        const unsigned char* rowc = nullptr;     // ascending: the highest stays
+        for (int d = 1; d < 4; ++d) {
+          s[d] = face(d, c[d]);
+          if (s[d] < 0) {
+            rowc = cst[d][c[d] < lo[d] ? 0 : 1];
+            s[d] = 0;
+          }
+        }
+        const int64_t drow = ((c3 * p[2] + c2) * p[1] + c1) * p[0];
+        const int64_t srow =
+            (((lo[3] + s[3]) * p[2] + lo[2] + s[2]) * p[1] + lo[1] + s[1]) *
+            p[0];
+        for (int64_t c0 = 0; c0 < p[0]; ++c0) {
+          const int64_t s0 = face(0, c0);
+          char* cell = base + (drow + c0) * elem_bytes;
+          if (rowc)
+            memcpy(cell, rowc, (size_t)elem_bytes);
+          else if (s0 < 0)
+            memcpy(cell, cst[0][c0 < lo[0] ? 0 : 1], (size_t)elem_bytes);
+          else if (srow + lo[0] + s0 != drow + c0)     // a ghost cell
+            memcpy(cell, base + (srow + lo[0] + s0) * elem_bytes,
+                   (size_t)elem_bytes);
+        }
+      }
+  return SODA_HIP_OK;
+}
+
 }  // extern "C"

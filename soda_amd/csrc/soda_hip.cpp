@@ -149,6 +149,7 @@ size_t soda_hip_sizeof(int which) {
     case 19: return sizeof(soda_hip_border_strip_t);
     case 20: return sizeof(soda_hip_border_fused_info_t);
     case 21: return sizeof(soda_hip_border_fused_boxes_t);
+    case 22: return sizeof(soda_hip_border_faces_t);
     default: return 0;
   }
 }

@@ -33,6 +33,7 @@
 #include "soda_internal.h"
 
 #include <cstddef>
+#include <cstdlib>
 #include <cstring>
 #include <new>
 
@@ -73,18 +74,33 @@ struct ExtendArgs {
   uint64_t constant[16];
 };
 
-// a batched wrap or extend kernel's (soda_rt_domain_batch.h): its unbatched
-// block, then the cells from an item to the next in the destination and in
-// the source.  Room for the steps behind either block
+// the faces kernel's (soda_rt_faces.h): the same block, then
+// a mode per face and, per tensor, a constant per face
+struct FacesArgs {
+  WrapArgs w;
+  int32_t mode_lo[4];
+  int32_t mode_hi[4];
+  uint64_t constant[16][4][2];
+};
+
+// a batched wrap, extend or faces kernel's (soda_rt_domain_batch.h): its
+// unbatched block, then the cells from an item to the next in the destination
+// and in the source.  Room for the steps behind any of the blocks, which all
+// begin with the wrap kernel's
 struct DomainArgs {
-  ExtendArgs e;
+  union {
+    ExtendArgs e;
+    FacesArgs f;
+  };
   uint64_t steps[2];
 };
 // (the kernels' struct puts the steps at the block's size: no padding)
 static_assert(sizeof(WrapArgs) % alignof(uint64_t) == 0 &&
                   sizeof(ExtendArgs) % alignof(uint64_t) == 0 &&
-                  offsetof(DomainArgs, steps) == sizeof(ExtendArgs),
-              "the item steps lie right behind either block");
+                  sizeof(FacesArgs) % alignof(uint64_t) == 0 &&
+                  sizeof(ExtendArgs) <= sizeof(FacesArgs) &&
+                  offsetof(DomainArgs, steps) == sizeof(FacesArgs),
+              "the item steps lie right behind any block");
 
 // the box kernel's one argument, as soda_rt_box.h declares it
 struct BoxArgs {
@@ -134,8 +150,14 @@ struct Frame {
   const Kind* kind = &kTorus;
   int32_t mode[4] = {0, 0, 0, 0};      // kBorder: SODA_HIP_BORDER_* ...
   uint64_t constant[SODA_HIP_MAX_TENSORS] = {};   // ... and per input
+  // kBorder, a request whose faces differ: `mode` the low
+  // faces, these the high ones and the constants per input, dimension, side
+  bool faces = false;
+  int32_t mode_hi[4] = {0, 0, 0, 0};
+  uint64_t face_constant[SODA_HIP_MAX_TENSORS][4][2] = {};
   Torus t;
-  Helpers wrap;                        // the wrap or the extend kernels
+  Helpers wrap;                        // the wrap, the extend or (`faces`)
+                                       // the faces kernels
   int32_t batch = 0;                   // > 0: a batched handle, every array
                                        // that many items, `wrap` the _bt
                                        // kernels
@@ -252,7 +274,9 @@ int wrap_launch(const Frame& f, WrapJob job, void* const* dst,
                 hipStream_t stream) {
   // the wrap kernel takes the block without the border behind it, a batched
   // kernel the item steps behind its block
-  const size_t block = f.kind->extend ? sizeof(ExtendArgs) : sizeof(WrapArgs);
+  const size_t block = f.faces          ? sizeof(FacesArgs)
+                       : f.kind->extend ? sizeof(ExtendArgs)
+                                        : sizeof(WrapArgs);
   const uint64_t padded = (uint64_t)cells_of(f.t.p, f.t.dim);
   const uint64_t dense = (uint64_t)cells_of(f.t.n, f.t.dim);
   const uint64_t steps[2] = {job == kCrop ? dense : padded,
@@ -263,12 +287,26 @@ int wrap_launch(const Frame& f, WrapJob job, void* const* dst,
       [&](int size, const int* tensor, int m, DomainArgs* all,
           uint64_t* total) -> int {
         ExtendArgs* args = &all->e;
-        for (int j = 0; j < m; ++j) {
-          args->w.dst[j] = dst[tensor[j]];
-          args->w.src[j] = src[tensor[j]];
-          args->constant[j] = f.constant[tensor[j]];
+        if (f.faces) {      // the same block, the faces kernel's border behind
+          FacesArgs* fa = &all->f;
+          for (int j = 0; j < m; ++j) {
+            fa->w.dst[j] = dst[tensor[j]];
+            fa->w.src[j] = src[tensor[j]];
+            memcpy(fa->constant[j], f.face_constant[tensor[j]],
+                   sizeof fa->constant[j]);
+          }
+          for (int d = 0; d < 4; ++d) {
+            fa->mode_lo[d] = f.mode[d];
+            fa->mode_hi[d] = f.mode_hi[d];
+          }
+        } else {
+          for (int j = 0; j < m; ++j) {
+            args->w.dst[j] = dst[tensor[j]];
+            args->w.src[j] = src[tensor[j]];
+            args->constant[j] = f.constant[tensor[j]];
+          }
+          for (int d = 0; d < 4; ++d) args->mode[d] = f.mode[d];
         }
-        for (int d = 0; d < 4; ++d) args->mode[d] = f.mode[d];
         if (!wrap_regions(f.t, job, size, &args->w))
           return fail(SODA_HIP_ERR_INVALID,
                       std::string(f.kind->who) +
@@ -566,6 +604,88 @@ int border_modes(const soda_hip_plan_t* plan,
   return SODA_HIP_OK;
 }
 
+// A bordered request with its faces resolved.
+struct FaceRule {
+  bool asymmetric;          // a pair of faces or a tensor's constants differ
+  int32_t mode_hi[4];
+  uint64_t constant[SODA_HIP_MAX_TENSORS][4][2];
+  // the request of soda_hip_border_*: the low faces as its modes, per input
+  // the constant of dimension 0's low face.  A symmetric request IS this one;
+  // an asymmetric one has its geometry (the same wall dimensions)
+  soda_hip_border_desc_t low;
+};
+
+// The faces of a request checked and resolved; `faces` NULL: the desc's own.
+int border_faces(const soda_hip_plan_t* plan,
+                 const soda_hip_border_desc_t* desc,
+                 const soda_hip_border_faces_t* faces, FaceRule* out) {
+  memset(out, 0, sizeof *out);
+  out->low = *desc;
+  const int dim = plan->dim < 0                  ? 0
+                  : plan->dim > SODA_HIP_MAX_DIM ? SODA_HIP_MAX_DIM
+                                                 : plan->dim;
+  const int nin = plan->num_inputs < 0 ? 0
+                  : plan->num_inputs > SODA_HIP_MAX_TENSORS
+                      ? SODA_HIP_MAX_TENSORS
+                      : plan->num_inputs;
+  bool all_wrap = true;
+  for (int d = 0; d < dim; ++d) {
+    const int32_t lo = desc->mode[d], hi = faces ? faces->mode_hi[d] : lo;
+    if (lo < SODA_HIP_BORDER_WRAP || lo > SODA_HIP_BORDER_CONSTANT ||
+        hi < SODA_HIP_BORDER_WRAP || hi > SODA_HIP_BORDER_CONSTANT)
+      return fail(SODA_HIP_ERR_INVALID,
+                  "border: a face mode that is none of SODA_HIP_BORDER_*; "
+                  "nothing was launched");
+    if ((lo == SODA_HIP_BORDER_WRAP) != (hi == SODA_HIP_BORDER_WRAP))
+      return fail(SODA_HIP_ERR_INVALID,
+                  "border: a dimension wraps on both faces or on none (wrap "
+                  "on one face only is not served); nothing was launched");
+    if (lo != SODA_HIP_BORDER_WRAP) all_wrap = false;
+    if (lo != hi) out->asymmetric = true;
+    out->mode_hi[d] = hi;
+  }
+  if (!all_wrap && desc->domain.refill_every > 1)
+    return fail(SODA_HIP_ERR_INVALID,
+                "border: only a wrapped ghost evolves with its interior: with "
+                "any other mode the frame is refilled after every iteration "
+                "(refill_every 0 or 1); nothing was launched");
+  const bool per_face = faces && faces->per_face_constants;
+  for (int i = 0; i < nin; ++i) {
+    const uint64_t first = per_face ? faces->constant[i][0][0]
+                                    : desc->constant[i];
+    out->low.constant[i] = first;
+    for (int d = 0; d < dim; ++d)
+      for (int side = 0; side < 2; ++side) {
+        const uint64_t c = per_face ? faces->constant[i][d][side] : first;
+        out->constant[i][d][side] = c;
+      }
+  }
+  // Only a CONSTANT face ever shows its constant: a tensor's constants are
+  // one where those of its CONSTANT faces are, and that one is the request's
+  for (int i = 0; i < nin && per_face; ++i) {
+    bool seen = false;
+    uint64_t shown = out->low.constant[i];
+    for (int d = 0; d < dim; ++d)
+      for (int side = 0; side < 2; ++side) {
+        const int32_t m = side ? out->mode_hi[d] : desc->mode[d];
+        if (m != SODA_HIP_BORDER_CONSTANT) continue;
+        if (seen && out->constant[i][d][side] != shown) out->asymmetric = true;
+        if (!seen) shown = out->constant[i][d][side];
+        seen = true;
+      }
+    out->low.constant[i] = shown;
+  }
+  return SODA_HIP_OK;
+}
+
+// SODA_HIP_FACES_FORCE=1 (A/B runs, tools/faces_ab.py; read once per handle,
+// when it is made): a create twin that is given the faces module serves a
+// symmetric request with it too
+bool faces_forced() {
+  const char* g = getenv("SODA_HIP_FACES_FORCE");
+  return g && !strcmp(g, "1");
+}
+
 // soda_hip_border_fused_plan: a handle on the domain whose
 // chunks run fused on P, and per wall dimension a handle of the same kind on
 // a narrow strip that advances the cells near the two walls one iteration at
@@ -740,8 +860,10 @@ int create_core(const Kind& kind, soda_hip_program_t* p,
                 const soda_hip_periodic_desc_t* desc, const int32_t* mode,
                 const uint64_t* constant, const void* const* code,
                 const size_t* code_size, soda_hip_periodic** handle,
-                int32_t batch = 0) {
+                int32_t batch = 0, const FaceRule* rule = nullptr) {
+  // (`rule`: a handle that fills by the faces kernels, `code` their modules)
   const std::string who(kind.who);
+  const char* what = rule ? "faces" : "wrap";
   const soda_hip_plan_t& plan = p->plan;
   if (p->bank_tensors)
     return fail(SODA_HIP_ERR_UNSUPPORTED,
@@ -753,7 +875,7 @@ int create_core(const Kind& kind, soda_hip_program_t* p,
     return rc;
   const int nin = plan.num_inputs, nout = plan.num_outputs;
   bool need[4] = {false, false, false, false};
-  if (int rc = helpers_needed(plan, code, code_size, who, "wrap", need))
+  if (int rc = helpers_needed(plan, code, code_size, who, what, need))
     return rc;
   HIP_TRY(hipSetDevice(p->device));
   soda_hip_periodic* h = new (std::nothrow) soda_hip_periodic;
@@ -774,8 +896,13 @@ int create_core(const Kind& kind, soda_hip_program_t* p,
   }
   if (constant)
     for (int i = 0; i < nin; ++i) h->constant[i] = constant[i];
-  int rc = load_helpers(&h->wrap, need, code, kind.kernel, plan.dim, who,
-                        "wrap", batch > 0);
+  if (rule) {
+    h->faces = true;
+    memcpy(h->mode_hi, rule->mode_hi, sizeof h->mode_hi);
+    memcpy(h->face_constant, rule->constant, sizeof h->face_constant);
+  }
+  int rc = load_helpers(&h->wrap, need, code, rule ? "soda_faces" : kind.kernel,
+                        plan.dim, who, what, batch > 0);
   // (a batched handle: every array [batch, P...])
   const int64_t cells = cells_of(h->t.p, plan.dim) * h->items();
   h->pad_in.resize(nin);
@@ -1510,13 +1637,16 @@ int soda_hip_border_fused_plan(const soda_hip_plan_t* plan,
                          &all_wrap);
 }
 
-int soda_hip_border_fused_create(soda_hip_program_t* p,
-                                 const soda_hip_border_fused_desc_t* desc,
-                                 const void* const* code,
-                                 const size_t* code_size,
-                                 const void* const* box_code,
-                                 const size_t* box_code_size,
-                                 soda_hip_border_fused_t** handle) {
+// soda_hip_border_fused_create; `rule`: of its _faces twin on a request served
+// by the faces kernels, `code` their modules -- the main
+// handle and every strip take the request's faces and constants
+static int fused_create(soda_hip_program_t* p,
+                        const soda_hip_border_fused_desc_t* desc,
+                        const void* const* code, const size_t* code_size,
+                        const void* const* box_code,
+                        const size_t* box_code_size,
+                        soda_hip_border_fused_t** handle,
+                        const FaceRule* rule) {
   if (handle) *handle = nullptr;
   if (!p || !desc || !code || !code_size || !box_code || !box_code_size ||
       !handle)
@@ -1538,14 +1668,15 @@ int soda_hip_border_fused_create(soda_hip_program_t* p,
   soda_hip_periodic_desc_t domain = desc->border.domain;
   domain.refill_every = all_wrap ? info.depth : 1;
   int rc = create_core(kBorder, p, &domain, desc->border.mode,
-                       desc->border.constant, code, code_size, &f->main);
+                       desc->border.constant, code, code_size, &f->main, 0,
+                       rule);
   for (int i = 0; i < info.num_strips && !rc; ++i) {
     const soda_hip_border_strip_t& s = info.strip[i];
     soda_hip_border_fused::Strip& mine = f->strip[i];
     soda_hip_periodic_desc_t sdom = domain;
     sdom.extent[s.dim] = s.lo + s.hi;
     rc = create_core(kBorder, p, &sdom, desc->border.mode,
-                     desc->border.constant, code, code_size, &mine.h);
+                     desc->border.constant, code, code_size, &mine.h, 0, rule);
     if (rc) break;
     mine.d = s.dim;
     mine.lo = s.lo;
@@ -1565,6 +1696,17 @@ int soda_hip_border_fused_create(soda_hip_program_t* p,
   residual_boxes(info, domain.extent, plan.dim, &f->boxes);
   *handle = f;
   return SODA_HIP_OK;
+}
+
+int soda_hip_border_fused_create(soda_hip_program_t* p,
+                                 const soda_hip_border_fused_desc_t* desc,
+                                 const void* const* code,
+                                 const size_t* code_size,
+                                 const void* const* box_code,
+                                 const size_t* box_code_size,
+                                 soda_hip_border_fused_t** handle) {
+  return fused_create(p, desc, code, code_size, box_code, box_code_size,
+                      handle, nullptr);
 }
 
 int soda_hip_border_fused_destroy(soda_hip_border_fused_t* f) {
@@ -1648,6 +1790,171 @@ int soda_hip_border_fused_residual_boxes(
     return rc;
   residual_boxes(info, desc->border.domain.extent, plan->dim, boxes);
   return SODA_HIP_OK;
+}
+
+// -- a mode and a constant per face: the _faces twins -------
+// Each resolves the faces, then IS the entry it is named after on the request
+// of the low faces -- all there is to a plan, whose geometry knows the wall
+// dimensions only, and to a symmetric create -- or, for an asymmetric create,
+// that entry's core with the faces kernels in the extend kernels' place.
+
+// whether a create twin fills by the faces kernels; their modules, then
+static int faces_serve(const FaceRule& rule, const void* const* faces_code,
+                       const size_t* faces_code_size, const char* who,
+                       bool* serve) {
+  *serve = rule.asymmetric || (faces_forced() && faces_code && faces_code_size);
+  if (*serve && (!faces_code || !faces_code_size))
+    return fail(SODA_HIP_ERR_INVALID,
+                std::string(who) + ": the faces differ and the faces modules "
+                                   "are NULL; nothing was launched");
+  return SODA_HIP_OK;
+}
+
+int soda_hip_border_plan_faces(const soda_hip_plan_t* plan,
+                               const soda_hip_border_desc_t* desc,
+                               const soda_hip_border_faces_t* faces,
+                               int32_t iterate, soda_hip_periodic_info_t* info,
+                               int32_t capacity, int32_t* chunks,
+                               int32_t* count) {
+  if (!plan || !desc)
+    return fail(SODA_HIP_ERR_INVALID, "border_plan_faces: NULL argument");
+  FaceRule rule;
+  if (int rc = border_faces(plan, desc, faces, &rule)) return rc;
+  return soda_hip_border_plan(plan, &rule.low, iterate, info, capacity, chunks,
+                              count);
+}
+
+int soda_hip_border_plan_batch_faces(const soda_hip_plan_t* plan,
+                                     const soda_hip_border_desc_t* desc,
+                                     const soda_hip_border_faces_t* faces,
+                                     int32_t batch, int32_t iterate,
+                                     soda_hip_periodic_info_t* info,
+                                     int32_t capacity, int32_t* chunks,
+                                     int32_t* count) {
+  if (!plan || !desc)
+    return fail(SODA_HIP_ERR_INVALID,
+                "border_plan_batch_faces: NULL argument");
+  if (int rc = check_domain_batch(*plan, batch, "border_plan_batch_faces"))
+    return rc;
+  FaceRule rule;
+  if (int rc = border_faces(plan, desc, faces, &rule)) return rc;
+  return soda_hip_border_plan_batch(plan, &rule.low, batch, iterate, info,
+                                    capacity, chunks, count);
+}
+
+int soda_hip_border_create_faces(soda_hip_program_t* p,
+                                 const soda_hip_border_desc_t* desc,
+                                 const soda_hip_border_faces_t* faces,
+                                 const void* const* code,
+                                 const size_t* code_size,
+                                 const void* const* faces_code,
+                                 const size_t* faces_code_size,
+                                 soda_hip_border_t** handle) {
+  if (handle) *handle = nullptr;
+  if (!p || !desc || !handle)
+    return fail(SODA_HIP_ERR_INVALID, "border_create_faces: NULL argument");
+  FaceRule rule;
+  if (int rc = border_faces(&p->plan, desc, faces, &rule)) return rc;
+  bool serve;
+  if (int rc = faces_serve(rule, faces_code, faces_code_size,
+                           "border_create_faces", &serve))
+    return rc;
+  if (!serve)
+    return soda_hip_border_create(p, &rule.low, code, code_size, handle);
+  bool all_wrap;
+  if (int rc = border_modes(&p->plan, &rule.low, &all_wrap)) return rc;
+  soda_hip_periodic_desc_t domain = rule.low.domain;
+  if (!all_wrap && domain.refill_every == 0) domain.refill_every = 1;
+  return create_core(kBorder, p, &domain, rule.low.mode, rule.low.constant,
+                     faces_code, faces_code_size, handle, 0, &rule);
+}
+
+int soda_hip_border_create_batch_faces(soda_hip_program_t* p,
+                                       const soda_hip_border_desc_t* desc,
+                                       const soda_hip_border_faces_t* faces,
+                                       int32_t batch, const void* const* code,
+                                       const size_t* code_size,
+                                       const void* const* faces_code,
+                                       const size_t* faces_code_size,
+                                       soda_hip_border_t** handle) {
+  if (handle) *handle = nullptr;
+  if (!p || !desc || !handle)
+    return fail(SODA_HIP_ERR_INVALID,
+                "border_create_batch_faces: NULL argument");
+  if (int rc = check_domain_batch(p->plan, batch, "border_create_batch_faces"))
+    return rc;
+  FaceRule rule;
+  if (int rc = border_faces(&p->plan, desc, faces, &rule)) return rc;
+  bool serve;
+  if (int rc = faces_serve(rule, faces_code, faces_code_size,
+                           "border_create_batch_faces", &serve))
+    return rc;
+  if (!serve)
+    return soda_hip_border_create_batch(p, &rule.low, batch, code, code_size,
+                                        handle);
+  bool all_wrap;
+  if (int rc = border_modes(&p->plan, &rule.low, &all_wrap)) return rc;
+  soda_hip_periodic_desc_t domain = rule.low.domain;
+  if (!all_wrap && domain.refill_every == 0) domain.refill_every = 1;
+  return create_core(kBorder, p, &domain, rule.low.mode, rule.low.constant,
+                     faces_code, faces_code_size, handle, batch, &rule);
+}
+
+int soda_hip_border_fused_plan_faces(const soda_hip_plan_t* plan,
+                                     const soda_hip_border_fused_desc_t* desc,
+                                     const soda_hip_border_faces_t* faces,
+                                     int32_t iterate,
+                                     soda_hip_border_fused_info_t* info,
+                                     int32_t capacity, int32_t* chunks,
+                                     int32_t* count) {
+  if (!plan || !desc)
+    return fail(SODA_HIP_ERR_INVALID,
+                "border_fused_plan_faces: NULL argument");
+  FaceRule rule;
+  if (int rc = border_faces(plan, &desc->border, faces, &rule)) return rc;
+  soda_hip_border_fused_desc_t low = *desc;
+  low.border = rule.low;
+  return soda_hip_border_fused_plan(plan, &low, iterate, info, capacity,
+                                    chunks, count);
+}
+
+int soda_hip_border_fused_create_faces(
+    soda_hip_program_t* p, const soda_hip_border_fused_desc_t* desc,
+    const soda_hip_border_faces_t* faces, const void* const* code,
+    const size_t* code_size, const void* const* box_code,
+    const size_t* box_code_size, const void* const* faces_code,
+    const size_t* faces_code_size, soda_hip_border_fused_t** handle) {
+  if (handle) *handle = nullptr;
+  if (!p || !desc || !handle)
+    return fail(SODA_HIP_ERR_INVALID,
+                "border_fused_create_faces: NULL argument");
+  FaceRule rule;
+  if (int rc = border_faces(&p->plan, &desc->border, faces, &rule)) return rc;
+  bool serve;
+  if (int rc = faces_serve(rule, faces_code, faces_code_size,
+                           "border_fused_create_faces", &serve))
+    return rc;
+  soda_hip_border_fused_desc_t low = *desc;
+  low.border = rule.low;
+  if (!serve)
+    return soda_hip_border_fused_create(p, &low, code, code_size, box_code,
+                                        box_code_size, handle);
+  return fused_create(p, &low, faces_code, faces_code_size, box_code,
+                      box_code_size, handle, &rule);
+}
+
+int soda_hip_border_fused_residual_boxes_faces(
+    const soda_hip_plan_t* plan, const soda_hip_border_fused_desc_t* desc,
+    const soda_hip_border_faces_t* faces,
+    soda_hip_border_fused_boxes_t* boxes) {
+  if (!plan || !desc || !boxes)
+    return fail(SODA_HIP_ERR_INVALID,
+                "border_fused_residual_boxes_faces: NULL argument");
+  FaceRule rule;
+  if (int rc = border_faces(plan, &desc->border, faces, &rule)) return rc;
+  soda_hip_border_fused_desc_t low = *desc;
+  low.border = rule.low;
+  return soda_hip_border_fused_residual_boxes(plan, &low, boxes);
 }
 
 // -- the entries every kind of handle has -----------

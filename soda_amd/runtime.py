@@ -268,6 +268,16 @@ class BorderDesc(ctypes.Structure):
               ('constant', ctypes.c_uint64 * MAX_TENSORS)]
 
 
+class BorderFaces(ctypes.Structure):
+  """Mirror of soda_hip_border_faces_t: the high face's mode per dimension
+  (BorderDesc.mode becomes the low face's) and a constant per input tensor,
+  dimension and side."""
+  _fields_ = [('mode_hi', ctypes.c_int32 * MAX_DIM),
+              ('per_face_constants', ctypes.c_int32),
+              ('reserved', ctypes.c_int32 * 3),
+              ('constant', ((ctypes.c_uint64 * 2) * MAX_DIM) * MAX_TENSORS)]
+
+
 class BorderFusedDesc(ctypes.Structure):
   """Mirror of soda_hip_border_fused_desc_t: a bordered request, the fusion
   depth, what one iteration reaches."""
@@ -464,6 +474,45 @@ API = {
     'soda_hip_border_fused_residual_boxes': (ctypes.c_int, [
         ctypes.POINTER(Plan), ctypes.POINTER(BorderFusedDesc),
         ctypes.POINTER(BorderFusedBoxes)
+    ]),
+    'soda_hip_extend_faces_host': (ctypes.c_int, [
+        _vp, _i32, _i32, _pi32, _pi32, _pi32, _pi32, _pi32,
+        ctypes.POINTER(ctypes.c_uint64)
+    ]),
+    'soda_hip_border_plan_faces': (ctypes.c_int, [
+        ctypes.POINTER(Plan), ctypes.POINTER(BorderDesc),
+        ctypes.POINTER(BorderFaces), _i32, ctypes.POINTER(PeriodicInfo), _i32,
+        _pi32, _pi32
+    ]),
+    'soda_hip_border_plan_batch_faces': (ctypes.c_int, [
+        ctypes.POINTER(Plan), ctypes.POINTER(BorderDesc),
+        ctypes.POINTER(BorderFaces), _i32, _i32, ctypes.POINTER(PeriodicInfo),
+        _i32, _pi32, _pi32
+    ]),
+    'soda_hip_border_create_faces': (ctypes.c_int, [
+        _vp, ctypes.POINTER(BorderDesc), ctypes.POINTER(BorderFaces), _pvp,
+        ctypes.POINTER(ctypes.c_size_t), _pvp, ctypes.POINTER(ctypes.c_size_t),
+        ctypes.POINTER(_vp)
+    ]),
+    'soda_hip_border_create_batch_faces': (ctypes.c_int, [
+        _vp, ctypes.POINTER(BorderDesc), ctypes.POINTER(BorderFaces), _i32,
+        _pvp, ctypes.POINTER(ctypes.c_size_t), _pvp,
+        ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(_vp)
+    ]),
+    'soda_hip_border_fused_plan_faces': (ctypes.c_int, [
+        ctypes.POINTER(Plan), ctypes.POINTER(BorderFusedDesc),
+        ctypes.POINTER(BorderFaces), _i32, ctypes.POINTER(BorderFusedInfo),
+        _i32, _pi32, _pi32
+    ]),
+    'soda_hip_border_fused_create_faces': (ctypes.c_int, [
+        _vp, ctypes.POINTER(BorderFusedDesc), ctypes.POINTER(BorderFaces),
+        _pvp, ctypes.POINTER(ctypes.c_size_t), _pvp,
+        ctypes.POINTER(ctypes.c_size_t), _pvp,
+        ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(_vp)
+    ]),
+    'soda_hip_border_fused_residual_boxes_faces': (ctypes.c_int, [
+        ctypes.POINTER(Plan), ctypes.POINTER(BorderFusedDesc),
+        ctypes.POINTER(BorderFaces), ctypes.POINTER(BorderFusedBoxes)
     ]),
     **{
         'soda_hip_%s_%s' % (handle, name): (ctypes.c_int, argtypes)
@@ -1522,18 +1571,22 @@ def periodic_plan(plan: Plan, extent: Sequence[int], refill_every: int,
 
 
 def _plan_call(what: str, plan: Plan, desc, raw, iterate: int,
-               batch: Optional[int] = None):
+               batch: Optional[int] = None, faces=None):
   """The plan entry soda_hip_<what> on `desc` -- `batch` an integer:
-  soda_hip_<what>_batch -- : (`raw`, the info struct, filled; the iterations
-  of every chunk of a run of `iterate`)."""
+  soda_hip_<what>_batch; `faces` a BorderFaces: the `_faces` twin of either
+  -- : (`raw`, the info struct, filled; the iterations of every chunk of a run
+  of `iterate`)."""
   cap = max(1, iterate)
   chunks = (ctypes.c_int32 * cap)()
   n = ctypes.c_int32()
   if batch is not None:
     what += '_batch'
+  if faces is not None:
+    what += '_faces'
   fn = getattr(library(), 'soda_hip_' + what)
   head = (ctypes.byref(plan), ctypes.byref(desc)) + (
-      () if batch is None else (int(batch),))
+      () if faces is None else (ctypes.byref(faces),)) + (
+          () if batch is None else (int(batch),))
   check(fn(*head, iterate, ctypes.byref(raw), cap, chunks, ctypes.byref(n)),
         what)
   return raw, list(chunks[:n.value])
@@ -1583,7 +1636,9 @@ class Periodic:
     for resource in resources:
       codes = (ctypes.c_void_p * 4)()
       sizes = (ctypes.c_size_t * 4)()
-      if not st.preserve_border:    # (refused by create: nothing to build for)
+      if resource is None:          # (a module the request never looks at)
+        pass
+      elif not st.preserve_border:  # (refused by create: nothing to build for)
         sizes_needed = {t.size_in_bytes
                         for t in list(st.input_types) + list(st.output_types)}
         for elem in sorted(sizes_needed & {1, 2, 4, 8}):
@@ -1607,24 +1662,32 @@ class Periodic:
     self.batch = None if batch is None else int(batch)
     prog._check_extent(self.extent)
     if modes is not None:
-      self.modes = tuple([modes] * st.dim if isinstance(modes, str) else modes)
+      self.modes = _mode_names(modes, st.dim)
     return list(st.input_types) != list(st.output_types)
 
-  def _create(self, desc, resources, where: str) -> None:
+  def _create(self, desc, resources, where: str, faces=None) -> None:
     """What every constructor ends with: the handle made by the library's
     create entry from `desc` and the code objects of `resources`, and
-    registered with its program.  `where`: the domain, for a refusal."""
+    registered with its program.  `where`: the domain, for a refusal.
+    `faces`: a BorderFaces, and the `_faces` twin of the entry -- with the
+    faces modules behind the others and without the extend modules, which
+    such a request never looks at."""
     self._lib = library()
     self._handle = ctypes.c_void_p()
+    head, twin = (ctypes.byref(desc),), ''
+    if faces is not None:
+      resources = [None if r is extend_resources else r
+                   for r in resources] + [faces_resources]
+      head, twin = (ctypes.byref(desc), ctypes.byref(faces)), '_faces'
     if self.batch is None:
       args = self._codes_of(*resources)
-      status = self._fn('create')(self.prog._handle, ctypes.byref(desc), *args,
-                                  ctypes.byref(self._handle))
+      status = self._fn('create' + twin)(self.prog._handle, *head, *args,
+                                         ctypes.byref(self._handle))
     else:                           # the batched modules, the _batch entry
-      args = self._codes_of(*[functools.partial(r, batch=True)
+      args = self._codes_of(*[r and functools.partial(r, batch=True)
                               for r in resources])
-      status = self._fn('create_batch')(
-          self.prog._handle, ctypes.byref(desc), self.batch, *args,
+      status = self._fn('create_batch' + twin)(
+          self.prog._handle, *head, self.batch, *args,
           ctypes.byref(self._handle))
       where = '%d x %s' % (self.batch, where)
     check(status, '`%s` on %s' % (self.prog.stencil.app_name, where))
@@ -1779,18 +1842,56 @@ class Periodic:
 
 
 # -- bordered domains: a border mode per dimension (DESIGN.md 4.12) -----------
-def _border_modes(modes, dim: int):
-  """SODA_HIP_BORDER_* per dimension of `modes`: one name for all dimensions
-  or one per dimension, dimension 0 first."""
+def _face_pair(entry):
+  """[low, high] of one dimension's entry of `modes`: one name (or number) for
+  both faces, a (low, high) pair, or the string 'low/high'."""
+  if isinstance(entry, str):
+    pair = entry.split('/') if '/' in entry else [entry, entry]
+  elif isinstance(entry, (tuple, list)):
+    pair = list(entry)
+  else:
+    pair = [entry, entry]
+  if len(pair) != 2:
+    raise util.InputError('border: a dimension takes one mode or a (low, high) '
+                          'pair of modes, not %r' % (entry,))
+  return pair
+
+
+def _border_faces(modes, dim: int):
+  """(low, high): SODA_HIP_BORDER_* of the two faces per dimension of `modes`
+  -- one entry for all dimensions or one per dimension, dimension 0 first, an
+  entry one name for both faces, a (low, high) pair of names or the string
+  'low/high' (DESIGN.md 4.16).  `wrap` comes as the pair (wrap, wrap) only."""
   from soda_amd.codegen.hip import extend as _extend
   names = [modes] * dim if isinstance(modes, str) else list(modes)
   if len(names) != dim:
     raise util.InputError('border: one mode, or one per dimension (%d)' % dim)
-  for m in names:
-    if m not in _extend.MODES:
-      raise util.InputError('border: unknown mode %r (one of %s)' % (
-          m, ', '.join(sorted(_extend.MODES))))
-  return [_extend.MODES[m] for m in names]
+  low, high = [], []
+  for entry in names:
+    pair = _face_pair(entry)
+    for m in pair:
+      if not isinstance(m, str) or m not in _extend.MODES:
+        raise util.InputError('border: unknown mode %r (one of %s)' % (
+            m, ', '.join(sorted(_extend.MODES))))
+    if (pair[0] == 'wrap') != (pair[1] == 'wrap'):
+      raise util.InputError('border: a dimension wraps on both faces or on '
+                            'none, not %s/%s' % tuple(pair))
+    low.append(_extend.MODES[pair[0]])
+    high.append(_extend.MODES[pair[1]])
+  return low, high
+
+
+def _border_modes(modes, dim: int):
+  """SODA_HIP_BORDER_* per dimension of `modes` (_border_faces): of the LOW
+  faces, which say as much as both about which dimensions wrap."""
+  return _border_faces(modes, dim)[0]
+
+
+def _mode_names(modes, dim: int):
+  """`modes` one string per dimension, a pair as 'low/high'."""
+  names = [modes] * dim if isinstance(modes, str) else list(modes)
+  return tuple(m if isinstance(m, str) else '/'.join(map(str, m))
+               for m in names)
 
 
 def _cell_bits(value, np_name: str) -> int:
@@ -1815,23 +1916,113 @@ def _border_constants(stencil: core.Stencil, constants):
           for n, t in zip(stencil.input_names, stencil.input_types)]
 
 
+def _per_face(spec, dim: int, what: str):
+  """[[low, high]] * dim of the constants of one tensor: `spec` a scalar (every
+  face), or a sequence of `dim` entries, each a scalar (both faces of the
+  dimension) or a (low, high) pair; None where `spec` is a scalar."""
+  if not isinstance(spec, (list, tuple)):
+    return None
+  if len(spec) != dim:
+    raise util.InputError('%s: constants per face come one entry per '
+                          'dimension (%d), each a scalar or a (low, high) '
+                          'pair' % (what, dim))
+  out = []
+  for entry in spec:
+    pair = list(entry) if isinstance(entry, (list, tuple)) else [entry, entry]
+    if len(pair) != 2:
+      raise util.InputError('%s: a dimension takes one constant or a (low, '
+                            'high) pair, not %r' % (what, entry))
+    out.append(pair)
+  return out
+
+
+def _border_face_constants(stencil: core.Stencil, constants):
+  """Per input of `stencil` the bits of its constants [dimension][side], or
+  None where every input takes one constant on every face (_border_constants
+  has those): `constants` as for _border_constants, or in a scalar's place a
+  sequence of `dim` entries, each a scalar or a (low, high) pair."""
+  if constants is None:
+    return None
+  if not isinstance(constants, dict):
+    constants = {n: constants for n in stencil.input_names}
+  dim = stencil.dim
+  specs = {n: _per_face(c, dim, 'border') for n, c in constants.items()}
+  if all(s is None for s in specs.values()):
+    return None
+  unknown = sorted(set(constants) - set(stencil.input_names))
+  if unknown:
+    raise util.InputError('border: constants for %s, which are no inputs' %
+                          ', '.join(unknown))
+  table = []
+  for n, t in zip(stencil.input_names, stencil.input_types):
+    spec = specs.get(n) or [[constants.get(n, 0)] * 2] * dim
+    table.append([[_cell_bits(v, t.np_name) for v in pair] for pair in spec])
+  return table
+
+
+def _faces_forced() -> bool:
+  """SODA_HIP_FACES_FORCE=1 (A/B runs, tools/faces_ab.py): a symmetric
+  request goes through the `_faces` entries with the faces modules too."""
+  return os.environ.get('SODA_HIP_FACES_FORCE') == '1'
+
+
+def _shown_constants(low, high, rows):
+  """The constants of one tensor ([dimension][side]) on the faces whose mode
+  is `constant` (SODA_HIP_BORDER_CONSTANT), the only ones that ever show."""
+  return [c for d, pair in enumerate(rows)
+          for m, c in zip((low[d], high[d]), pair) if m == 4]
+
+
+def _border_faces_struct(low, high, table=None, force: bool = False):
+  """The BorderFaces of a request with the faces `low` / `high` and the
+  constants `table` (_border_face_constants), or None where it is the request
+  of the low faces alone: pairs alike, every tensor one constant on the faces
+  that show one (those whose mode is `constant`)."""
+  uneven = table is not None and any(
+      len(set(_shown_constants(low, high, rows))) > 1 for rows in table)
+  if list(low) == list(high) and not uneven and not force:
+    return None
+  faces = BorderFaces()
+  for d, m in enumerate(high):
+    faces.mode_hi[d] = m
+  if table is not None:
+    faces.per_face_constants = 1
+    for i, rows in enumerate(table):
+      for d, pair in enumerate(rows):
+        faces.constant[i][d][0], faces.constant[i][d][1] = pair
+  return faces
+
+
 def extend_host(arr, ghost_lo: Sequence[int], ghost_hi: Sequence[int], modes,
                 constant=0):
   """wrap_host with a border mode per dimension: refills the ghost frame of the
   padded numpy array `arr` IN PLACE from its interior (soda_hip_extend_host,
   plain C++; no GPU needed).  `modes`: one name or one per dimension,
   dimension 0 (the LAST numpy axis) first; `constant`: the value of a ghost
-  cell outside in a `constant` dimension, converted to the cell type.  Returns
-  `arr`."""
+  cell outside in a `constant` dimension, converted to the cell type.  A
+  dimension's mode may be a (low, high) pair or 'low/high', and `constant` a
+  sequence of one entry per dimension, each a scalar or a (low, high) pair
+  (soda_hip_extend_faces_host).  Returns `arr`."""
   import numpy as np
   args = _frame_args(arr, ghost_lo, ghost_hi, 'extend_host', 'a domain')
-  bits = constant if isinstance(constant, (bytes, bytearray)) else \
-      np.asarray(constant).astype(arr.dtype).tobytes()
-  if len(bits) != arr.dtype.itemsize:
-    raise util.InputError('extend_host: a constant of one cell')
-  check(library().soda_hip_extend_host(
-      *args, (ctypes.c_int32 * arr.ndim)(*_border_modes(modes, arr.ndim)),
-      int.from_bytes(bits, sys.byteorder)), 'extend_host')
+  dim = arr.ndim
+  low, high = _border_faces(modes, dim)
+  per_face = _per_face(constant, dim, 'extend_host')
+
+  def cell(value):
+    bits = value if isinstance(value, (bytes, bytearray)) else \
+        np.asarray(value).astype(arr.dtype).tobytes()
+    if len(bits) != arr.dtype.itemsize:
+      raise util.InputError('extend_host: a constant of one cell')
+    return int.from_bytes(bits, sys.byteorder)
+  if per_face is None and low == high:
+    check(library().soda_hip_extend_host(
+        *args, (ctypes.c_int32 * dim)(*low), cell(constant)), 'extend_host')
+    return arr
+  flat = [cell(v) for pair in per_face or [[constant] * 2] * dim for v in pair]
+  check(library().soda_hip_extend_faces_host(
+      *args, (ctypes.c_int32 * dim)(*low), (ctypes.c_int32 * dim)(*high),
+      (ctypes.c_uint64 * (2 * dim))(*flat)), 'extend_host')
   return arr
 
 
@@ -1866,12 +2057,12 @@ def border_plan(plan: Plan, extent: Sequence[int], modes,
   `refill_every` must be 0 or 1 and every chunk is one iteration; with all
   `wrap` this is periodic_plan.  `batch` = N: of a batched handle over N
   domains (soda_hip_border_plan_batch)."""
-  raw_modes = _raw_modes(modes, plan.dim)
+  raw_modes, faces = _raw_faces(modes, plan.dim)
   desc = _border_desc(_periodic_desc(
       plan.dim, extent, refill_every, ghost_lo, ghost_hi, preserve,
       not_iterable), raw_modes, ())
   raw, chunks = _plan_call('border_plan', plan, desc, PeriodicInfo(), iterate,
-                           batch)
+                           batch, faces)
   return _periodic_info(raw, plan.dim), chunks
 
 
@@ -1887,12 +2078,48 @@ def _raw_modes(modes, dim: int, *reaches):
   return raw
 
 
+def _raw_faces(modes, dim: int, *reaches):
+  """(the low faces as _raw_modes gives them, the BorderFaces of the `_faces`
+  twin of a plan entry or None where every pair is alike): `modes` as names
+  (_border_faces), or as raw numbers -- a number or a (low, high) pair of
+  numbers per dimension -- which pass unchecked."""
+  entries = [modes] * dim if isinstance(modes, str) else list(modes)
+  pairs = [_face_pair(m) for m in entries]
+  if entries and all(isinstance(f, int) for p in pairs for f in p):
+    low, high = [p[0] for p in pairs], [p[1] for p in pairs]    # raw numbers
+  else:                           # names: checked, a mixed list among them
+    low, high = _border_faces(modes, dim)
+  _raw_modes(low, dim, *reaches)  # one per dimension, the reaches too
+  return low, _border_faces_struct(low, high)
+
+
+def _border_request(stencil: core.Stencil, modes, constants):
+  """What a bordered handle is made from: (the low faces' SODA_HIP_BORDER_*,
+  the BorderFaces of the `_faces` create entry or None where the request is
+  one of soda_hip_border_create, a constant per input for the desc)."""
+  low, high = _border_faces(modes, stencil.dim)
+  table = _border_face_constants(stencil, constants)
+  flat = [(_shown_constants(low, high, rows) or [rows[0][0]])[0]
+          for rows in table] if table is not None else \
+      _border_constants(stencil, constants)
+  return low, _border_faces_struct(low, high, table, _faces_forced()), flat
+
+
 def extend_resources(elem: int, dim: int, batch: bool = False):
   """(code object, kernel_resources of it) of the extend module of a cell size
   and dimension count -- `batch`: of the batched one --
   JIT-built like every module, cached like them; needs no GPU."""
   from soda_amd.codegen.hip import extend as _extend
   return _helper_resources(_extend, 'extend', elem, dim, batch)
+
+
+def faces_resources(elem: int, dim: int, batch: bool = False):
+  """(code object, kernel_resources of it) of the faces module of a cell size
+  and dimension count (a border mode per face) -- `batch`: of
+  the batched one -- JIT-built like every module, cached like them; needs no
+  GPU."""
+  from soda_amd.codegen.hip import faces as _faces
+  return _helper_resources(_faces, 'faces', elem, dim, batch)
 
 
 class Bordered(Periodic):
@@ -1912,19 +2139,26 @@ class Bordered(Periodic):
     scalar or {input: scalar}, converted to the cell type's bits (default
     zero); an output's ghost takes the constant of the input it replaces.
     `batch` = N: a handle over N domains of `extent`, every array [N, ...]
-    (soda_hip_border_create_batch)."""
+    (soda_hip_border_create_batch).
+    A mode and a constant per FACE: a dimension's entry of
+    `modes` may be a (low, high) pair of names or 'low/high' (`wrap` as the
+    pair of both only); a constant may be a sequence of one entry per
+    dimension, each a scalar or a (low, high) pair.  A request whose pairs
+    are alike and whose constants are one per tensor is the request above,
+    with its kernels; any other fills with the faces kernels
+    (soda_hip_border_create_faces)."""
     not_iterable = self._begin(prog, extent, modes, batch)
     st = prog.stencil
-    raw_modes = _border_modes(modes, st.dim)
+    raw_modes, faces, flat = _border_request(st, modes, constants)
     k = 1
     if not any(raw_modes):          # a torus: Periodic's default
       k = max(p.fused_iters for p in prog.module.passes)
     lo, hi = periodic_ghosts(st, k)
     desc = _border_desc(_periodic_desc(
         st.dim, self.extent, k, lo, hi, st.preserve_border, not_iterable),
-                        raw_modes, _border_constants(st, constants))
+                        raw_modes, flat)
     self._create(desc, [extend_resources], '%s with borders %s' % (
-        'x'.join(map(str, self.extent)), ', '.join(self.modes)))
+        'x'.join(map(str, self.extent)), ', '.join(self.modes)), faces)
 
 
 # -- bordered domains, fused away from the walls (DESIGN.md 4.13) -------------
@@ -2026,12 +2260,12 @@ def border_fused_plan(plan: Plan, extent: Sequence[int], modes, depth: int,
   """border_plan for the fused form (soda_hip_border_fused_plan; no GPU
   needed): (info, chunks), info as BorderedFused.info().  `depth` 0: the
   plan's deepest pass."""
-  raw_modes = _raw_modes(modes, plan.dim, reach_lo, reach_hi)
+  raw_modes, faces = _raw_faces(modes, plan.dim, reach_lo, reach_hi)
   desc = _border_fused_desc(_border_desc(_periodic_desc(
       plan.dim, extent, refill_every, ghost_lo, ghost_hi, preserve,
       not_iterable), raw_modes, ()), depth, reach_lo, reach_hi)
   raw, chunks = _plan_call('border_fused_plan', plan, desc, BorderFusedInfo(),
-                           iterate)
+                           iterate, faces=faces)
   return _border_fused_info(raw, plan.dim), chunks
 
 
@@ -2048,15 +2282,20 @@ def border_fused_residual_boxes(plan: Plan, extent: Sequence[int], modes,
   coordinates of the domain, 'strips': [{'dim', 'low': (lo, hi), 'high': (lo,
   hi)}] in each strip's own padded coordinates}, dimension 0 first.  At depth
   1 and on a torus there are no strips and the trusted box is the domain."""
-  raw_modes = _raw_modes(modes, plan.dim, reach_lo, reach_hi)
+  raw_modes, faces = _raw_faces(modes, plan.dim, reach_lo, reach_hi)
   desc = _border_fused_desc(_border_desc(_periodic_desc(
       plan.dim, extent, 0, ghost_lo, ghost_hi, preserve, not_iterable),
                                          raw_modes, ()), depth, reach_lo,
                             reach_hi)
   raw = BorderFusedBoxes()
-  check(library().soda_hip_border_fused_residual_boxes(
-      ctypes.byref(plan), ctypes.byref(desc), ctypes.byref(raw)),
-        'border_fused_residual_boxes')
+  if faces is None:
+    status = library().soda_hip_border_fused_residual_boxes(
+        ctypes.byref(plan), ctypes.byref(desc), ctypes.byref(raw))
+  else:
+    status = library().soda_hip_border_fused_residual_boxes_faces(
+        ctypes.byref(plan), ctypes.byref(desc), ctypes.byref(faces),
+        ctypes.byref(raw))
+  check(status, 'border_fused_residual_boxes')
   dim = plan.dim
   box = lambda lo, hi: (tuple(lo[:dim]), tuple(hi[:dim]))
   return {'depth': raw.depth,
@@ -2087,7 +2326,7 @@ class BorderedFused(Bordered):
     wall dimension is narrower than the two parts of its strip."""
     not_iterable = self._begin(prog, extent, modes)
     st = prog.stencil
-    raw_modes = _border_modes(modes, st.dim)
+    raw_modes, faces, flat = _border_request(st, modes, constants)
     depth = int(depth)
     if depth < 0:
       raise util.InputError('border: depth < 0')
@@ -2096,13 +2335,12 @@ class BorderedFused(Bordered):
     rlo, rhi, lo, hi = border_fused_ghosts(st, modes, depth)
     desc = _border_fused_desc(_border_desc(_periodic_desc(
         st.dim, self.extent, 0, lo, hi, st.preserve_border, not_iterable),
-                                           raw_modes,
-                                           _border_constants(st, constants)),
+                                           raw_modes, flat),
                               depth, rlo, rhi)
     self._create(desc, [extend_resources, box_resources],
                  '%s with borders %s, fused %d deep' % (
                      'x'.join(map(str, self.extent)), ', '.join(self.modes),
-                     depth))
+                     depth), faces)
 
   def info(self) -> dict:
     """Bordered.info() of the handle on the domain, and: 'depth' as resolved,
@@ -2643,8 +2881,11 @@ class Program:
     program fuses deep.  `batch` = N: on N domains at once, every array
     [N, ...] (DESIGN.md 4.15; needs a program built with LowerOptions.batch;
     the fused form has no batch: with `depth` other than 1 the library's
-    refusal of a batched plan is raised).  The handle is closed with the
-    program at the latest."""
+    refusal of a batched plan is raised).  A dimension's entry of `modes` may
+    be a (low, high) pair or 'low/high', a constant a sequence of one entry
+    per dimension, each a scalar or a (low, high) pair: a mode and a constant
+    per face, here and in every run_bordered* method.  The
+    handle is closed with the program at the latest."""
     if depth == 1:
       return Bordered(self, extent, modes, constants, batch)
     if batch is not None and not self.plan.batched:
